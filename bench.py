@@ -15,7 +15,10 @@ part of the BED/TSV output; `--gather` additionally collects every record on ran
   --scaling strong  ONE assembly; its contigs are split over the ranks by cornetto_amd.dist.lpt_partition
 In both, the only data-path collective is the all-reduce of the 3 x u64 depth totals behind the coverage thresholds.
 
-Rank 0 prints ONE JSON line.  Beside the contract's fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times --steps steps and prints the contract's fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step) with the workload's configuration, the stage walls and the
+kernel times of the timed steps.  `--dump-outputs DIR` writes the records of the last timed step as DIR/<name>.npy.
+With --full the line also carries
   roofline        the dominant kernel (sdust_kernel) from HIP events on its launch stream
   cpu_baseline    the reference's own functions (oracle/_ref, "reference") or the CPU oracle ("port") on 1 host core
                   over the leading contigs of the same workload (N=1 only)
@@ -370,6 +373,40 @@ def digest(arrs):
     return h.hexdigest()
 
 
+DUMP_ROWS = 1 << 18       # rows kept per record array by --dump-outputs (a seeded sample beyond that): about 31 MB in all
+DUMP_SEED = 20240917
+
+
+def dump_outputs(R, out_dir):
+    """--dump-outputs: the four record arrays the last timed step delivered, as float64 matrices with one column per field (every
+    field is an int32, exact in float64) and global contig ids, + the counts and the coverage thresholds of that step.  An array of
+    more than DUMP_ROWS rows is a sample: DUMP_ROWS rows picked by a generator seeded with DUMP_SEED, in their order, whose row
+    numbers go beside it as <name>_rows.npy.  With several ranks every rank writes its own records (<name>.rank<r>.npy)."""
+    import cornetto_amd
+    hits, wins, ivls, recs, ctg_first = R.held
+    R.held = None
+    if recs.dtype != cornetto_amd.REGREC_DT:       # (the packed selection of the step: its rows as cornetto_cov_select() returns them)
+        recs = R.acc.unpack_regs(recs, ctg_first, R.lens_own, 2500)
+    gmap = np.asarray(R.gl_ctg, dtype=np.int64)
+    sfx = "" if R.world == 1 else ".rank%d" % R.rank
+    cap = max(1, DUMP_ROWS // R.world)
+    os.makedirs(out_dir, exist_ok=True)
+    counts = []
+    for name, arr in (("telomere_runs", hits), ("telomere_windows", wins), ("sdust_intervals", ivls), ("selected_cov_windows", recs)):
+        cols = arr.dtype.names
+        m = np.empty((len(arr), len(cols)), dtype=np.float64)
+        for j, c in enumerate(cols):
+            m[:, j] = gmap[arr[c]] if c == "ctg" else arr[c]
+        counts.append(len(arr))
+        if len(m) > cap:
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(len(m), cap, replace=False))
+            m = m[rows]
+            np.save(os.path.join(out_dir, name + "_rows" + sfx + ".npy"), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), m)
+    np.save(os.path.join(out_dir, "counts" + sfx + ".npy"), np.array(counts, dtype=np.float64))
+    np.save(os.path.join(out_dir, "cov_thresholds" + sfx + ".npy"), np.array([R.lo, R.hi], dtype=np.float64))
+
+
 class _Handoff:
     """one value from one thread to another: put() never waits, get() blocks in the lock's own wait (no GIL, no condition variable) —
     the two hand-overs of a step cost a few microseconds instead of the tens a queue.Queue takes, which a 1.5 ms step of a 395 Mb share notices"""
@@ -451,6 +488,7 @@ class Rank:
         self.sd_async = self.overlap and os.environ.get("CORNETTO_BENCH_SDUST_ASYNC", "1") == "1"
         self.sd_begun = False
         self.stepped = False
+        self.hold, self.held = False, None
         self.lag_us = float(os.environ.get("CORNETTO_BENCH_SDUST_LAG_US", "0"))
         self.lazy = self.overlap and os.environ.get("CORNETTO_BENCH_LAZY", "1") != "0"
         # cornetto_panel_step (the other thread's three calls as one, two synchronisations instead of five): measured and NOT the default — with its
@@ -715,6 +753,8 @@ class Rank:
                 self._lap("gather", t0)
         self.counts = [len(hits), len(wins), len(ivls), len(recs)]
         self.stepped = True
+        if self.hold:                                 # (--dump-outputs: the last timed step's records, as the step returned them)
+            self.held = (hits, wins, ivls, recs, ctg_first)
         if keep:
             return (hits, wins, ivls, recs), gathered
         return None
@@ -755,8 +795,9 @@ class Rank:
         self.share_probe_ms = {str(k): round(v / 4 * 1e3, 3) for k, v in seen.items()}
         self.acc2.set_share(self.share)
 
-    def timed(self, steps, warmup):
-        """`warmup` untimed steps, then exactly `steps` steps between two fences; max over ranks -> seconds"""
+    def timed(self, steps, warmup, hold_last=False):
+        """`warmup` untimed steps, then exactly `steps` steps between two fences; max over ranks -> seconds.  hold_last: the records of
+        the last timed step stay in self.held (only that step's: the arrays of earlier steps are released as they always are)"""
         for _ in range(warmup):
             self.step(False)
         self.tune_share()
@@ -765,10 +806,12 @@ class Rank:
         self.fence()
         t0 = time.perf_counter()
         counts, marks = [], [t0]
-        for _ in range(steps):
+        for i in range(steps):
+            self.hold = hold_last and i == steps - 1
             self.step(True)
             counts.append(tuple(self.counts))
             marks.append(time.perf_counter())         # (a step has delivered its results to the host when it returns)
+        self.hold = False
         self.fence()
         elapsed = time.perf_counter() - t0
         self.elapsed_local = elapsed
@@ -1293,6 +1336,80 @@ def reads_leg(R, torch, dist, cornetto_amd, gbases):
     return out
 
 
+def roofline(R, args, kavg, alg, kern, n_bases, ms_per_step):
+    """--full: the dominant kernel against the HBM roofline, with the committed counter passes of this workload beside it"""
+    dom = "sdust_kernel"
+    # which kernel family the library chose for this assembly (CORNETTO_SDUST_SIFT unset: by a sample of the bases)
+    st0 = R.acc2.sdust_stats(R.asm2, 20, 64)
+    symbol = "sd_sift" if st0 and st0.get("kernel") == "sd_sift" else "sdust_w64"
+    ach = alg[dom] / (kavg[dom] * 1e-3) / 1e9 if kavg.get(dom, 0) > 0 else 0.0
+    # HBM/fabric bytes per launch of the dominant kernel and its instruction mix: NOT measured in this run — taken from the
+    # committed rocprofv3 PMC passes of this workload (profiles/README.md), scaled to the bases of this run
+    traffic, traffic_source, traffic_ms, issue = None, None, None, None
+    cands = [PMC_FILE % (rd, args.profile, symbol) for rd in PMC_ROUNDS] + [os.path.join("profiles", "r03_pmc_traffic_%s.json" % symbol), os.path.join("profiles", "r02_pmc_traffic.json")]
+    for cand in cands:
+        try:
+            pmcs = json.load(open(os.path.join(ROOT, cand)))
+            pmc = pmcs.get(symbol) or pmcs["sdust_w64"]
+            traffic, traffic_source = round(pmc["hbm_bytes"] / pmc["bases"] * n_bases, 0), cand
+            traffic_ms = pmc.get("production_ms") or pmcs.get("production_ms")
+            break
+        except Exception:
+            continue
+    try:
+        sq_name = None
+        for rd in PMC_ROUNDS:
+            if os.path.exists(os.path.join(ROOT, SQ_FILE % (rd, args.profile, symbol))):
+                sq_name = SQ_FILE % (rd, args.profile, symbol)
+                break
+        if sq_name is None:
+            sq_name = os.path.join("profiles", "r03_sq_%s.json" % symbol)
+        sq = json.load(open(os.path.join(ROOT, sq_name)))
+        pl = sq["per_launch"]
+        issue = {"valu_insts": pl["SQ_INSTS_VALU"], "salu_insts": pl["SQ_INSTS_SALU"], "lds_insts": pl["SQ_INSTS_LDS"],
+                 "valu_busy": sq.get("valu_busy_of_kernel_time"), "per_64_bases": sq.get("per_64_bases"), "source": sq_name,
+                 "counting_build_ms": sq.get("counting_build_ms", sq.get("kernel_ms")), "production_ms": sq.get("production_ms"),
+                 "note": "a wave-64 vector instruction holds its SIMD's ALU for 4 cycles: valu_busy = 4 x SQ_INSTS_VALU / (SIMDs x cycles of the kernel); "
+                         "not measured in this run: the committed rocprofv3 --pmc passes of the same workload"}
+        # the counters describe the kernel as it was when they were collected: compare that build's time alone on the chip with this run's
+        # (ms_uncontended of the dominant kernel) and say so when they are more than 10 % apart — a stale file must not survive a kernel change
+        now_ms = kern.get(dom, {}).get("ms_uncontended")
+        if now_ms and issue.get("production_ms"):
+            issue["this_run_ms_alone"] = now_ms
+            issue["stale"] = bool(abs(issue["production_ms"] - now_ms) > 0.10 * now_ms)
+    except Exception:
+        pass
+    # ---- roofline: the dominant kernel as the contract asks (algorithmic bytes / its launch duration against the HBM peak), what really
+    # bounds it, the other streaming kernels alone and inside the step, and the whole step (6 B/base: 1 B of sequence read by sdust,
+    # 1 B read again by the telomere scan, 4 B of coverage; SURVEY 8d)
+    now_alone = kern.get(dom, {}).get("ms_uncontended")
+    stale_t = bool(traffic_ms and now_alone and abs(traffic_ms - now_alone) > 0.10 * now_alone)
+    kfr = {}
+    for kname in ("cov_blocks", "tf_scan", dom):
+        kk = kern.get(kname, {})
+        ent = {"bytes_per_base": alg[kname] / n_bases}
+        if kk.get("ms_uncontended"):
+            g = alg[kname] / (kk["ms_uncontended"] * 1e-3) / 1e9
+            ent["alone"] = {"ms": kk["ms_uncontended"], "GBps": round(g, 1), "frac": round(g / HBM_PEAK_GBS, 4)}
+        if kk.get("ms"):
+            g = alg[kname] / (kk["ms"] * 1e-3) / 1e9
+            ent["in_step"] = {"ms": kk["ms"], "GBps": round(g, 1), "frac": round(g / HBM_PEAK_GBS, 4)}
+        kfr[kname] = ent
+    step_gbps = 6.0 * n_bases / (ms_per_step * 1e-3) / 1e9
+    roof = {"bound": "hbm", "limited_by": "instruction issue and the LDS pipeline of the dominant kernel, not HBM (profiles/README.md)",
+            "kernel": dom, "kernel_symbol": symbol, "achieved": round(ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(ach / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_source,
+            "traffic_ratio": round(traffic / alg[dom], 3) if traffic else None, "traffic_source_production_ms": traffic_ms, "traffic_stale": stale_t,
+            "issue": issue,
+            "step": {"bytes_per_base": 6, "achieved_GBps": round(step_gbps, 1), "frac": round(step_gbps / HBM_PEAK_GBS, 4),
+                     "what": "all three scans of a step: 6 algorithmic bytes per base (SURVEY 8d) x bases / ms_per_step against the HBM peak"},
+            "kernels": kfr,
+            "note": "sdust is integer work per base, bound by instruction issue and LDS cycles, not by HBM (profiles/r05_<profile>_sq_<kernel>.json); achieved / peak / frac are "
+                    "against the HBM roofline as the contract asks (1 B/base algorithmic). traffic and issue are not measured in this run: "
+                    "the committed rocprofv3 PMC figures scaled by bases, flagged stale when that build's kernel time differs from this run's by more than 10 %"}
+    return roof
+
+
 def emulate_ranks(R, ns, steps, t1_ms):
     """Strong scaling modelled on ONE GPU: for N in ns the contigs are split exactly as an N-rank run splits them
     (cornetto_amd.dist.lpt_partition), and every rank's share is run as its own resident workload, one after the other, with
@@ -1344,30 +1461,32 @@ def device_identity(torch, idx):
     return "ordinal:%d" % idx
 
 
-def collectives_info(R, dist, torch, elapsed_local, steps):
+def collectives_info(R, dist, torch, elapsed_local, steps, latency=True):
     """who ran where and what the exchange costs: backend, world size, (host, device) of every rank, per-rank step times,
-    the latency of the 3 x int64 all-reduce.  Rank 0 gets the dict; every rank gets `shared` (two ranks on one device)."""
+    the latency of the 3 x int64 all-reduce (latency=False: not measured).  Rank 0 gets the dict; every rank gets `shared`
+    (two ranks on one device)."""
     import socket
     me = (socket.gethostname(), device_identity(torch, R.local_dev), round(elapsed_local / steps * 1e3, 3))
     allr = [None] * R.world
     dist.all_gather_object(allr, me)
-    t = torch.tensor([1, 2, 3], dtype=torch.int64, device=R.cdev)
-    for _ in range(5):
-        dist.all_reduce(t)
-    if R.cdev.type == "cuda":
-        torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    reps = 50
-    for _ in range(reps):
-        dist.all_reduce(t)
-    if R.cdev.type == "cuda":
-        torch.cuda.synchronize()
-    ar_us = (time.perf_counter() - t0) / reps * 1e6
     devs = [(h, d) for h, d, _ in allr]
     shared = len(set(devs)) != len(devs)
     info = {"backend": dist.get_backend(), "world": dist.get_world_size(), "devices": ["%s/%s" % d for d in devs],
-            "distinct_devices": not shared, "per_rank_ms": [x[2] for x in allr], "allreduce_3xi64_us": round(ar_us, 1),
+            "distinct_devices": not shared, "per_rank_ms": [x[2] for x in allr],
             "data_path": "strong: one all-reduce of 3 x int64 per step (boringbits_main.c:293-294 -> :518-519); weak: none; --gather: all_gather of counts + gather of the record arrays to rank 0"}
+    if latency:
+        t = torch.tensor([1, 2, 3], dtype=torch.int64, device=R.cdev)
+        for _ in range(5):
+            dist.all_reduce(t)
+        if R.cdev.type == "cuda":
+            torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        reps = 50
+        for _ in range(reps):
+            dist.all_reduce(t)
+        if R.cdev.type == "cuda":
+            torch.cuda.synchronize()
+        info["allreduce_3xi64_us"] = round((time.perf_counter() - t0) / reps * 1e6, 1)
     return info, shared
 
 
@@ -1479,7 +1598,15 @@ def main():
     ap.add_argument("--gather", action="store_true", help="also gather every result record to rank 0 inside the step (not part of the path: each rank owns the output of its contigs)")
     ap.add_argument("--allreduce-always", action="store_true", help="weak scaling: all-reduce the depth totals as well (treats the N assemblies as one)")
     ap.add_argument("--serial", action="store_true", help="run the stages one after the other on one stream (per-kernel timing without overlap)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline figure, each in runs of its own: the serial per-kernel pass and the roofline, "
+                    "the determinism digests, the CPU leg with its parity check, the scaling model, the cold step of a next assembly, the CLI end to end, the "
+                    "other workload profiles, the read-level leg, the all-reduce latency and (--gpus > 1) the second measurement.  Without it a run sets up, "
+                    "warms up, times --steps steps and prints the line; the --no-* / --check-steps / --emulate-ranks / --reads-gbases options shape --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps: the records the last timed step delivered as DIR/<name>.npy "
+                    "(float64, one column per field; a seeded sample of %d rows of a larger array)" % DUMP_ROWS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.scaling is None:
         args.scaling = "strong" if args.gpus > 1 else "weak"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1502,24 +1629,26 @@ def main():
     R.step(False)                                   # the first step of a resident assembly builds its decomposition tables
     first_step_ms = (time.perf_counter() - t_first) * 1e3
 
-    elapsed = R.timed(args.steps, args.warmup)
+    elapsed = R.timed(args.steps, args.warmup, hold_last=args.dump_outputs is not None)
     elapsed_local = R.elapsed_local
     steps_ms0 = list(getattr(R, "step_ms", []))        # (of the headline measurement: later legs time steps of their own)
-    serial = R.serial_kernel_times()
     n_bases = R.my_bases
 
     coll, shared = None, False
     if world > 1:
-        coll, shared = collectives_info(R, dist, torch, elapsed_local, args.steps)
+        coll, shared = collectives_info(R, dist, torch, elapsed_local, args.steps, latency=args.full)
         if shared and not args.allow_shared_device:
             if rank == 0:
                 sys.stderr.write("bench.py: two ranks share one device (%s): refusing to report a multi-GPU number; --allow-shared-device is for tests\n" % coll["devices"])
             R.unload()
             R.close()
             sys.exit(3)
+    if args.dump_outputs is not None:
+        dump_outputs(R, args.dump_outputs)
+    serial = R.serial_kernel_times() if args.full else None
 
     # ---- determinism: digest of the four result arrays of every step of an extra, untimed run ---------------
-    nchk = min(args.steps, 20) if args.check_steps < 0 else args.check_steps
+    nchk = 0 if not args.full else min(args.steps, 20) if args.check_steps < 0 else args.check_steps
     det, last, gathered_digests = None, None, None
     if nchk > 0:
         digs = []
@@ -1549,75 +1678,7 @@ def main():
         ms_per_step = elapsed / args.steps * 1e3
         value = R.job_bases / (elapsed / args.steps) / 1e9
         kavg, alg, kern = kernel_table(R, serial, n_bases)
-        dom = "sdust_kernel"
-        # which kernel family the library chose for this assembly (CORNETTO_SDUST_SIFT unset: by a sample of the bases)
-        st0 = R.acc2.sdust_stats(R.asm2, 20, 64)
-        symbol = "sd_sift" if st0 and st0.get("kernel") == "sd_sift" else "sdust_w64"
-        ach = alg[dom] / (kavg[dom] * 1e-3) / 1e9 if kavg.get(dom, 0) > 0 else 0.0
-        # HBM/fabric bytes per launch of the dominant kernel and its instruction mix: NOT measured in this run — taken from the
-        # committed rocprofv3 PMC passes of this workload (profiles/README.md), scaled to the bases of this run
-        traffic, traffic_source, traffic_ms, issue = None, None, None, None
-        cands = [PMC_FILE % (rd, args.profile, symbol) for rd in PMC_ROUNDS] + [os.path.join("profiles", "r03_pmc_traffic_%s.json" % symbol), os.path.join("profiles", "r02_pmc_traffic.json")]
-        for cand in cands:
-            try:
-                pmcs = json.load(open(os.path.join(ROOT, cand)))
-                pmc = pmcs.get(symbol) or pmcs["sdust_w64"]
-                traffic, traffic_source = round(pmc["hbm_bytes"] / pmc["bases"] * n_bases, 0), cand
-                traffic_ms = pmc.get("production_ms") or pmcs.get("production_ms")
-                break
-            except Exception:
-                continue
-        try:
-            sq_name = None
-            for rd in PMC_ROUNDS:
-                if os.path.exists(os.path.join(ROOT, SQ_FILE % (rd, args.profile, symbol))):
-                    sq_name = SQ_FILE % (rd, args.profile, symbol)
-                    break
-            if sq_name is None:
-                sq_name = os.path.join("profiles", "r03_sq_%s.json" % symbol)
-            sq = json.load(open(os.path.join(ROOT, sq_name)))
-            pl = sq["per_launch"]
-            issue = {"valu_insts": pl["SQ_INSTS_VALU"], "salu_insts": pl["SQ_INSTS_SALU"], "lds_insts": pl["SQ_INSTS_LDS"],
-                     "valu_busy": sq.get("valu_busy_of_kernel_time"), "per_64_bases": sq.get("per_64_bases"), "source": sq_name,
-                     "counting_build_ms": sq.get("counting_build_ms", sq.get("kernel_ms")), "production_ms": sq.get("production_ms"),
-                     "note": "a wave-64 vector instruction holds its SIMD's ALU for 4 cycles: valu_busy = 4 x SQ_INSTS_VALU / (SIMDs x cycles of the kernel); "
-                             "not measured in this run: the committed rocprofv3 --pmc passes of the same workload"}
-            # the counters describe the kernel as it was when they were collected: compare that build's time alone on the chip with this run's
-            # (ms_uncontended of the dominant kernel) and say so when they are more than 10 % apart — a stale file must not survive a kernel change
-            now_ms = kern.get(dom, {}).get("ms_uncontended")
-            if now_ms and issue.get("production_ms"):
-                issue["this_run_ms_alone"] = now_ms
-                issue["stale"] = bool(abs(issue["production_ms"] - now_ms) > 0.10 * now_ms)
-        except Exception:
-            pass
-        # ---- roofline: the dominant kernel as the contract asks (algorithmic bytes / its launch duration against the HBM peak), what really
-        # bounds it, the other streaming kernels alone and inside the step, and the whole step (6 B/base: 1 B of sequence read by sdust,
-        # 1 B read again by the telomere scan, 4 B of coverage)
-        now_alone = kern.get(dom, {}).get("ms_uncontended")
-        stale_t = bool(traffic_ms and now_alone and abs(traffic_ms - now_alone) > 0.10 * now_alone)
-        kfr = {}
-        for kname in ("cov_blocks", "tf_scan", dom):
-            kk = kern.get(kname, {})
-            ent = {"bytes_per_base": alg[kname] / n_bases}
-            if kk.get("ms_uncontended"):
-                g = alg[kname] / (kk["ms_uncontended"] * 1e-3) / 1e9
-                ent["alone"] = {"ms": kk["ms_uncontended"], "GBps": round(g, 1), "frac": round(g / HBM_PEAK_GBS, 4)}
-            if kk.get("ms"):
-                g = alg[kname] / (kk["ms"] * 1e-3) / 1e9
-                ent["in_step"] = {"ms": kk["ms"], "GBps": round(g, 1), "frac": round(g / HBM_PEAK_GBS, 4)}
-            kfr[kname] = ent
-        step_gbps = 6.0 * n_bases / (ms_per_step * 1e-3) / 1e9
-        roof = {"bound": "hbm", "limited_by": "instruction issue and the LDS pipeline of the dominant kernel, not HBM (profiles/README.md)",
-                "kernel": dom, "kernel_symbol": symbol, "achieved": round(ach, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(ach / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_source,
-                "traffic_ratio": round(traffic / alg[dom], 3) if traffic else None, "traffic_source_production_ms": traffic_ms, "traffic_stale": stale_t,
-                "issue": issue,
-                "step": {"bytes_per_base": 6, "achieved_GBps": round(step_gbps, 1), "frac": round(step_gbps / HBM_PEAK_GBS, 4),
-                         "what": "all three scans of a step: 6 algorithmic bytes per base (SURVEY 8d) x bases / ms_per_step against the HBM peak"},
-                "kernels": kfr,
-                "note": "sdust is integer work per base, bound by instruction issue and LDS cycles, not by HBM (profiles/r05_<profile>_sq_<kernel>.json); achieved / peak / frac are "
-                        "against the HBM roofline as the contract asks (1 B/base algorithmic). traffic and issue are not measured in this run: "
-                        "the committed rocprofv3 PMC figures scaled by bases, flagged stale when that build's kernel time differs from this run's by more than 10 %"}
+        roof = roofline(R, args, kavg, alg, kern, n_bases, ms_per_step) if args.full else None
         sm_ = sorted(steps_ms0) if steps_ms0 else []
         spread = {"min": round(sm_[0], 3), "median": round(sm_[len(sm_) // 2], 3), "max": round(sm_[-1], 3), "steps": len(sm_),
                   "what": "host time from one step's return to the next's on rank 0 inside the timed region (ms_per_step is the region / steps)"} if sm_ else None
@@ -1651,6 +1712,8 @@ def main():
             "first_step_ms": round(first_step_ms, 3), "accel_warm_ms": round(R.warm_ms, 2),
             "sdust_share_percent": getattr(R, "share", None), "sdust_share_probe_ms": getattr(R, "share_probe_ms", None),
         }
+        if not args.full:
+            del line["roofline"]
         if coll:
             line["collectives"] = coll
         if det:
@@ -1658,7 +1721,7 @@ def main():
         if gathered_digests:
             line["gathered_digests"] = gathered_digests
     ok = True
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         base, results = cpu_reference_leg(R.bases, R.depth, R.mq, R.offs, R.lens, R.own, int(args.cpu_sample_mbases * 1e6))
         line["cpu_baseline"] = base
         if last is None:
@@ -1672,10 +1735,10 @@ def main():
     if det and not det["identical"]:
         ok = False
     last = None
-    if rank == 0 and world == 1 and args.emulate_ranks.strip():
+    if args.full and rank == 0 and world == 1 and args.emulate_ranks.strip():
         ns = [int(x) for x in args.emulate_ranks.split(",") if x.strip()]
         line["scaling_model"] = emulate_ranks(R, ns, max(3, min(args.steps, 10)), line["ms_per_step"])
-    if world > 1 and not args.no_second:
+    if args.full and world > 1 and not args.no_second:
         # the other scaling mode, with the gather of every record to rank 0: BASELINE config 4 is "8 assemblies, RCCL gather of BED intervals"
         other = "weak" if args.scaling == "strong" else "strong"
         st2 = max(3, min(args.steps, 10))
@@ -1684,7 +1747,7 @@ def main():
             line["second"] = {"scaling": other, "gather": True, "steps": st2, "ms_per_step": round(el2 / st2 * 1e3, 3),
                               "value": round(R.job_bases / (el2 / st2) / 1e9, 4), "unit": "Gbases/s", "bases_job": R.job_bases,
                               "stage_wall_ms": {k: round(float(np.mean(v)), 3) for k, v in R.wall.items()}}
-    if rank == 0 and world == 1 and getattr(R, "plan", None) is None:
+    if args.full and rank == 0 and world == 1 and getattr(R, "plan", None) is None:
         # the cold pass once more, in a process that is warm: the same resident inputs wrapped as new objects (no decomposition tables, no result
         # counts to size anything by) — what a second assembly costs a panel run that scans eight (BASELINE config 4); first_step_ms above is
         # the first step of the process (code objects, workspaces and pinned pools come into being in it)
@@ -1696,9 +1759,9 @@ def main():
         line["cold_step_ms_next_assembly"] = round((time.perf_counter() - t_c) * 1e3, 3)
         line["cold_step_next_assembly_stage_ms"] = {k: round(v[0], 3) for k, v in R.wall.items()}
         R.wall = keep_wall
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if args.full and rank == 0 and world == 1 and not args.no_e2e:
         line["e2e"] = e2e_cli(R, cornetto_amd)
-    if rank == 0 and world == 1 and not args.no_profiles:
+    if args.full and rank == 0 and world == 1 and not args.no_profiles:
         if R.scaling != args.scaling or R.profile != args.profile:
             R.unload()
             R.load(args.profile, args.scaling)
@@ -1719,7 +1782,7 @@ def main():
                 ok = False
         line["profiles"] = profs
     R.unload()
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if args.full and rank == 0 and world == 1 and not args.no_e2e:
         line["e2e"]["noboringbits"] = e2e_noboringbits(R, torch, cornetto_amd)
         e2 = line["e2e"]
         e2_ok = [e2.get("sdust", {}).get("stdout_equals_step_records", True), e2.get("telofind", {}).get("stdout_equals_step_records", True),
@@ -1728,7 +1791,7 @@ def main():
         e2["parity_ok"] = bool(all(e2_ok))
         if not e2["parity_ok"]:
             ok = False
-    if not args.no_reads:                               # every rank: N > 1 streams one FASTQ stream sharded by cumulative bases (config 5)
+    if args.full and not args.no_reads:                     # every rank: N > 1 streams one FASTQ stream sharded by cumulative bases (config 5)
         rd = reads_leg(R, torch, dist, cornetto_amd, args.reads_gbases)
         if rank == 0:
             line["reads"] = rd

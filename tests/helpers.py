@@ -230,6 +230,77 @@ def tricky_fastx(rng, n_rec, strict=False, lowc=0.0):
     return text
 
 
+# ---- the random cases of the differential tests against the reference's own code (tests/test_oracle_golden.py).  Where oracle/_ref is
+# not built the tests take the cases and the reference's outputs recorded by tests/golden/make_golden_random.py (ref_*_random.npz)
+def sdust_random_cases():
+    """-> [(sequence uint8, T, W)]: 300 sequences of up to 3000 bases (uniform ACGT, any letter, STR mosaics, two letters)"""
+    rng = np.random.default_rng(7)
+    alpha = np.frombuffer(b"ACGTacgtNNRY", dtype=np.uint8)
+    cases = []
+    for it in range(300):
+        n = int(rng.integers(0, 3000))
+        kind = it % 4
+        if kind == 0:
+            s = alpha[rng.integers(0, 4, size=n)]
+        elif kind == 1:
+            s = alpha[rng.integers(0, len(alpha), size=n)]
+        elif kind == 2:   # STR mosaic
+            parts = []
+            while sum(map(len, parts)) < n:
+                u = alpha[rng.integers(0, 4, size=int(rng.integers(1, 6)))]
+                parts.append(np.tile(u, int(rng.integers(1, 40))))
+                if rng.random() < 0.2:
+                    parts.append(np.frombuffer(b"N" * int(rng.integers(1, 5)), dtype=np.uint8))
+            s = np.concatenate(parts)[:n] if parts else np.zeros(0, np.uint8)
+        else:             # two-letter low complexity
+            s = alpha[rng.integers(0, 2, size=n)]
+        s = np.ascontiguousarray(s, dtype=np.uint8)
+        T = int(rng.choice([20, 20, 10, 5, 30]))
+        W = int(rng.choice([64, 64, 32, 16, 100, 8]))
+        cases.append((s, T, W))
+    return cases
+
+
+def ref_sdust(refso, cases):
+    """the reference's sdust() (oracle/_ref/libcornetto_ref.so) on every case -> [uint64 intervals]"""
+    import ctypes as C
+    ref = C.CDLL(refso)
+    ref.sdust.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    ref.sdust.restype = C.POINTER(C.c_uint64)
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    out = []
+    for s, T, W in cases:
+        cnt = C.c_int()
+        r = ref.sdust(None, s.tobytes() + b"\0", len(s), T, W, C.byref(cnt))
+        out.append(np.array([r[i] for i in range(cnt.value)], dtype=np.uint64))
+        libc.free(r)
+    return out
+
+
+def fastx_random_texts():
+    """-> [bytes]: 150 FASTA/FASTQ texts of up to 11 records (tricky_fastx; every third one strict FASTQ)"""
+    rng = np.random.default_rng(3)
+    return [tricky_fastx(rng, int(rng.integers(0, 12)), strict=(it % 3 == 0)) for it in range(150)]
+
+
+def seq_prints_records(text, recs, rc):
+    """`seq` prints stale memory for FASTA records and for a read whose quality the end of the file cuts off"""
+    return all(q is not None for _, _, _, q in recs) and not text.endswith(b"+\n") and rc == -1
+
+
+def pack_bytes(items):
+    """[bytes-like or None] -> (uint8 concatenation, int64 offsets[n + 1], bool present[n]) for an .npz fixture"""
+    parts = [np.frombuffer(bytes(x), dtype=np.uint8) if x is not None else np.zeros(0, np.uint8) for x in items]
+    offs = np.zeros(len(parts) + 1, dtype=np.int64)
+    offs[1:] = np.cumsum([len(p) for p in parts])
+    return (np.concatenate(parts) if parts else np.zeros(0, np.uint8)), offs, np.array([x is not None for x in items], dtype=bool)
+
+
+def unpack_bytes(data, offs, present=None):
+    return [bytes(data[offs[i]:offs[i + 1]]) if present is None or present[i] else None for i in range(len(offs) - 1)]
+
+
 # ---- the CLI goldens (stdout of the unmodified reference: tests/golden/make_golden.py), shared by the device tests
 # (tests/test_gpu_cli.py) and the host-path tests (tests/test_cli_accel_no.py)
 FASTA_SIDE = [

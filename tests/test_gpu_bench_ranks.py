@@ -15,7 +15,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--gbases", "0.05", "--steps", "2", "--warmup", "1", "--check-steps", "2", "--gather", "--no-cpu", "--no-profiles", "--no-e2e", "--no-reads",
+COMMON = ["--full", "--gbases", "0.05", "--steps", "2", "--warmup", "1", "--check-steps", "2", "--gather", "--no-cpu", "--no-profiles", "--no-e2e", "--no-reads",
           "--emulate-ranks", "", "--no-second"]
 
 
@@ -132,7 +132,7 @@ def test_plain_command_starts_its_own_ranks():
     (`reads`: one FASTQ stream sharded over the ranks by cumulative bases) are in it"""
     shared = [] if _n_gpus() >= 2 else ["--allow-shared-device"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--gbases", "0.05", "--steps", "2", "--warmup", "1", "--check-steps", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--gbases", "0.05", "--steps", "2", "--warmup", "1", "--check-steps", "2",
            "--reads-gbases", "0.08"] + shared
     p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=1500, cwd=ROOT)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]

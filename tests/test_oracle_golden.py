@@ -1,7 +1,6 @@
 """CPU: the oracle restatement (oracle/oracle.c) against golden stdout of the unmodified reference
 (tests/golden/*.exp, made by tests/golden/make_golden.py) and, where oracle/_ref is present, directly
 against the reference's own functions through ctypes.  This is the parity PIN of the oracle."""
-import ctypes as C
 import os
 import sys
 
@@ -9,7 +8,8 @@ import numpy as np
 import pytest
 
 import oracle_bind as ob
-from helpers import (fmt_sdust, fmt_telofind, fmt_telowin, golden, read_bedgraph_pair, read_fastx)
+from helpers import (fastx_random_texts, fmt_sdust, fmt_telofind, fmt_telowin, golden, read_bedgraph_pair, read_fastx, ref_sdust, sdust_random_cases,
+                     seq_prints_records, unpack_bytes)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -245,42 +245,26 @@ def test_bigenough_golden(golden_dir, chroms, bed, T, exp_bed, exp_csv):
 REFSO = os.path.join(ROOT, "oracle", "_ref", "libcornetto_ref.so")
 
 
-@pytest.mark.skipif(not os.path.exists(REFSO), reason="oracle/_ref not built (no /root/reference here)")
-def test_sdust_vs_reference_function_random():
-    ref = C.CDLL(REFSO)
-    ref.sdust.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
-    ref.sdust.restype = C.POINTER(C.c_uint64)
-    libc = C.CDLL(None)
-    libc.free.argtypes = [C.c_void_p]
-    rng = np.random.default_rng(7)
-    alpha = np.frombuffer(b"ACGTacgtNNRY", dtype=np.uint8)
-    for it in range(300):
-        n = int(rng.integers(0, 3000))
-        kind = it % 4
-        if kind == 0:
-            s = alpha[rng.integers(0, 4, size=n)]
-        elif kind == 1:
-            s = alpha[rng.integers(0, len(alpha), size=n)]
-        elif kind == 2:   # STR mosaic
-            parts = []
-            while sum(map(len, parts)) < n:
-                u = alpha[rng.integers(0, 4, size=int(rng.integers(1, 6)))]
-                parts.append(np.tile(u, int(rng.integers(1, 40))))
-                if rng.random() < 0.2:
-                    parts.append(np.frombuffer(b"N" * int(rng.integers(1, 5)), dtype=np.uint8))
-            s = np.concatenate(parts)[:n] if parts else np.zeros(0, np.uint8)
-        else:             # two-letter low complexity
-            s = alpha[rng.integers(0, 2, size=n)]
-        s = np.ascontiguousarray(s, dtype=np.uint8)
-        T = int(rng.choice([20, 20, 10, 5, 30]))
-        W = int(rng.choice([64, 64, 32, 16, 100, 8]))
-        cnt = C.c_int()
-        buf = s.tobytes() + b"\0"
-        r = ref.sdust(None, buf, len(s), T, W, C.byref(cnt))
-        exp = np.array([r[i] for i in range(cnt.value)], dtype=np.uint64)
-        libc.free(r)
+def _sdust_random_cases_and_ref(golden_dir):
+    """[(sequence, T, W, the reference's intervals)]: the reference's sdust() where oracle/_ref is built (and the recording must agree with
+    it), else the cases and outputs recorded from it (tests/golden/make_golden_random.py)"""
+    z = np.load(os.path.join(golden_dir, "ref_sdust_random.npz"))
+    seqs = [np.frombuffer(b, dtype=np.uint8) for b in unpack_bytes(z["seqs"], z["seq_offs"])]
+    rec = [(s, int(t), int(w), z["ivls"][z["ivl_offs"][i]:z["ivl_offs"][i + 1]]) for i, (s, t, w) in enumerate(zip(seqs, z["T"], z["W"]))]
+    if not os.path.exists(REFSO):
+        return rec
+    live = [(s, T, W) for s, T, W, _ in rec]
+    assert all(np.array_equal(a, r[3]) for a, r in zip(ref_sdust(REFSO, live), rec)), "tests/golden/ref_sdust_random.npz is stale"
+    cases = sdust_random_cases()
+    return [(s, T, W, exp) for (s, T, W), exp in zip(cases, ref_sdust(REFSO, cases))]
+
+
+def test_sdust_vs_reference_function_random(golden_dir):
+    cases = _sdust_random_cases_and_ref(golden_dir)
+    assert len(cases) == 300
+    for it, (s, T, W, exp) in enumerate(cases):
         got = ob.sdust(s, T, W)
-        assert np.array_equal(got, exp), (it, n, T, W)
+        assert np.array_equal(got, exp), (it, len(s), T, W)
 
 
 def _bench_cpu_leg(kind, monkeypatch):
@@ -400,24 +384,40 @@ def test_fastx_framing_status_codes():
 REFBIN = os.path.join(ROOT, "oracle", "_ref", "cornetto")
 
 
-@pytest.mark.skipif(not os.path.exists(REFBIN), reason="oracle/_ref not built (no /root/reference here)")
-def test_fastx_framing_vs_reference_binary_random(tmp_path):
+def test_fastx_framing_vs_reference_binary_random(tmp_path, golden_dir):
     """`fa2bed` prints every record's name and length, `seq -m 0` the four strings; FASTA records and a read whose
     quality is cut off by the end of the file make `seq` print stale memory, so those texts are
-    compared through fa2bed only."""
+    compared through fa2bed only.  The reference binary where oracle/_ref is built (and the recording must agree with it), else
+    its stdout recorded on the same texts (tests/golden/make_golden_random.py)."""
     import subprocess
-    from helpers import fmt_seq, fmt_fa2bed, tricky_fastx
-    rng = np.random.default_rng(3)
+    from helpers import fmt_seq, fmt_fa2bed
+    z = np.load(os.path.join(golden_dir, "ref_fastx_random.npz"))
+    rec_texts = unpack_bytes(z["texts"], z["text_offs"])
+    rec_fa2bed, rec_seq = unpack_bytes(z["fa2bed"], z["fa2bed_offs"]), unpack_bytes(z["seq"], z["seq_offs"], z["seq_present"])
     f = str(tmp_path / "t.fq")
-    n_seq = 0
-    for it in range(150):
-        text = tricky_fastx(rng, int(rng.integers(0, 12)), strict=(it % 3 == 0))
+
+    def ref(args, text):
         open(f, "wb").write(text)
+        return subprocess.run([REFBIN] + args + [f], capture_output=True).stdout
+
+    if os.path.exists(REFBIN):
+        for text, a, q in zip(rec_texts, rec_fa2bed, rec_seq):
+            assert ref(["fa2bed"], text) == a and (q is None or ref(["seq", "-m", "0"], text) == q), "tests/golden/ref_fastx_random.npz is stale"
+        texts = fastx_random_texts()
+        fa2bed = lambda it: ref(["fa2bed"], texts[it])                  # noqa: E731
+        seq = lambda it: ref(["seq", "-m", "0"], texts[it])             # noqa: E731
+    else:
+        texts = rec_texts
+        fa2bed = lambda it: rec_fa2bed[it]                              # noqa: E731
+        seq = lambda it: rec_seq[it]                                    # noqa: E731
+    assert len(texts) == 150
+    n_seq = 0
+    for it, text in enumerate(texts):
         recs, rc = ob.fastx_parse(text)
-        assert subprocess.run([REFBIN, "fa2bed", f], capture_output=True).stdout == fmt_fa2bed(recs), it
-        if all(q is not None for _, _, _, q in recs) and not text.endswith(b"+\n") and rc == -1:
+        assert fa2bed(it) == fmt_fa2bed(recs), it
+        if seq_prints_records(text, recs, rc):
             n_seq += 1
-            assert subprocess.run([REFBIN, "seq", "-m", "0", f], capture_output=True).stdout == fmt_seq(recs, 0), it
+            assert seq(it) == fmt_seq(recs, 0), it
     assert n_seq > 50
 
 

@@ -2,7 +2,7 @@
 V=$1; ON=$2; OFF=$3; SH=${4:-76}
 Q="--steps 30 --warmup 3 --no-cpu --no-e2e --no-reads --no-profiles --check-steps 0"
 for val in $ON $OFF $ON $OFF; do
-echo -n "$V=$val share $SH: "; env $V=$val python bench.py $Q --emulate-ranks 8 --sdust-share $SH 2>/dev/null | python -c "
+echo -n "$V=$val share $SH: "; env $V=$val python bench.py $Q --full --emulate-ranks 8 --sdust-share $SH 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 m=d['scaling_model']['8']

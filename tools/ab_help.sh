@@ -3,7 +3,7 @@
 export CORNETTO_LIB=${CORNETTO_LIB:-$PWD/cornetto_amd/libcornetto_hip_dev.so}
 Q="--steps 30 --warmup 3 --no-cpu --no-e2e --no-reads --no-profiles --check-steps 0"
 for sh in ${@:-72 76}; do for hb in 85 0 85 0; do
-echo -n "share $sh help_below $hb: "; CORNETTO_SDUST_HELP_BELOW=$hb python bench.py $Q --emulate-ranks 8 --sdust-share $sh 2>/dev/null | python -c "
+echo -n "share $sh help_below $hb: "; CORNETTO_SDUST_HELP_BELOW=$hb python bench.py $Q --full --emulate-ranks 8 --sdust-share $sh 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 m=d['scaling_model']['8']

@@ -1,5 +1,5 @@
 # bash tools/ab_model.sh "<ENV=VAL or ->" ...: the strong-scaling model (8 shares of the 3.16 Gbp assembly, one after the other) with / without a switch
-B="--no-cpu --no-profiles --no-e2e --no-reads --no-second --emulate-ranks 8 --steps 20 --warmup 5"
+B="--full --no-cpu --no-profiles --no-e2e --no-reads --no-second --emulate-ranks 8 --steps 20 --warmup 5"
 cat > /tmp/ab_model_fmt.py <<'PY'
 import sys, json
 tag = sys.argv[1]
