@@ -25,6 +25,7 @@ IVL_DT = np.dtype([("ctg", "<i4"), ("start", "<i4"), ("finish", "<i4")])
 TELROW_DT = np.dtype([("ctg", "<i4"), ("start", "<i4"), ("end", "<i4"), ("matched", "<i4")])
 FQREC_DT = np.dtype([("head", "<i8"), ("seq", "<i8"), ("qual", "<i8"), ("len", "<i4"), ("name_len", "<i4"),
                      ("comment_len", "<i4"), ("keep", "<i4")])
+EMITREC_DT = np.dtype([("ctg", "<i4"), ("rc", "<i4"), ("head", "<i8"), ("head_len", "<i8")])
 FAREC_DT = np.dtype([("head", "<i8"), ("len", "<i8"), ("name_len", "<i4"), ("pad", "<i4")])
 REG_DT = np.dtype([("st", "<i4"), ("end", "<i4"), ("depth", "<i4"), ("mq_depth", "<i4")])
 REGREC_DT = np.dtype([("ctg", "<i4"), ("st", "<i4"), ("end", "<i4"), ("depth", "<i4"), ("mq_depth", "<i4")])
@@ -110,6 +111,10 @@ def lib(dev=False):
         "cornetto_text_put": (C.c_int, [vp, vp, vp, i64, i64, C.c_int]),
         "cornetto_text_wait": (C.c_int, [vp, vp, C.c_int]),
         "cornetto_fasta_split_text": (C.c_int, [vp, vp, i64, C.c_int, pp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), pp]),
+        "cornetto_emit_open": (C.c_int, [vp, vp, vp, i64, vp, i64, pp, C.POINTER(i64)]),
+        "cornetto_emit_get": (C.c_int, [vp, vp, vp, i64, i64, C.c_int]),
+        "cornetto_emit_wait": (C.c_int, [vp, vp, C.c_int]),
+        "cornetto_emit_free": (None, [vp, vp]),
         "cornetto_asm_upload": (C.c_int, [vp, vp, vp, i32, pp]),
         "cornetto_asm_wrap": (C.c_int, [vp, vp, vp, vp, i32, pp]),
         "cornetto_asm_free": (None, [vp, vp]),
@@ -276,6 +281,42 @@ class Accel:
         out = C.c_void_p()
         self._chk(self.L.cornetto_asm_wrap(self.h, dev_ptr, offsets.ctypes.data, lens.ctypes.data, len(lens), C.byref(out)))
         return _Resident(self, out, self.L.cornetto_asm_free, lens)
+
+    def emit(self, asm, recs, heads, windows, slots=4):
+        """the fixasm output text of `asm` (cornetto_emit_*): recs = [(ctg, rc, head, head_len)] (EMITREC_DT fields), heads = the header bytes
+        -> (total bytes of the text, [bytes of every (at, n) of `windows`]); the windows go round the slots, each through a pinned buffer"""
+        r = np.array([tuple(x) for x in recs], dtype=EMITREC_DT) if len(recs) else np.zeros(1, dtype=EMITREC_DT)
+        hb = np.frombuffer(bytes(heads), dtype=np.uint8) if len(heads) else np.zeros(1, dtype=np.uint8)
+        e, total = C.c_void_p(), C.c_int64()
+        self._chk(self.L.cornetto_emit_open(self.h, asm.ptr, r.ctypes.data, len(recs), hb.ctypes.data, len(heads), C.byref(e), C.byref(total)))
+        out, pins, pend = [], [None] * slots, [None] * slots
+        try:
+            for k, (at, n) in enumerate(windows):
+                s = k % slots
+                if pend[s] is not None:
+                    self._chk(self.L.cornetto_emit_wait(self.h, e, s))
+                    out[pend[s]] = C.string_at(pins[s], out[pend[s]])
+                    self.L.cornetto_pinned_free(pins[s])
+                pins[s] = self.L.cornetto_pinned_alloc(max(1, n))
+                if not pins[s]:
+                    raise MemoryError("cornetto_pinned_alloc(%d)" % n)
+                self._chk(self.L.cornetto_emit_get(self.h, e, pins[s], at, n, s))
+                pend[s] = len(out)
+                out.append(n)
+            for s in range(slots):
+                if pend[s] is not None:
+                    self._chk(self.L.cornetto_emit_wait(self.h, e, s))
+                    out[pend[s]] = C.string_at(pins[s], out[pend[s]])
+                    pend[s] = None
+        finally:
+            for s in range(slots):
+                if pend[s] is not None:
+                    self.L.cornetto_emit_wait(self.h, e, s)
+            self.L.cornetto_emit_free(self.h, e)
+            for p in pins:
+                if p:
+                    self.L.cornetto_pinned_free(p)
+        return total.value, out
 
     def fastq_split(self, text, final=True, min_len=0, want_reads=False):
         """text: bytes-like FASTQ piece (or (address, size) of e.g. pinned memory) -> (records FQREC_DT, consumed bytes,

@@ -136,6 +136,20 @@ void cli_batch_take(cli_batch_t *b, const char *name, cli_str_t *seq); /* takes 
 void cli_batch_clear(cli_batch_t *b);
 int64_t cli_batch_limit(void); /* $CORNETTO_BATCH_BASES, default 4e9 */
 
+/* ---- the FASTA/FASTQ driver of the device path (cli/fasta_cmds.c) ---- */
+typedef struct {
+    const char *name;   /* not NUL-terminated */
+    int32_t name_len;
+    int64_t len;
+} cli_recname_t;
+
+/* scan the resident sequences `a` (record i of it = r[i]) and print the sub-command's lines */
+typedef void (*scan_fn)(cornetto_accel_t *h, const cli_recname_t *r, int64_t n, const cornetto_asm_t *a, void *arg);
+
+/* every record of the FASTA/FASTQ(+gz) file `path`, framed on the device where the text allows it (else by the sequential reader), handed
+ * to `scan` in input order, a batch at a time; must_open: a file that cannot be opened is the reference's F_CHK error (exit 1) */
+void stream_records(const char *path, int must_open, scan_fn scan, void *arg);
+
 /* ---- the host path (cli/host_backend.c): plain sequential C99 for every scan, chosen with --accel=no (noboringbits / boringbits, the
  * reference's own switch: src/boringbits_main.c:627-632) or CORNETTO_ACCEL=no (every sub-command) — never by itself ---- */
 int cli_host_mode(void);
@@ -175,5 +189,6 @@ int telomere_breaks_main(int argc, char *argv[]);
 int sdust_main(int argc, char *argv[]);
 int assbed_main(int argc, char *argv[]);
 int seq_main(int argc, char *argv[]);
+int fixasm_main(int argc, char *argv[]);
 
 #endif

@@ -57,15 +57,6 @@ static void batches_of(cli_fastx_t *fx, cornetto_accel_t *h_open, batch_fn fn, v
 
 /* ---------------------------------------------------------------- records on the device */
 /* a record as the scans need it: its name (not NUL-terminated when it points into a file piece) and length */
-typedef struct {
-    const char *name;
-    int32_t name_len;
-    int64_t len;
-} cli_recname_t;
-
-/* scan the resident sequences `a` (record i of it = r[i]) and print the sub-command's lines */
-typedef void (*scan_fn)(cornetto_accel_t *h, const cli_recname_t *r, int64_t n, const cornetto_asm_t *a, void *arg);
-
 static void print_hit(const char *name, size_t name_len, int64_t len, const cornetto_hit_t *h);
 static void print_ivl(const char *name, size_t name_len, const cornetto_ivl_t *v);
 
@@ -560,7 +551,7 @@ static int stream_whole_fasta(const char *path, int fd, int64_t size, scan_fn sc
     return 1;
 }
 
-static void stream_records(const char *path, int must_open, scan_fn scan, void *arg)
+void stream_records(const char *path, int must_open, scan_fn scan, void *arg)
 {
     const int trace = getenv("CORNETTO_CLI_TRACE") != NULL;
     const double t_begin = cli_realtime();
@@ -597,7 +588,7 @@ static void stream_records(const char *path, int must_open, scan_fn scan, void *
         }
         {
             struct stat st;
-            if (fasta && raw_fd >= 0 && fstat(raw_fd, &st) == 0 && (int64_t)st.st_size >= (256LL << 20))
+            if (fasta && raw_fd >= 0 && (scan == sdust_scan || scan == telofind_scan) && fstat(raw_fd, &st) == 0 && (int64_t)st.st_size >= (256LL << 20))
                 cli_accel_warm_hint(scan == sdust_scan ? CORNETTO_WARM_SDUST : CORNETTO_WARM_TELO);      /* (an assembly: its one scan should not be the runtime's first) */
         }
         cli_accel_open_begin();

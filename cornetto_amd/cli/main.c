@@ -1,8 +1,8 @@
 /* main.c — `cornetto <command>` dispatcher; mirrors src/main.c:95-152 of the reference for the
- * panel-creation sub-commands (same names, same exit codes, same 3-line stderr footer).  Sub-commands of
- * the reference that are outside this path (fixasm, minidot, asmstats, nx, report, telocontigs)
- * are named in the usage text as not built here and exit with status 1; telobreaks
- * is built and dispatched below. */
+ * panel-creation sub-commands (same names, same exit codes, same 3-line stderr footer) and for fixasm,
+ * the first step of the assembly toolkit (fixasm_main.c).  Sub-commands of the reference that are
+ * outside this build (minidot, asmstats, nx, report, telocontigs) are not in the usage text and exit
+ * with status 1 as unrecognised; telobreaks is built and dispatched below. */
 #include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
@@ -23,6 +23,8 @@ static int print_usage(FILE *fp)
     fprintf(fp, "       telofind        find telomere sequences in a fasta file\n");
     fprintf(fp, "       telobreaks      find telomere sequences inside low-complexity runs\n");
     fprintf(fp, "       sdust           symmetric DUST (https://github.com/lh3/sdust)\n");
+    fprintf(fp, "   assembly toolkit:\n");
+    fprintf(fp, "       fixasm          rename and reorient assembly contigs after their alignments to a reference\n");
     fprintf(fp, "   misc:\n");
     fprintf(fp, "       fa2bed          create a bed file with assembly contig lengths\n");
     fprintf(fp, "       seq             extract reads equal or longer than a threshold from a fastq\n");
@@ -56,6 +58,8 @@ int main(int argc, char *argv[])
         ret = sdust_main(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "fa2bed") == 0) {
         ret = assbed_main(argc - 1, argv + 1);
+    } else if (strcmp(argv[1], "fixasm") == 0) {
+        ret = fixasm_main(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "seq") == 0) {
         ret = seq_main(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "-V") == 0) {

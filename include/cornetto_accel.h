@@ -458,6 +458,33 @@ int cornetto_fasta_split_text(cornetto_accel_t *h, cornetto_text_t *t, int64_t n
                               int64_t *consumed, int32_t *plain, cornetto_asm_t **seqs);
 
 /* ---------------------------------------------------------------------------------------------------
+ * fixasm output text: the records of a resident assembly, renamed and reoriented
+ * ------------------------------------------------------------------------------------------------- */
+
+/* One record of the text: heads[head .. head + head_len) (the ">name\n" line, built by the caller), then the bases of contig `ctg`
+ * of the assembly — reversed and complemented when rc != 0, as reverse_complement() does it (src/fixasm.c:208-224: only the
+ * upper-case A<->T and C<->G are complemented; lower case, N and IUPAC codes are reversed only) — then '\n'.  Concatenated
+ * over the records, this is what fix_the_assembly() prints with ">%s_%d\n%s\n" (src/fixasm.c:384). */
+typedef struct cornetto_emit_rec {
+    int32_t ctg;
+    int32_t rc;
+    int64_t head;
+    int64_t head_len;
+} cornetto_emit_rec_t;
+
+/* cornetto_emit_open(): a plan over `a` (which must outlive it) and recs[0..n); heads (n_heads bytes) is copied, *total_bytes is
+ * the length of the whole text.  cornetto_emit_get(): bytes [at, at + n) of the text into `dst_pinned` (pinned memory:
+ * cornetto_pinned_alloc), asynchronously, on queue `slot` (0..3: the kernel of a window on one slot runs beside the copy of
+ * another's); a window may cut records anywhere.  cornetto_emit_wait(): returns when the last get of that slot has landed.
+ * Device memory: the plan (40 B per record + the head bytes) and one slab per slot of the largest window asked of it. */
+typedef struct cornetto_emit cornetto_emit_t;
+int cornetto_emit_open(cornetto_accel_t *h, const cornetto_asm_t *a, const cornetto_emit_rec_t *recs, int64_t n, const char *heads,
+                       int64_t n_heads, cornetto_emit_t **out, int64_t *total_bytes);
+int cornetto_emit_get(cornetto_accel_t *h, cornetto_emit_t *e, char *dst_pinned, int64_t at, int64_t n, int slot);
+int cornetto_emit_wait(cornetto_accel_t *h, cornetto_emit_t *e, int slot);
+void cornetto_emit_free(cornetto_accel_t *h, cornetto_emit_t *e);
+
+/* ---------------------------------------------------------------------------------------------------
  * panel interval stage — scripts/create-cornetto.sh:41-66 without bedtools / sort / awk (parity with bedtools itself
  * is unpinned: see cornetto_amd/csrc/panel.hip)
  * ------------------------------------------------------------------------------------------------- */
