@@ -149,6 +149,40 @@ typedef void (*scan_fn)(cornetto_accel_t *h, const cli_recname_t *r, int64_t n, 
 /* every record of the FASTA/FASTQ(+gz) file `path`, framed on the device where the text allows it (else by the sequential reader), handed
  * to `scan` in input order, a batch at a time; must_open: a file that cannot be opened is the reference's F_CHK error (exit 1) */
 void stream_records(const char *path, int must_open, scan_fn scan, void *arg);
+/* the same for callers that need only every record's name and length: `names` is handed a == NULL.  No bases reach the device (the framing
+ * runs with seqs == NULL, the sequential reader uploads nothing); one device handle serves every call of the process, and what a call
+ * allocates (device text, pinned slabs and pieces, threads) is released before it returns, so it may be called once per file.
+ * CORNETTO_ACCEL=no: the sequential reader alone, no device. */
+void stream_names(const char *path, int must_open, scan_fn names, void *arg);
+
+/* ---- text tables shared by fixasm, telocontigs and asmstats (cli/tables.c) ---- */
+FILE *cli_fopen_chk(const char *path, const char *mode);   /* fopen(), or the reference's F_CHK message and exit(EXIT_FAILURE) */
+/* a string -> dense index map (indices in order of insertion) */
+typedef struct {
+    int32_t *slot;   /* index + 1, 0 = empty */
+    size_t cap;      /* power of two */
+    size_t n;
+    char **keys;     /* by index, NUL-terminated */
+    int32_t *klen;
+    size_t kcap;
+} cli_map_t;
+int32_t cli_map_get(const cli_map_t *m, const char *s, size_t n);              /* -1 if absent */
+int32_t cli_map_put(cli_map_t *m, const char *s, size_t n, int *added);       /* the index of s, a new one (*added = 1) if absent */
+void cli_map_free(cli_map_t *m);
+/* one PAF line as src/pafrec.c:43-98 reads it: strtok on "\t\r\n", atoi() fields; fewer than 12 fields is the reference's
+ * "Malformed PAF record" exit(EXIT_FAILURE).  rid / tid point into the line, which is modified. */
+typedef struct {
+    char *rid, *tid;
+    int32_t qlen, qs, qe, tlen, ts, te, match, block;
+    int8_t strand;
+    uint8_t mapq;
+    char tp;
+} cli_paf_t;
+void cli_paf_parse(char *line, cli_paf_t *r);
+/* a telomere BED (load_telobed of src/telocontigs.c:59-108 and src/asmstats.c:230-290): sscanf("%s\t%ld\t%ld") per line; fewer than three
+ * fields, a negative coordinate or start >= end is exit(EXIT_FAILURE).  on_row(contig name, arg) once per row, in file order. */
+void cli_telobed_load(const char *path, void (*on_row)(const char *ctg, void *arg), void *arg);
+int cli_strnum_cmp(const char *a, const char *b);   /* natural order of src/misc.c:139-171: digit runs compare as numbers, leading zeros skipped */
 
 /* ---- the host path (cli/host_backend.c): plain sequential C99 for every scan, chosen with --accel=no (noboringbits / boringbits, the
  * reference's own switch: src/boringbits_main.c:627-632) or CORNETTO_ACCEL=no (every sub-command) — never by itself ---- */
@@ -190,5 +224,9 @@ int sdust_main(int argc, char *argv[]);
 int assbed_main(int argc, char *argv[]);
 int seq_main(int argc, char *argv[]);
 int fixasm_main(int argc, char *argv[]);
+int nx_main(int argc, char *argv[]);
+int report_main(int argc, char *argv[]);
+int telocontigs_main(int argc, char *argv[]);
+int asmstats_main(int argc, char *argv[]);
 
 #endif

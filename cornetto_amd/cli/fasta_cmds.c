@@ -285,6 +285,22 @@ static void scan_batch(cornetto_accel_t *h, cli_batch_t *b, void *arg)
     cornetto_asm_free(h, a);
 }
 
+/* the sequential reader for stream_names(): every record's name and length handed over one at a time, nothing uploaded (fx closed here) */
+static void names_of(cli_fastx_t *fx, cornetto_accel_t *h, scan_fn scan, void *arg)
+{
+    cli_str_t name = {0, 0, 0}, comment = {0, 0, 0}, seq = {0, 0, 0}, qual = {0, 0, 0};
+    int64_t l;
+    while ((l = cli_fastx_read(fx, &name, &comment, &seq, &qual)) >= 0) {
+        const cli_recname_t r = {name.s, (int32_t)name.l, l};
+        scan(h, &r, 1, NULL, arg);
+    }
+    free(name.s);
+    free(comment.s);
+    free(seq.s);
+    free(qual.s);
+    cli_fastx_close(fx);
+}
+
 /* FASTA / FASTQ file -> scans, with the records framed on the device wherever the text is plain (cornetto_fasta_split,
  * cornetto_fastq_split): the file goes to the device in pieces as it is, names are printed straight from the piece.
  * Anything else — wrapped FASTQ, stray lines, a FASTQ record inside a FASTA file, the reference's error cases — is read
@@ -443,8 +459,8 @@ static void *whole_pinner(void *p)
     return NULL;
 }
 
-static int stream_whole_fasta(const char *path, int fd, int64_t size, scan_fn scan, void *arg, cornetto_accel_t **h_io, int64_t *resume_off, int trace,
-                              double t_begin)
+static int stream_whole_fasta(const char *path, int fd, int64_t size, scan_fn scan, void *arg, int names_only, cornetto_accel_t **h_io, int64_t *resume_off,
+                              int trace, double t_begin)
 {
     const int64_t LIMIT = 0xFFFFFF00LL - 4096;
     cornetto_accel_t *h = *h_io;
@@ -466,8 +482,8 @@ static int stream_whole_fasta(const char *path, int fd, int64_t size, scan_fn sc
     if (w.n_slots > WHOLE_SLOTS) w.n_slots = WHOLE_SLOTS;
     if (w.n_slots < 1) w.n_slots = 1;
     pthread_t pin_th;
-    if (pthread_create(&pin_th, NULL, whole_pinner, &w) != 0) whole_pinner(&w);
-    else pthread_detach(pin_th);
+    const int pin_started = pthread_create(&pin_th, NULL, whole_pinner, &w) == 0;
+    if (!pin_started) whole_pinner(&w);
     int n_thr = getenv("CORNETTO_READ_THREADS") ? READ_THREADS : 16;
     if (n_thr > w.n_slots) n_thr = w.n_slots;
     int64_t off = 0;
@@ -513,7 +529,7 @@ static int stream_whole_fasta(const char *path, int fd, int64_t size, scan_fn sc
         cornetto_asm_t *a = NULL;
         int64_t nrec = 0, used = 0;
         int32_t plain = 1;
-        cli_accel_check(h, cornetto_fasta_split_text(h, t, n, final, &recs, &nrec, &used, &plain, &a), "framing the FASTA records");
+        cli_accel_check(h, cornetto_fasta_split_text(h, t, n, final, &recs, &nrec, &used, &plain, names_only ? NULL : &a), "framing the FASTA records");
         TRACE("records framed");
         if (nrec) {
             /* the names: from the file, by offset (the slabs are gone) */
@@ -546,12 +562,23 @@ static int stream_whole_fasta(const char *path, int fd, int64_t size, scan_fn sc
         else if (used == 0 && !final) plain_all = 0; /* one record longer than a text (2^32 bytes): the sequential reader reports it as the reference's reader would */
         else if (final) off = size;
     }
-    /* (the slabs, the text and the handle are left to the end of the process: main.c leaves with _exit) */
+    if (pin_started) pthread_join(pin_th, NULL);   /* (it uses `w`, which lives on this stack) */
+    if (names_only) {                              /* called once per file: nothing may pile up */
+        for (int s = 0; s < w.n_slots; ++s) cornetto_pinned_free(w.ring[s]);
+        cornetto_text_free(h, t);
+    }
+    /* (otherwise the slabs, the text and the handle are left to the end of the process: main.c leaves with _exit) */
+    pthread_mutex_destroy(&w.mu);
+    pthread_cond_destroy(&w.cv);
     *resume_off = off;
     return 1;
 }
 
-void stream_records(const char *path, int must_open, scan_fn scan, void *arg)
+/* names_only (stream_names): the framing calls get seqs == NULL (the scan is handed a == NULL), the sequential reader uploads nothing,
+ * the device handle is the process's one, and the text, the slabs and the pinned pieces are freed before returning */
+static cornetto_accel_t *g_names_h;
+
+static void stream_core(const char *path, int must_open, scan_fn scan, void *arg, int names_only)
 {
     const int trace = getenv("CORNETTO_CLI_TRACE") != NULL;
     const double t_begin = cli_realtime();
@@ -564,8 +591,8 @@ void stream_records(const char *path, int must_open, scan_fn scan, void *arg)
         return; /* sdust: the reference has no NULL check (src/sdust/sdust.c:194) and crashes; we just stop */
     }
     gzbuffer(fp, 1 << 18);
-    cornetto_accel_t *h = NULL;
-    char first = 0, *buf = &first;
+    cornetto_accel_t *h = names_only ? g_names_h : NULL;
+    char first = 0, *buf = &first, *other = NULL;
     int64_t have = 0, start = 0; /* unread bytes: buf[start .. have) */
     int eof = 0;
     const int r0 = gzread(fp, &first, 1);
@@ -591,7 +618,7 @@ void stream_records(const char *path, int must_open, scan_fn scan, void *arg)
             if (fasta && raw_fd >= 0 && (scan == sdust_scan || scan == telofind_scan) && fstat(raw_fd, &st) == 0 && (int64_t)st.st_size >= (256LL << 20))
                 cli_accel_warm_hint(scan == sdust_scan ? CORNETTO_WARM_SDUST : CORNETTO_WARM_TELO);      /* (an assembly: its one scan should not be the runtime's first) */
         }
-        cli_accel_open_begin();
+        if (!h) cli_accel_open_begin();
         /* read-ahead (uncompressed FASTA file; CORNETTO_CLI_AHEAD=0 switches it off) */
         const char *ahead_env = getenv("CORNETTO_CLI_AHEAD");
         const int use_ahead = fasta && raw_fd >= 0 && !(ahead_env && !atoi(ahead_env));
@@ -604,13 +631,15 @@ void stream_records(const char *path, int must_open, scan_fn scan, void *arg)
             struct stat st;
             if (use_ahead && !(we && !atoi(we)) && !getenv("CORNETTO_FASTQ_PIECE") && fstat(raw_fd, &st) == 0 && st.st_size > 0) {
                 int64_t resume = 0;
-                (void)stream_whole_fasta(path, raw_fd, (int64_t)st.st_size, scan, arg, &h, &resume, trace, t_begin);
+                (void)stream_whole_fasta(path, raw_fd, (int64_t)st.st_size, scan, arg, names_only, &h, &resume, trace, t_begin);
                 close(raw_fd);
+                if (names_only) g_names_h = h;
                 if (resume < (int64_t)st.st_size) {     /* not plain from there on: the sequential reader takes the rest */
                     gzseek(fp, (z_off_t)resume, SEEK_SET);
                     batch_scan_t bs = {scan, arg};
                     cli_fastx_t *fx = cli_fastx_open_prefixed(fp, NULL, 0);
-                    batches_of(fx, h, scan_batch, &bs);
+                    if (names_only) names_of(fx, h, scan, arg);
+                    else batches_of(fx, h, scan_batch, &bs);
                 } else {
                     gzclose(fp);
                 }
@@ -634,7 +663,7 @@ void stream_records(const char *path, int must_open, scan_fn scan, void *arg)
         TRACE("pinned piece allocated");
         fa_ahead_t ah;
         memset(&ah, 0, sizeof(ah));
-        char *other = NULL;          /* the second buffer, once the thread has made it */
+        /* other: the second buffer, once the thread has made it */
         int64_t buf_off = 0;         /* file offset of buf[0] (raw files) */
         int ahead_ready = 0;         /* buf already holds the next piece (have, eof set) */
         for (;;) {
@@ -690,7 +719,7 @@ void stream_records(const char *path, int must_open, scan_fn scan, void *arg)
             int32_t plain = 1;
             if (fasta) {
                 cornetto_farec_t *recs = NULL;
-                cli_accel_check(h, cornetto_fasta_split(h, buf, have, eof, &recs, &n, &used, &plain, &a), "framing the FASTA records");
+                cli_accel_check(h, cornetto_fasta_split(h, buf, have, eof, &recs, &n, &used, &plain, names_only ? NULL : &a), "framing the FASTA records");
                 r = (cli_recname_t *)cli_xmalloc(((size_t)n + 1) * sizeof(*r));
                 for (int64_t i = 0; i < n; ++i) {
                     r[i].name = buf + recs[i].head + 1;
@@ -700,7 +729,7 @@ void stream_records(const char *path, int must_open, scan_fn scan, void *arg)
                 cornetto_free(recs);
             } else {
                 cornetto_fqrec_t *recs = NULL;
-                cli_accel_check(h, cornetto_fastq_split(h, buf, have, eof, 0, &recs, &n, &used, &plain, &a), "framing the FASTQ records");
+                cli_accel_check(h, cornetto_fastq_split(h, buf, have, eof, 0, &recs, &n, &used, &plain, names_only ? NULL : &a), "framing the FASTQ records");
                 r = (cli_recname_t *)cli_xmalloc(((size_t)n + 1) * sizeof(*r));
                 for (int64_t i = 0; i < n; ++i) {
                     r[i].name = buf + recs[i].head + 1;
@@ -768,14 +797,38 @@ void stream_records(const char *path, int must_open, scan_fn scan, void *arg)
     if (start < have || !eof) { /* the rest (or all of it) through the sequential reader */
         batch_scan_t bs = {scan, arg};
         cli_fastx_t *fx = cli_fastx_open_prefixed(fp, buf + start, (size_t)(have - start));
-        batches_of(fx, h, scan_batch, &bs);
+        if (names_only) names_of(fx, h, scan, arg);
+        else batches_of(fx, h, scan_batch, &bs);
     } else {
         gzclose(fp);
     }
-    /* the pinned piece and the device handle are left to the end of the process (main.c leaves with _exit right after
+    if (names_only) {
+        g_names_h = h;
+        if (buf != &first) cornetto_pinned_free(buf);
+        if (other) cornetto_pinned_free(other);
+    }
+    /* otherwise the pinned piece and the device handle are left to the end of the process (main.c leaves with _exit right after
      * the sub-command): unpinning a 1 GB piece and closing the handle take about 0.1 s */
-    (void)h;
     TRACE("done");
+}
+
+void stream_records(const char *path, int must_open, scan_fn scan, void *arg) { stream_core(path, must_open, scan, arg, 0); }
+
+void stream_names(const char *path, int must_open, scan_fn names, void *arg)
+{
+    if (cli_host_mode()) {                          /* CORNETTO_ACCEL=no: the sequential reader, no device */
+        cli_fastx_t *fx = cli_fastx_open(path);
+        if (!fx) {
+            if (must_open) {
+                CLI_ERROR("Could not to open file %s: %s", path, strerror(errno)); /* F_CHK, src/error.h:114-119: its words */
+                exit(EXIT_FAILURE);
+            }
+            return;
+        }
+        names_of(fx, NULL, names, arg);
+        return;
+    }
+    stream_core(path, must_open, names, arg, 1);
 }
 
 /* the host path (--accel=no / CORNETTO_ACCEL=no): the sequential reader, one record at a time, printed as it is scanned */

@@ -3,7 +3,7 @@
  * src/fixasm.c:226-284 (load_paf), :287-338 (write_corrected_paf), :341-405 (fix_the_assembly), :419-480 (options), with the PAF
  * fields of src/pafrec.c:43-98.
  *
- * The PAF side (O(lines)) runs here on the host.  The FASTA side goes through stream_records() (fasta_cmds.c): the records are framed on
+ * The PAF side (O(lines)) runs here on the host, with the parser of cli/tables.c.  The FASTA side goes through stream_records() (fasta_cmds.c): the records are framed on
  * the device, the header lines are built here, and the output text — headers, bases forward or reverse-complemented, newlines — is
  * written on the device window by window (cornetto_emit_*) and copied into pinned slabs that go to stdout with write().
  * CORNETTO_EMIT_SLAB = bytes per window (default 32 MiB; never changes a byte of the output).  CORNETTO_ACCEL=no: the same on the
@@ -25,127 +25,6 @@
 
 #include "cli.h"
 
-/* ---------------------------------------------------------------- a string -> index map (the reference's khash maps: :90-93) */
-typedef struct {
-    int32_t *slot;   /* index + 1, 0 = empty */
-    size_t cap;      /* power of two */
-    size_t n;
-    char **keys;     /* by index, NUL-terminated */
-    int32_t *klen;
-    size_t kcap;
-} fx_map_t;
-
-static uint64_t fx_hash(const char *s, size_t n)
-{
-    uint64_t h = 1469598103934665603ULL;
-    for (size_t i = 0; i < n; ++i) h = (h ^ (uint8_t)s[i]) * 1099511628211ULL;
-    return h;
-}
-
-static int32_t fx_get(const fx_map_t *m, const char *s, size_t n)
-{
-    if (!m->cap) return -1;
-    for (size_t i = fx_hash(s, n) & (m->cap - 1);; i = (i + 1) & (m->cap - 1)) {
-        const int32_t v = m->slot[i];
-        if (!v) return -1;
-        if ((size_t)m->klen[v - 1] == n && !memcmp(m->keys[v - 1], s, n)) return v - 1;
-    }
-}
-
-/* the index of key s, added as the next index if it is new (*added = 1) */
-static int32_t fx_put(fx_map_t *m, const char *s, size_t n, int *added)
-{
-    *added = 0;
-    const int32_t have = fx_get(m, s, n);
-    if (have >= 0) return have;
-    if ((m->n + 1) * 2 > m->cap) {
-        const size_t cap = m->cap ? m->cap * 2 : 1024;
-        int32_t *slot = (int32_t *)calloc(cap, sizeof(int32_t));
-        if (!slot) { CLI_ERROR("Failed to allocate memory: %s", strerror(errno)); exit(EXIT_FAILURE); }
-        for (size_t k = 0; k < m->n; ++k) {
-            size_t i = fx_hash(m->keys[k], (size_t)m->klen[k]) & (cap - 1);
-            while (slot[i]) i = (i + 1) & (cap - 1);
-            slot[i] = (int32_t)k + 1;
-        }
-        free(m->slot);
-        m->slot = slot;
-        m->cap = cap;
-    }
-    if (m->n == m->kcap) {
-        m->kcap = m->kcap ? m->kcap * 2 : 256;
-        m->keys = (char **)cli_xrealloc(m->keys, m->kcap * sizeof(char *));
-        m->klen = (int32_t *)cli_xrealloc(m->klen, m->kcap * sizeof(int32_t));
-    }
-    char *k = (char *)cli_xmalloc(n + 1);
-    memcpy(k, s, n);
-    k[n] = 0;
-    m->keys[m->n] = k;
-    m->klen[m->n] = (int32_t)n;
-    size_t i = fx_hash(s, n) & (m->cap - 1);
-    while (m->slot[i]) i = (i + 1) & (m->cap - 1);
-    m->slot[i] = (int32_t)m->n + 1;
-    *added = 1;
-    return (int32_t)m->n++;
-}
-
-/* ---------------------------------------------------------------- the PAF (src/pafrec.c:43-98) */
-typedef struct {
-    char *rid, *tid;   /* into the line */
-    int32_t qlen, qs, qe, tlen, ts, te, match, block;
-    int8_t strand;
-    uint8_t mapq;
-    char tp;
-} fx_paf_t;
-
-static int32_t fx_atoi(const char *s) { return (int32_t)strtol(s, NULL, 10); }   /* glibc's atoi() */
-
-static char *fx_field(char **save)
-{
-    char *p = strtok_r(NULL, "\t\r\n", save);
-    if (!p) {
-        CLI_ERROR("%s", "Malformed PAF record. Exiting.");
-        exit(EXIT_FAILURE);
-    }
-    return p;
-}
-
-static void fx_parse(char *line, fx_paf_t *r)
-{
-    char *save = NULL;
-    char *p = strtok_r(line, "\t\r\n", &save);
-    if (!p) {
-        CLI_ERROR("%s", "Malformed PAF record. Exiting.");
-        exit(EXIT_FAILURE);
-    }
-    r->rid = p;
-    r->qlen = fx_atoi(fx_field(&save));
-    r->qs = fx_atoi(fx_field(&save));
-    r->qe = fx_atoi(fx_field(&save));
-    r->strand = strcmp(fx_field(&save), "+") == 0 ? 0 : 1;
-    r->tid = fx_field(&save);
-    r->tlen = fx_atoi(fx_field(&save));
-    r->ts = fx_atoi(fx_field(&save));
-    r->te = fx_atoi(fx_field(&save));
-    r->match = fx_atoi(fx_field(&save));
-    r->block = fx_atoi(fx_field(&save));
-    r->mapq = (uint8_t)fx_atoi(fx_field(&save));
-    r->tp = 'P';
-    while ((p = strtok_r(NULL, "\t\r\n", &save))) {
-        if (!strcmp(p, "tp:A:P")) r->tp = 'P';
-        else if (!strcmp(p, "tp:A:S")) r->tp = 'S';
-    }
-}
-
-static FILE *fx_open(const char *path, const char *mode)
-{
-    FILE *f = fopen(path, mode);
-    if (!f) {
-        CLI_ERROR("Could not to open file %s: %s", path, strerror(errno)); /* F_CHK, src/error.h:114-119: its words */
-        exit(EXIT_FAILURE);
-    }
-    return f;
-}
-
 /* ---------------------------------------------------------------- the state of a run */
 typedef struct {
     int64_t sump, sumn;
@@ -157,7 +36,7 @@ typedef struct {
 } fx_ctg_t;
 
 typedef struct {
-    fx_map_t ctgs, tgts;
+    cli_map_t ctgs, tgts;
     fx_ctg_t *ctg;
     size_t ctg_cap;
     char **clean;          /* target names, trimmed under --trim-pat-mat (cleanup_str, :57-71) */
@@ -175,14 +54,14 @@ typedef struct {
 
 static void fx_load_paf(fx_run_t *R, const char *paf)
 {
-    FILE *fp = fx_open(paf, "r");
+    FILE *fp = cli_fopen_chk(paf, "r");
     char *line = NULL;
     size_t cap = 0;
-    fx_paf_t r;
+    cli_paf_t r;
     while (getline(&line, &cap, fp) != -1) {
-        fx_parse(line, &r);
+        cli_paf_parse(line, &r);
         int added;
-        const int32_t ci = fx_put(&R->ctgs, r.rid, strlen(r.rid), &added);
+        const int32_t ci = cli_map_put(&R->ctgs, r.rid, strlen(r.rid), &added);
         if (added) {
             if ((size_t)ci >= R->ctg_cap) {
                 R->ctg_cap = R->ctg_cap ? R->ctg_cap * 2 : 256;
@@ -190,7 +69,7 @@ static void fx_load_paf(fx_run_t *R, const char *paf)
             }
             memset(&R->ctg[ci], 0, sizeof(fx_ctg_t));
         }
-        const int32_t ti = fx_put(&R->tgts, r.tid, strlen(r.tid), &added);
+        const int32_t ti = cli_map_put(&R->tgts, r.tid, strlen(r.tid), &added);
         fx_ctg_t *c = &R->ctg[ci];
         const int32_t length = (int32_t)((uint32_t)r.te - (uint32_t)r.ts);   /* int32_t difference (:268), wrapping */
         if (r.strand == 0) c->sump += length;
@@ -246,7 +125,7 @@ static void fx_trim_names(fx_run_t *R, int trim)
 /* one FASTA record: -1 if the PAF does not name it (then listed in -m), else its contig; *head gets ">new_name\n" */
 static int32_t fx_name(fx_run_t *R, const char *name, size_t name_len, char **head, size_t *head_len)
 {
-    const int32_t ci = fx_get(&R->ctgs, name, name_len);
+    const int32_t ci = cli_map_get(&R->ctgs, name, name_len);
     if (ci < 0) {
         if (R->fp_missing) {
             fwrite(name, 1, name_len, R->fp_missing);
@@ -398,14 +277,14 @@ static void fx_host_fasta(fx_run_t *R, const char *path)
 /* ---------------------------------------------------------------- -w (write_corrected_paf, :287-338) */
 static void fx_write_paf(const fx_run_t *R, const char *out_paf, const char *paf)
 {
-    FILE *fp = fx_open(paf, "r");
-    FILE *fw = fx_open(out_paf, "w");
+    FILE *fp = cli_fopen_chk(paf, "r");
+    FILE *fw = cli_fopen_chk(out_paf, "w");
     char *line = NULL;
     size_t cap = 0;
-    fx_paf_t r;
+    cli_paf_t r;
     while (getline(&line, &cap, fp) != -1) {
-        fx_parse(line, &r);
-        const int32_t ci = fx_get(&R->ctgs, r.rid, strlen(r.rid));
+        cli_paf_parse(line, &r);
+        const int32_t ci = cli_map_get(&R->ctgs, r.rid, strlen(r.rid));
         if (ci < 0) {   /* (the file changed since it was loaded) */
             fprintf(stderr, "Error: contig %s not found in hash table\n", r.rid);
             exit(EXIT_FAILURE);
@@ -472,8 +351,8 @@ int fixasm_main(int argc, char *argv[])
         }
         gzclose(g);
     }
-    if (report) R.fp_report = fx_open(report, "w");
-    if (missing) R.fp_missing = fx_open(missing, "w");
+    if (report) R.fp_report = cli_fopen_chk(report, "w");
+    if (missing) R.fp_missing = cli_fopen_chk(missing, "w");
 
     if (cli_host_mode()) {
         fx_host_fasta(&R, fasta);

@@ -1,7 +1,7 @@
 /* main.c — `cornetto <command>` dispatcher; mirrors src/main.c:95-152 of the reference for the
- * panel-creation sub-commands (same names, same exit codes, same 3-line stderr footer) and for fixasm,
- * the first step of the assembly toolkit (fixasm_main.c).  Sub-commands of the reference that are
- * outside this build (minidot, asmstats, nx, report, telocontigs) are not in the usage text and exit
+ * panel-creation sub-commands (same names, same exit codes, same 3-line stderr footer), for fixasm
+ * (fixasm_main.c) and for the evaluation sub-commands asmstats, nx, report and telocontigs (eval_main.c).
+ * minidot, the one sub-command of the reference outside this build, is not in the usage text and exits
  * with status 1 as unrecognised; telobreaks is built and dispatched below. */
 #include <stdlib.h>
 #include <string.h>
@@ -12,7 +12,7 @@
 static int print_usage(FILE *fp)
 {
     fprintf(fp, "Usage: cornetto <command> [options]\n\n");
-    fprintf(fp, "commands (MI355X build: panel-creation path only):\n");
+    fprintf(fp, "commands (MI355X build; minidot is not built):\n");
     fprintf(fp, "   create panel:\n");
     fprintf(fp, "       noboringbits    print no boring bits in an assembly\n");
     fprintf(fp, "       boringbits      print boring bits in an assembly (deprecated)\n");
@@ -25,6 +25,11 @@ static int print_usage(FILE *fp)
     fprintf(fp, "       sdust           symmetric DUST (https://github.com/lh3/sdust)\n");
     fprintf(fp, "   assembly toolkit:\n");
     fprintf(fp, "       fixasm          rename and reorient assembly contigs after their alignments to a reference\n");
+    fprintf(fp, "   eval:\n");
+    fprintf(fp, "       asmstats        calculate assembly statistics\n");
+    fprintf(fp, "       nx              nx or ngx plot tables\n");
+    fprintf(fp, "       report          generate a report table for one or more assemblies\n");
+    fprintf(fp, "       telocontigs     prints contigs from largest to smallest with number of telomeres\n");
     fprintf(fp, "   misc:\n");
     fprintf(fp, "       fa2bed          create a bed file with assembly contig lengths\n");
     fprintf(fp, "       seq             extract reads equal or longer than a threshold from a fastq\n");
@@ -60,6 +65,14 @@ int main(int argc, char *argv[])
         ret = assbed_main(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "fixasm") == 0) {
         ret = fixasm_main(argc - 1, argv + 1);
+    } else if (strcmp(argv[1], "nx") == 0) {
+        ret = nx_main(argc - 1, argv + 1);
+    } else if (strcmp(argv[1], "report") == 0) {
+        ret = report_main(argc - 1, argv + 1);
+    } else if (strcmp(argv[1], "telocontigs") == 0) {
+        ret = telocontigs_main(argc - 1, argv + 1);
+    } else if (strcmp(argv[1], "asmstats") == 0) {
+        ret = asmstats_main(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "seq") == 0) {
         ret = seq_main(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "-V") == 0) {

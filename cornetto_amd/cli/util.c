@@ -67,11 +67,18 @@ void cli_out_flush(void)
     cli_out_n = 0;
 }
 
+/* CORNETTO_CLI_TRACE: one stderr line per device handle the CLI opens (tests count them) */
+static void trace_open(int dev, int rc)
+{
+    if (getenv("CORNETTO_CLI_TRACE")) fprintf(stderr, "[cli trace] device %d opened (rc %d)\n", dev, rc);
+}
+
 cornetto_accel_t *cli_accel_open(void)
 {
     const char *d = getenv("CORNETTO_DEVICE");
     cornetto_accel_t *h = NULL;
     int rc = cornetto_accel_open(&h, d ? atoi(d) : 0, NULL);
+    trace_open(d ? atoi(d) : 0, rc);
     if (rc != CORNETTO_OK) {
         CLI_ERROR("cannot open HIP device %d: %s. The scans run on an AMD GPU; the sequential host path is a choice (--accel=no / CORNETTO_ACCEL=no), never a fallback.",
                   d ? atoi(d) : 0, cornetto_accel_strerror(rc));
@@ -96,6 +103,7 @@ static void *open_thread(void *arg)
     (void)arg;
     cornetto_accel_t *h = NULL;
     const int rc = cornetto_accel_open(&h, g_open.dev, NULL);
+    trace_open(g_open.dev, rc);
     pthread_mutex_lock(&g_open.mu);
     g_open.rc = rc;
     g_open.h = h;

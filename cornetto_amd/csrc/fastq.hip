@@ -439,8 +439,8 @@ static int fasta_split_core(cornetto_accel_t *h, const char *text_in, uint8_t *d
     const size_t nl1 = (size_t)n_lines + 1;
     uint32_t *d_nl = (uint32_t *)cn_ws(h, WS_FQ_NL, (nl1 + 8) * 4);
     uint32_t *d_lw = (uint32_t *)cn_ws(h, WS_FQ_ENDS, (5 * nl1 + 2 * ((nl1 + 4095) / 4096 + 2) + 16) * 4);
-    int64_t *d_dst = (int64_t *)cn_ws(h, WS_FQ_SRC, nl1 * 8);
-    if (!d_nl || !d_lw || !d_dst) return cn_fail(h, CORNETTO_E_NOMEM, "fasta_split: workspace allocation failed");
+    int64_t *d_dst = seqs ? (int64_t *)cn_ws(h, WS_FQ_SRC, nl1 * 8) : nullptr;   // (fa_linedst's, only when the bases are wanted)
+    if (!d_nl || !d_lw || (seqs && !d_dst)) return cn_fail(h, CORNETTO_E_NOMEM, "fasta_split: workspace allocation failed");
     uint32_t *d_hdr = d_lw, *d_pay = d_hdr + nl1, *d_H = d_pay + nl1, *d_P = d_H + nl1, *d_hl = d_P + nl1, *d_pp = d_hl + nl1;
     CN_HIP(h, hipMemsetAsync(d_bad, 0xFF, 4, h->stream));
     if (n_nl) CN_LAUNCH(h, "fq_nl_scatter", fq_nl_scatter<<<dim3((unsigned)nt), dim3(FQ_THREADS), 0, h->stream>>>(d_text, n, d_off, d_nl));
