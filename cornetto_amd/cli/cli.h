@@ -109,15 +109,23 @@ typedef struct {
     size_t l, m;
 } cli_str_t;
 
+typedef struct {
+    cli_str_t name, comment, seq, qual;   /* NUL-terminated; seq.l = bases */
+} cli_rec_t;
+
 typedef struct cli_fastx cli_fastx_t;
 extern int cli_dash_is_stdin;                  /* set by sdust_main: "-" = stdin (the other FASTA sub-commands open a file of that name, as the reference does) */
-cli_fastx_t *cli_fastx_open(const char *path); /* NULL on failure */
+/* gzopen() for reading (a gzFile).  A file that cannot be opened: the reference's F_CHK message and exit(EXIT_FAILURE) if must_open, else NULL */
+void *cli_gz_open(const char *path, int must_open);
+cli_fastx_t *cli_fastx_open(const char *path, int must_open); /* a reader over cli_gz_open() */
 /* a reader over `n` bytes at `prefix` (borrowed: must outlive the reads of them) followed by the rest of the open
  * gzFile `gz` (owned: closed by cli_fastx_close) */
 cli_fastx_t *cli_fastx_open_prefixed(void *gz, const void *prefix, size_t n);
-void cli_fastx_close(cli_fastx_t *f);
-/* >= 0: sequence length; -1 end of file; -2 truncated quality string */
-int64_t cli_fastx_read(cli_fastx_t *f, cli_str_t *name, cli_str_t *comment, cli_str_t *seq, cli_str_t *qual);
+void cli_fastx_close(cli_fastx_t *f);          /* frees the record as well */
+/* the next record (the reader's own: valid until the next call), NULL at the end of the file or at a truncated quality string */
+cli_rec_t *cli_fastx_next(cli_fastx_t *f);
+/* the same where the reference's kseq_t holds the length in an int: a record of more than 2^31-1 bases is an error and exit(EXIT_FAILURE) */
+cli_rec_t *cli_fastx_next_checked(cli_fastx_t *f);
 
 /* $CORNETTO_DEVICES: ordinals of the GPUs to spread the contigs over (at most CLI_MAX_DEV); returns how many, 0 if unset */
 #define CLI_MAX_DEV 64
@@ -135,8 +143,11 @@ void cli_batch_push(cli_batch_t *b, const char *name, const char *seq, int64_t l
 void cli_batch_take(cli_batch_t *b, const char *name, cli_str_t *seq); /* takes seq's buffer over when it is long */
 void cli_batch_clear(cli_batch_t *b);
 int64_t cli_batch_limit(void); /* $CORNETTO_BATCH_BASES, default 4e9 */
+/* every record of `f` (cli_fastx_next_checked; closed here) in batches of cli_batch_limit() bases, each handed to `fn` and cleared after it */
+typedef void (*cli_batch_fn)(cli_batch_t *b, void *arg);
+void cli_fastx_batches(cli_fastx_t *f, cli_batch_fn fn, void *arg);
 
-/* ---- the FASTA/FASTQ driver of the device path (cli/fasta_cmds.c) ---- */
+/* ---- the FASTA/FASTQ record streamer of the device path (cli/stream.c) ---- */
 typedef struct {
     const char *name;   /* not NUL-terminated */
     int32_t name_len;
@@ -147,8 +158,9 @@ typedef struct {
 typedef void (*scan_fn)(cornetto_accel_t *h, const cli_recname_t *r, int64_t n, const cornetto_asm_t *a, void *arg);
 
 /* every record of the FASTA/FASTQ(+gz) file `path`, framed on the device where the text allows it (else by the sequential reader), handed
- * to `scan` in input order, a batch at a time; must_open: a file that cannot be opened is the reference's F_CHK error (exit 1) */
-void stream_records(const char *path, int must_open, scan_fn scan, void *arg);
+ * to `scan` in input order, a batch at a time; must_open: a file that cannot be opened is the reference's F_CHK error (exit 1).
+ * warm: the entry points `scan` will call (CORNETTO_WARM_*, or 0), warmed up behind the device open when the input is a large assembly */
+void stream_records(const char *path, int must_open, scan_fn scan, void *arg, int warm);
 /* the same for callers that need only every record's name and length: `names` is handed a == NULL.  No bases reach the device (the framing
  * runs with seqs == NULL, the sequential reader uploads nothing); one device handle serves every call of the process, and what a call
  * allocates (device text, pinned slabs and pieces, threads) is released before it returns, so it may be called once per file.

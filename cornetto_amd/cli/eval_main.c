@@ -1,7 +1,7 @@
 /* eval_main.c — the evaluation sub-commands of the assembly toolkit: nx (src/nx.c), report (src/report.c), telocontigs
  * (src/telocontigs.c) and asmstats (src/asmstats.c).  Same options, stdout bytes and exit codes as the reference.
  *
- * Every FASTA/FASTQ(+gz) input is read through stream_names() (fasta_cmds.c): the records are framed on the device with no bases
+ * Every FASTA/FASTQ(+gz) input is read through stream_names() (stream.c): the records are framed on the device with no bases
  * materialised, one device handle serving all files of the process (report reads one assembly per iteration); CORNETTO_ACCEL=no reads
  * them with the sequential reader.  The tables (telomere BED, fixasm report, PAF) are parsed on the host (tables.c).
  *

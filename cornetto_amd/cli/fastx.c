@@ -6,8 +6,11 @@
  *     otherwise the line is appended; after each appended line one trailing '\r' is dropped once more than
  *     one byte is held (:138);
  *   - '+' starts a FASTQ quality block: the rest of the '+' line is skipped, quality lines are appended
- *     until at least as many bytes as the sequence are held; different lengths -> -2. */
+ *     until at least as many bytes as the sequence are held; different lengths -> -2.
+ * On top of it, what every sequential caller shares: the open with the reference's error (cli_gz_open), the record the reader
+ * hands out (cli_fastx_next, with the 2^31-1 limit of kseq's int length: cli_fastx_next_checked) and the batch loop (cli_fastx_batches). */
 #include <ctype.h>
+#include <errno.h>
 #include <stdlib.h>
 #include <string.h>
 #include <unistd.h>
@@ -24,22 +27,23 @@ struct cli_fastx {
     int last_char;
     const unsigned char *pre; /* bytes to be read before the stream's own (cli_fastx_open_prefixed) */
     size_t pre_left;
+    cli_rec_t rec;            /* the record cli_fastx_next() hands out */
 };
 
 /* "-" is the standard input for `sdust` alone (src/sdust/sdust.c:194); telofind, fa2bed and seq hand their argument to gzopen() as it is
- * (src/find_telomere.c:96, src/assbed.c:92, src/seq.c:106): a file of that name, or their "Could not to open file" and exit status 1 */
+ * (src/find_telomere.c:96, src/assbed.c:92, src/seq.c:106): a file of that name, or their F_CHK error and exit status 1 */
 int cli_dash_is_stdin = 0;
 
-cli_fastx_t *cli_fastx_open(const char *path)
+void *cli_gz_open(const char *path, int must_open)
 {
     gzFile fp = (cli_dash_is_stdin && !strcmp(path, "-")) ? gzdopen(fileno(stdin), "r") : gzopen(path, "r");
-    if (!fp) return NULL;
+    if (!fp) {
+        if (!must_open) return NULL; /* sdust: the reference has no NULL check (src/sdust/sdust.c:194) and crashes; the caller just stops */
+        CLI_ERROR("Could not to open file %s: %s", path, strerror(errno)); /* F_CHK, src/error.h:114-119: its words */
+        exit(EXIT_FAILURE);
+    }
     gzbuffer(fp, 1 << 18);
-    cli_fastx_t *f = (cli_fastx_t *)cli_xmalloc(sizeof(*f));
-    memset(f, 0, sizeof(*f));
-    f->fp = fp;
-    f->buf = (unsigned char *)cli_xmalloc(FX_BUF);
-    return f;
+    return fp;
 }
 
 cli_fastx_t *cli_fastx_open_prefixed(void *gz, const void *prefix, size_t n)
@@ -53,11 +57,21 @@ cli_fastx_t *cli_fastx_open_prefixed(void *gz, const void *prefix, size_t n)
     return f;
 }
 
+cli_fastx_t *cli_fastx_open(const char *path, int must_open)
+{
+    void *fp = cli_gz_open(path, must_open);
+    return fp ? cli_fastx_open_prefixed(fp, NULL, 0) : NULL;
+}
+
 void cli_fastx_close(cli_fastx_t *f)
 {
     if (!f) return;
     gzclose(f->fp);
     free(f->buf);
+    free(f->rec.name.s);
+    free(f->rec.comment.s);
+    free(f->rec.seq.s);
+    free(f->rec.qual.s);
     free(f);
 }
 
@@ -132,7 +146,8 @@ static int fx_until(cli_fastx_t *f, int line_mode, cli_str_t *s)
     return got_any ? 0 : -1;
 }
 
-int64_t cli_fastx_read(cli_fastx_t *f, cli_str_t *name, cli_str_t *comment, cli_str_t *seq, cli_str_t *qual)
+/* >= 0: sequence length; -1 end of file; -2 truncated quality string */
+static int64_t fx_read(cli_fastx_t *f, cli_str_t *name, cli_str_t *comment, cli_str_t *seq, cli_str_t *qual)
 {
     int c;
     if (f->last_char == 0) {
@@ -168,4 +183,42 @@ int64_t cli_fastx_read(cli_fastx_t *f, cli_str_t *name, cli_str_t *comment, cli_
     f->last_char = 0;
     if (seq->l != qual->l) return -2;
     return (int64_t)seq->l;
+}
+
+cli_rec_t *cli_fastx_next(cli_fastx_t *f)
+{
+    return fx_read(f, &f->rec.name, &f->rec.comment, &f->rec.seq, &f->rec.qual) >= 0 ? &f->rec : NULL;
+}
+
+cli_rec_t *cli_fastx_next_checked(cli_fastx_t *f)
+{
+    cli_rec_t *r = cli_fastx_next(f);
+    if (r && r->seq.l > 0x7fffffffULL) {
+        CLI_ERROR("record %s has %zu bases; the reference's reader is limited to 2^31-1 (src/kseq.h:185)", r->name.s, r->seq.l);
+        exit(EXIT_FAILURE);
+    }
+    return r;
+}
+
+void cli_fastx_batches(cli_fastx_t *f, cli_batch_fn fn, void *arg)
+{
+    cli_batch_t b;
+    memset(&b, 0, sizeof(b));
+    const int64_t limit = cli_batch_limit();
+    cli_rec_t *r;
+    while ((r = cli_fastx_next_checked(f)) != NULL) {
+        cli_batch_take(&b, r->name.s, &r->seq);
+        if (b.bases >= limit) {
+            fn(&b, arg);
+            cli_batch_clear(&b);
+        }
+    }
+    if (b.n) {
+        fn(&b, arg);
+        cli_batch_clear(&b);
+    }
+    free(b.names);
+    free(b.seqs);
+    free(b.lens);
+    cli_fastx_close(f);
 }

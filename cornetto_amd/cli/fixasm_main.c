@@ -3,7 +3,7 @@
  * src/fixasm.c:226-284 (load_paf), :287-338 (write_corrected_paf), :341-405 (fix_the_assembly), :419-480 (options), with the PAF
  * fields of src/pafrec.c:43-98.
  *
- * The PAF side (O(lines)) runs here on the host, with the parser of cli/tables.c.  The FASTA side goes through stream_records() (fasta_cmds.c): the records are framed on
+ * The PAF side (O(lines)) runs here on the host, with the parser of cli/tables.c.  The FASTA side goes through stream_records() (stream.c): the records are framed on
  * the device, the header lines are built here, and the output text — headers, bases forward or reverse-complemented, newlines — is
  * written on the device window by window (cornetto_emit_*) and copied into pinned slabs that go to stdout with write().
  * CORNETTO_EMIT_SLAB = bytes per window (default 32 MiB; never changes a byte of the output).  CORNETTO_ACCEL=no: the same on the
@@ -233,23 +233,15 @@ static void fixasm_scan(cornetto_accel_t *h, const cli_recname_t *r, int64_t n_r
 /* ---------------------------------------------------------------- the host path (CORNETTO_ACCEL=no) */
 static void fx_host_fasta(fx_run_t *R, const char *path)
 {
-    cli_fastx_t *fx = cli_fastx_open(path);
-    if (!fx) {
-        CLI_ERROR("Could not to open file %s: %s", path, strerror(errno));
-        exit(EXIT_FAILURE);
-    }
-    cli_str_t name = {0, 0, 0}, comment = {0, 0, 0}, seq = {0, 0, 0}, qual = {0, 0, 0};
-    int64_t l;
-    while ((l = cli_fastx_read(fx, &name, &comment, &seq, &qual)) >= 0) {
-        if (l > 0x7fffffffLL) {
-            CLI_ERROR("record %s has %lld bases; the reference's reader is limited to 2^31-1 (src/kseq.h:185)", name.s, (long long)l);
-            exit(EXIT_FAILURE);
-        }
+    cli_fastx_t *fx = cli_fastx_open(path, 1);
+    cli_rec_t *r;
+    while ((r = cli_fastx_next_checked(fx)) != NULL) {
+        const int64_t l = (int64_t)r->seq.l;
         char *nm;
         size_t nl;
-        const int32_t ci = fx_name(R, name.s, name.l, &nm, &nl);
+        const int32_t ci = fx_name(R, r->name.s, r->name.l, &nm, &nl);
         if (ci < 0) continue;
-        const char *s = seq.s ? seq.s : "";
+        const char *s = r->seq.s;
         if (R->ctg[ci].rc) {   /* reverse_complement(), :208-224 */
             if ((size_t)l + 1 > R->rcbuf_cap) {
                 R->rcbuf_cap = (size_t)l + 1;
@@ -267,10 +259,6 @@ static void fx_host_fasta(fx_run_t *R, const char *path)
         fwrite(s, 1, (size_t)l, stdout);
         fputc('\n', stdout);
     }
-    free(name.s);
-    free(comment.s);
-    free(seq.s);
-    free(qual.s);
     cli_fastx_close(fx);
 }
 
@@ -343,14 +331,7 @@ int fixasm_main(int argc, char *argv[])
     memset(&R, 0, sizeof(R));
     fx_load_paf(&R, paf);
     fx_trim_names(&R, trim);
-    {   /* the FASTA is opened before the report and missing files (:343-356) */
-        gzFile g = gzopen(fasta, "r");
-        if (!g) {
-            CLI_ERROR("Could not to open file %s: %s", fasta, strerror(errno));
-            exit(EXIT_FAILURE);
-        }
-        gzclose(g);
-    }
+    gzclose((gzFile)cli_gz_open(fasta, 1));   /* the FASTA is opened before the report and missing files (:343-356) */
     if (report) R.fp_report = cli_fopen_chk(report, "w");
     if (missing) R.fp_missing = cli_fopen_chk(missing, "w");
 
@@ -366,7 +347,7 @@ int fixasm_main(int argc, char *argv[])
             snprintf(one, sizeof(one), "%d", devs[0]);
             setenv("CORNETTO_DEVICE", one, 1);
         }
-        stream_records(fasta, 1, fixasm_scan, &R);
+        stream_records(fasta, 1, fixasm_scan, &R, 0);
     }
     fflush(stdout);
     fprintf(stderr, "total: %d\nnegative: %d\nmissing: %d\n", R.total, R.neg, R.missing);

@@ -459,11 +459,11 @@ def test_cli_fasta_then_fastq_in_one_file_and_stdin(tmp_path):
 
 
 @pytest.mark.parametrize("big_at", [None, 0, 7, 19])
-def test_cli_small_first_piece_then_full_pieces_read_ahead(tmp_path, big_at):
-    """round 5: with read-ahead the first pinned piece of an uncompressed FASTA file is small (CORNETTO_CLI_FIRST_MB, here 1 MiB of a
-    ~7 MB file) and the full-size buffers are made by the read-ahead thread; the small buffer comes back as the second buffer and is
-    made again at the full size; a record larger than the first piece (at the start, in the middle, at the end) grows it.  Same bytes as
-    without read-ahead and as the reference's sdust over the same records."""
+def test_cli_whole_text_pieces_and_growing_pieces_agree(tmp_path, big_at):
+    """An uncompressed FASTA file of ~7 MB through each framing path of the streamer: as one text on the device (the default), through the
+    piece loop with a piece that holds the file (CORNETTO_CLI_WHOLE=0), and through pieces of 1 MiB that must grow (CORNETTO_FASTQ_GROW=1)
+    because one record of 1.6 Mbases (at the start, in the middle, at the end) does not fit.  Same bytes every way, and those of the
+    reference's sdust over the same records."""
     rng = np.random.default_rng(99 if big_at is None else big_at)
     acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
     recs = []
@@ -481,14 +481,13 @@ def test_cli_small_first_piece_then_full_pieces_read_ahead(tmp_path, big_at):
     open(f, "wb").write(text)
     want = sdust_text(text)
     assert len(want) > 2000
-    rc0, out0, err0 = run_cli(["sdust", f], env={"CORNETTO_CLI_AHEAD": "0"})
-    assert rc0 == 0 and out0 == want
-    for first in ("1", "2", "64"):
-        rc, out, err = run_cli(["sdust", f], env={"CORNETTO_CLI_FIRST_MB": first})
-        assert rc == 0 and out == want, (first, err[-300:])
-    rc, out, err = run_cli(["telofind", f], env={"CORNETTO_CLI_FIRST_MB": "1"})
-    rc1, out1, _ = run_cli(["telofind", f], env={"CORNETTO_CLI_AHEAD": "0"})
-    assert rc == 0 and rc1 == 0 and out == out1 and len(out) > 1000
+    modes = {"whole": {}, "pieces": {"CORNETTO_CLI_WHOLE": "0"}, "growing": {"CORNETTO_FASTQ_PIECE": "1048576", "CORNETTO_FASTQ_GROW": "1"}}
+    for mode, env in modes.items():
+        rc, out, err = run_cli(["sdust", f], env=env)
+        assert rc == 0 and out == want, (mode, err[-300:])
+    telo = {mode: run_cli(["telofind", f], env=env) for mode, env in modes.items()}
+    for mode, (rc, out, err) in telo.items():
+        assert rc == 0 and out == telo["whole"][1] and len(out) > 1000, (mode, err[-300:])
 
 
 def test_cli_pieces_grow_until_the_largest_record_fits(golden_dir):

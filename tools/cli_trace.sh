@@ -1,6 +1,6 @@
 #!/bin/bash
 # development aid: the full CORNETTO_CLI_TRACE timeline of `cornetto sdust` / `telofind` on the bench assembly as a FASTA in /dev/shm
-# (tools/perf_cli_ahead.py writes it and keeps it when KEEP=1)   bash tools/cli_trace.sh [out-prefix]
+#   bash tools/cli_trace.sh [out-prefix]
 out=${1:-gpurun_out/r06_cli_trace}
 python3 - <<'PY'
 import os, sys

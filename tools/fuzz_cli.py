@@ -132,10 +132,10 @@ def fuzz_fasta(seed, tmp):
     rr = run(REF, args, data=data)
     env = {"CORNETTO_DEVICES": "0,0"} if rnd.random() < 0.2 else {}
     # the streaming paths of the CLI, with sizes that make a small text many pieces: the piece loop (a record cut by a piece's end, a piece without a
-    # record start), the read-ahead and the whole-text path on and off, the sequential reader instead of the device's framing, batches of a few records
+    # record start), the whole-text path on and off, the sequential reader instead of the device's framing, batches of a few records
     if rnd.random() < 0.6:
         for key, vals in (("CORNETTO_FASTQ_PIECE", ["64", "100", "517", "3000", "65536"]), ("CORNETTO_BATCH_BASES", ["1", "700", "50000"]), ("CORNETTO_CLI_WHOLE", ["0", "1"]),
-                          ("CORNETTO_CLI_AHEAD", ["0", "1"]), ("CORNETTO_READ_THREADS", ["1", "3"]), ("CORNETTO_CLI_MMAP", ["0", "1"]), ("CORNETTO_FASTQ_SPLIT", ["host", "device"]),
+                          ("CORNETTO_READ_THREADS", ["1", "3"]), ("CORNETTO_CLI_MMAP", ["0", "1"]), ("CORNETTO_FASTQ_SPLIT", ["host", "device"]),
                           ("CORNETTO_FASTQ_GROW", ["0", "1"])):
             if rnd.random() < 0.35:
                 env[key] = rnd.choice(vals)
