@@ -4,6 +4,9 @@ cornetto_sdust_buf_destroy(), include/cornetto_accel.h — against the UNMODIFIE
 oracle/_ref/libcornetto_ref.so, which travels with the snapshot) in one process: the same bytes, l_seq given and -1 (strlen), T and W varied
 over what the reference accepts, sequences of every byte value (no NUL when the length is -1), lengths 0 .. 200 kb, low-complexity runs at
 both ends (intervals that reach beyond the sequence), lower case, other letters.  The result arrays must be equal word for word.
+Windows above 100 (the kernels off the fast path: tests/test_gpu_sdust_wide.py) get a T scaled with W, at most six planted repeats of at most 120
+bases and up to 40 kb, more than one default chunk of 32 W: the reference's find_perfect is quadratic in W inside low-complexity sequence, which at
+T = 20 random sequence itself is for such windows, and it needs about a quarter of a second per planted repeat at a scaled T whatever the length.
    python tools/fuzz_abi_sdust.py [first_seed] [n_seeds]"""
 import ctypes as C
 import os
@@ -49,21 +52,22 @@ def main():
             s = np.frombuffer(b"ACGTacgtNn", dtype=np.uint8)[rng.integers(0, 10, size=ln)].copy()
         else:
             s = rng.integers(1, 256, size=ln, dtype=np.uint8)
-        for _ in range(int(rng.integers(0, max(2, ln // 250)))):
+        T = int(rng.choice([20, 20, 25, 10, 5, 30, 2, 64, 100]))
+        W = int(rng.choice([64, 64, 40, 30, 16, 8, 4, 66, 100, 200, 500, 1026]))
+        if W > 100:
+            T = max(T, (W - 2) // 7 + int(rng.integers(0, 20)))
+            ln = min(ln, 40000)
+            s = s[:ln].copy()
+        for _ in range(int(rng.integers(0, max(2, ln // 250) if W <= 100 else 7))):
             if ln < 8:
                 break
             p = int(rng.integers(0, ln))
-            rep = np.frombuffer(units[int(rng.integers(0, len(units)))] * int(rng.integers(1, 300)), dtype=np.uint8)
+            rep = np.frombuffer(units[int(rng.integers(0, len(units)))] * int(rng.integers(1, 300)), dtype=np.uint8)[:1800 if W <= 100 else 120]
             seg = s[p:p + len(rep)]
             seg[:] = rep[:len(seg)]
         if ln >= 40 and rng.random() < 0.4:                 # low-complexity runs flush with both ends: intervals beyond the sequence
             s[:30] = ord("A")
             s[ln - 35:] = np.frombuffer(b"TTAGGG" * 6, dtype=np.uint8)[:35]
-        T = int(rng.choice([20, 20, 25, 10, 5, 30, 2, 64, 100]))
-        W = int(rng.choice([64, 64, 40, 30, 16, 8, 4, 66, 100, 200, 500, 1026]))
-        if W > 100 and ln > (400 if W > 200 else 3000):      # (the reference's find_perfect is quadratic in W inside a repeat: seconds per kilobase at W = 1026)
-            s = s[:400 if W > 200 else 3000].copy()
-            ln = len(s)
         by_strlen = ln > 0 and rng.random() < 0.3 and not np.any(s == 0)
         cbuf = C.create_string_buffer(s.tobytes(), ln + 1)
         l_arg = -1 if by_strlen else ln
