@@ -122,6 +122,7 @@ def lib(dev=False):
         "cornetto_telowin_threshold": (C.c_double, [C.c_double, C.c_double]),
         "cornetto_telowin": (C.c_int, [vp, vp, i64, vp, i32, C.c_double, pp, C.POINTER(i64)]),
         "cornetto_telo_scan": (C.c_int, [vp, vp, cp, C.c_double, pp, C.POINTER(i64), pp, C.POINTER(i64)]),
+        "cornetto_telo_ends": (C.c_int, [vp, vp, cp, C.c_double, i32, i32, pp, C.POINTER(i64)]),
         "cornetto_sdust_asm": (C.c_int, [vp, vp, i32, i32, pp, C.POINTER(i64)]),
         "cornetto_sdust_asm_begin": (C.c_int, [vp, vp, i32, i32]),
         "cornetto_sdust_asm_end": (C.c_int, [vp, vp, i32, i32, pp, C.POINTER(i64)]),
@@ -407,6 +408,13 @@ class Accel:
                                             C.byref(pw), C.byref(nw)))
         hits = _take(self.L, ph, nh.value, HIT_DT) if want_hits else None
         return hits, _take(self.L, pw, nw.value, WIN_DT)
+
+    def telo_ends(self, asm, motif, thr_adj, merge_dist=100, ends=50000):
+        """cornetto_telo_ends(): the telomere regions at the contig ends (the rows of scripts/telostats.sh's BED) -> IVL_DT rows
+        (ctg, start, finish), a region once per end interval of its contig that it overlaps"""
+        p, n = C.c_void_p(), C.c_int64()
+        self._chk(self.L.cornetto_telo_ends(self.h, asm.ptr, motif, thr_adj, merge_dist, ends, C.byref(p), C.byref(n)))
+        return _take(self.L, p, n.value, IVL_DT)
 
     # ---- sdust -----------------------------------------------------------------------------------
     def sdust(self, asm, T=20, W=64):

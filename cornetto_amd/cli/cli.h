@@ -205,6 +205,10 @@ void cli_host_telofind(const uint8_t *seq, int64_t len, const char *motif, int32
 int cli_host_sdust(const uint8_t *seq, int64_t len, int T, int W, int32_t ctg, cornetto_ivl_t **ivls, int64_t *n_ivls, int64_t *cap_ivls); /* -1: -w / -t out of range */
 /* same contract as cornetto_telowin(); results are malloc memory */
 void cli_host_telowin(const cornetto_hit_t *hits, int64_t n_hits, const int32_t *lens, int32_t n_ctg, double thr_adj, cornetto_win_t **wins, int64_t *n_wins);
+/* the rows of cornetto_telo_ends() for ONE record (their ctg = `ctg`), appended to a growing array (n, cap in rows): telofind, telowin, a
+ * sequential bedtools merge -d and the intersection with the record's end intervals (scripts/telostats.sh:35-47) */
+void cli_host_telo_ends(const uint8_t *seq, int64_t len, const char *motif, double thr_adj, int32_t merge_dist, int32_t ends, int32_t ctg,
+                        cornetto_ivl_t **rows, int64_t *n_rows, int64_t *cap_rows);
 /* get_depths(): what the two bedgraphs hold; exits with the reference's messages on malformed input */
 typedef struct {
     int32_t n_ctg;
@@ -240,5 +244,6 @@ int nx_main(int argc, char *argv[]);
 int report_main(int argc, char *argv[]);
 int telocontigs_main(int argc, char *argv[]);
 int asmstats_main(int argc, char *argv[]);
+int telostats_main(int argc, char *argv[]);
 
 #endif

@@ -149,6 +149,58 @@ void cli_host_telowin(const cornetto_hit_t *hits, int64_t n_hits, const int32_t 
     *n_wins = n;
 }
 
+/* ------------------------------------------------------------------------------------------------ telostats
+ * scripts/telostats.sh:35-47 on one record, step by step as the script's pipeline does it: the runs (telofind), the windows (telowin),
+ * `bedtools merge -d merge_dist` as a sweep over the windows in start order, then `bedtools intersect -wa` against the record's end
+ * intervals (:44) — a region once per end interval it shares a base with.  Deliberately the sequential form, not the run-length rule of
+ * the device stage (csrc/telostats.hip): a second, independent statement of the same rows. */
+static void ends_push(cornetto_ivl_t **rows, int64_t *n, int64_t *cap, int32_t ctg, int64_t s, int64_t e, const int64_t (*iv)[2], int n_iv)
+{
+    for (int k = 0; k < n_iv; ++k) {
+        if (!(s < iv[k][1] && e > iv[k][0])) continue;             /* no base in common with this end interval */
+        if (*n == *cap) {
+            *cap = *cap ? *cap * 2 : 64;
+            *rows = (cornetto_ivl_t *)cli_xrealloc(*rows, (size_t)*cap * sizeof(**rows));
+        }
+        (*rows)[*n].ctg = ctg;
+        (*rows)[*n].start = (int32_t)s;
+        (*rows)[*n].finish = (int32_t)e;
+        ++*n;
+    }
+}
+
+void cli_host_telo_ends(const uint8_t *seq, int64_t len, const char *motif, double thr_adj, int32_t merge_dist, int32_t ends, int32_t ctg,
+                        cornetto_ivl_t **rows, int64_t *n_rows, int64_t *cap_rows)
+{
+    cornetto_hit_t *hits = NULL;
+    int64_t n_hits = 0, cap_hits = 0, n_wins = 0;
+    cornetto_win_t *wins = NULL;
+    const int32_t len32 = (int32_t)len;
+    cli_host_telofind(seq, len, motif, 0, &hits, &n_hits, &cap_hits);
+    cli_host_telowin(hits, n_hits, &len32, 1, thr_adj, &wins, &n_wins);
+    int64_t iv[2][2] = {{0, len}, {0, 0}};                         /* :44 */
+    int n_iv = 1;
+    if (len > 2 * (int64_t)ends) {
+        iv[0][1] = ends;
+        iv[1][0] = len - ends;
+        iv[1][1] = len;
+        n_iv = 2;
+    }
+    int64_t s = 0, e = -1;                                         /* the region being grown (none yet: e < 0) */
+    for (int64_t i = 0; i < n_wins; ++i) {
+        if (e >= 0 && wins[i].start <= e + merge_dist) {           /* bedtools merge -d: at most merge_dist behind the end so far */
+            if (wins[i].end > e) e = wins[i].end;
+            continue;
+        }
+        if (e >= 0) ends_push(rows, n_rows, cap_rows, ctg, s, e, (const int64_t (*)[2])iv, n_iv);
+        s = wins[i].start;
+        e = wins[i].end;
+    }
+    if (e >= 0) ends_push(rows, n_rows, cap_rows, ctg, s, e, (const int64_t (*)[2])iv, n_iv);
+    free(hits);
+    free(wins);
+}
+
 /* ------------------------------------------------------------------------------------------------ sdust
  * src/sdust/sdust.c:130-160 on one record, base by base.  State: the FIFO of the last <= W - 2 three-letter words with
  * its pair score (rw), the suffix of it in which no word occurs more than 2T/10 times (length L, pair score rv), the

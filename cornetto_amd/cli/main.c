@@ -1,6 +1,7 @@
 /* main.c — `cornetto <command>` dispatcher; mirrors src/main.c:95-152 of the reference for the
  * panel-creation sub-commands (same names, same exit codes, same 3-line stderr footer), for fixasm
- * (fixasm_main.c) and for the evaluation sub-commands asmstats, nx, report and telocontigs (eval_main.c).
+ * (fixasm_main.c), for the evaluation sub-commands asmstats, nx, report and telocontigs (eval_main.c) and for telostats, the reference's
+ * scripts/telostats.sh as one sub-command (telostats_main.c).
  * minidot, the one sub-command of the reference outside this build, is not in the usage text and exits
  * with status 1 as unrecognised; telobreaks is built and dispatched below. */
 #include <stdlib.h>
@@ -22,6 +23,7 @@ static int print_usage(FILE *fp)
     fprintf(fp, "       telowin         analyse telomere windows in a fasta file\n");
     fprintf(fp, "       telofind        find telomere sequences in a fasta file\n");
     fprintf(fp, "       telobreaks      find telomere sequences inside low-complexity runs\n");
+    fprintf(fp, "       telostats       telomere regions at the contig ends (telomere.bed for telocontigs and asmstats)\n");
     fprintf(fp, "       sdust           symmetric DUST (https://github.com/lh3/sdust)\n");
     fprintf(fp, "   assembly toolkit:\n");
     fprintf(fp, "       fixasm          rename and reorient assembly contigs after their alignments to a reference\n");
@@ -55,6 +57,8 @@ int main(int argc, char *argv[])
         ret = telomere_windows_main(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "telobreaks") == 0) {
         ret = telomere_breaks_main(argc - 1, argv + 1);
+    } else if (strcmp(argv[1], "telostats") == 0) {
+        ret = telostats_main(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "telofind") == 0) {
         ret = find_telomere_main(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "bigenough") == 0) {

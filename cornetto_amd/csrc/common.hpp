@@ -83,6 +83,7 @@ struct cornetto_accel {
     // between calls), the tiles of a call take their numbers from a ticket counter that is never reset
     uint32_t scan_epoch = 0, scan_tickets = 0;
     uint32_t st_epoch = 0, st_tickets = 0;          // the same for the single-pass interval merge (ivlmerge.hpp, WS_STITCH)
+    size_t te_cap = 0;  // cornetto_telo_ends: regions the largest call so far needed (the next call's region list has room for them)
     int timing = 2;     // event pairs around: 2 every kernel launch, 1 the three streaming / scanning main kernels only, 0 none (cornetto_accel_set_timing)
 };
 
@@ -153,11 +154,12 @@ enum {   // device workspace slots
     WS_TB, WS_TB_SMALL, WS_TB_OUT, WS_CW_MERGE, WS_IVL_MERGE,
     WS_FQ_TEXT, WS_FQ_CNT, WS_FQ_NL, WS_FQ_RECS, WS_FQ_ENDS, WS_FQ_SRC,
     WS_SCAN, WS_STITCH,
+    WS_TE_WORDS, WS_TE_REG, WS_TE_ROWS, WS_TE_CNT,
     WS_COUNT
 };
 static_assert(WS_COUNT <= 64, "cornetto_accel::dev has 64 slots");
 enum {   // pinned host slots
-    PIN_A, PIN_B, PIN_C, PIN_D, PIN_E, PIN_F, PIN_SMALL, PIN_TW, PIN_CW, PIN_STEP
+    PIN_A, PIN_B, PIN_C, PIN_D, PIN_E, PIN_F, PIN_SMALL, PIN_TW, PIN_CW, PIN_STEP, PIN_TE
 };
 
 static inline int cn_fail(cornetto_accel_t *h, int status, const char *fmt, ...)

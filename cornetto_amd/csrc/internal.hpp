@@ -43,3 +43,8 @@ int cn_telo_spec_finish(cornetto_accel_t *h, cornetto_asm_t *a, const char *moti
                         cornetto_win_t **wins, int64_t *n_wins);
 int cn_telo_scan_impl(cornetto_accel_t *h, const cornetto_asm_t *a, const char *motif, double thr_adj, cornetto_hit_t **hits, int64_t *n_hits, cornetto_win_t **wins,
                       int64_t *n_wins);
+
+// The mark bitmap of a telomere scan alone (1 bit per base: the bases covered by a telofind run of either strand), left on the device in the
+// window layout of the assembly (cornetto_asm::d_tw_boff, d_tw_tiles, tw_n_tiles): written by tf_scan beside its matches for a motif without
+// a border, built from the runs otherwise.  Synchronises.  telostats.hip turns it into the merged regions at the contig ends.
+int cn_telo_marks_impl(cornetto_accel_t *h, const cornetto_asm_t *a, const char *motif, const unsigned long long **d_marks);

@@ -18,7 +18,7 @@
 // tf_greedy for motifs WITH a border (AAAA, ACACA ...) only: the sequential greedy rule of
 //           src/find_telomere.c:49-58 over the compacted match list, one thread per (contig,strand).
 // tw_fill   marks [start,end) of explicit hits in the bitmap (src/telomere_windows.c:75-79).
-// tw_scan   one thread per 200-bp window start: popcount of <=1000 bitmap bits, double-precision
+// tw_scan   one thread per 200-bp window start: popcount of <=1000 bitmap bits (telowin_tile.hpp), double-precision
 //           car/den >= threshold exactly as :36-37, passing windows appended.
 #include <algorithm>
 #include <cmath>
@@ -27,6 +27,7 @@
 #include "common.hpp"
 #include "scan.hpp"
 #include "tiles.hpp"
+#include "telowin_tile.hpp"
 #include "internal.hpp"
 
 namespace {
@@ -484,59 +485,22 @@ struct TwArgs {
     uint32_t cap;
 };
 
-__device__ __forceinline__ int popc_range(const unsigned long long *bm, long long a, long long b)
-{
-    int c = 0;
-    while (a < b) {
-        const long long wi = a >> 6;
-        const int lo = (int)(a & 63);
-        const long long wend = (wi + 1) << 6;
-        const int hi = (int)((b < wend ? b : wend) - (wi << 6));
-        const unsigned long long m = (hi == 64 ? ~0ull : ((1ull << hi) - 1ull)) & ~((1ull << lo) - 1ull);
-        c += __popcll(bm[wi] & m);
-        a = wend;
-    }
-    return c;
-}
-
-// One thread per window start j (every 200 bases, :31); a window is five blocks of 200 bases (the last ones clipped at the contig's
-// end, :36), so a workgroup counts its 260 blocks ONCE (4-5 bitmap words each) and a window adds five counts — the first version
-// counted the 16-17 words of every window per thread: 0.11 G wave-instructions per 3.16 Gbp step, a quarter of that now.
+// One thread per window start j (every 200 bases, :31): the window's mark count comes from telowin_tile.hpp (the workgroup's 260 blocks
+// counted once, a window adds five counts); passing windows are appended.
 __global__ __launch_bounds__(256) void tw_scan(TwArgs A)
 {
     __builtin_amdgcn_s_setprio(CN_STREAM_PRIO);   // short streaming kernel: issue ahead of a long compute-bound kernel of another stream
 
-    __shared__ int bc[256 + 4];
-    __shared__ unsigned long long sw[816];            // the workgroup's 260 blocks of marks: 52 000 bits from any bit of a word
+    __shared__ int bc[cntw::TW_BLOCKS];
+    __shared__ unsigned long long sw[cntw::TW_WORDS];
     const int2 tile = A.tiles[blockIdx.x];
     const int ctg = tile.x;
-    const int len = A.ctg_len[ctg];
-    const long long boff = A.bit_off[ctg];
-    // the words once, side by side (round 5; before: every thread its own 4-5 words one after the other — a chain of dependent round trips
-    // to memory per workgroup, 0.166 ms for 0.4 GB; 0.138 now), the counts from LDS
-    const long long bit0 = boff + (long long)tile.y * 200, bit1 = boff + len < bit0 + 260 * 200 ? boff + len : bit0 + 260 * 200;
-    const long long w0 = bit0 >> 6;
-    const int nw = bit1 > bit0 ? (int)(((bit1 + 63) >> 6) - w0) : 0;
-    for (int k = threadIdx.x; k < nw; k += 256) sw[k] = A.bitmap[w0 + k];
-    __syncthreads();
-    for (int k = threadIdx.x; k < 260; k += 256) {
-        const long long lo = ((long long)tile.y + k) * 200;
-        const long long hi = lo + 200 < len ? lo + 200 : len;
-        bc[k] = lo < hi ? popc_range(sw, boff + lo - (w0 << 6), boff + hi - (w0 << 6)) : 0;
-    }
-    __syncthreads();
-    const long long j = (long long)tile.y + threadIdx.x;
-    const long long i = j * 200;                                   // WINDOW_SIZE / 5, :31
-    // the loop of :31-41 visits i = 0, 200, ... up to and including the first i with i + 1000 >= len
-    if (i > len) return;
-    if (i > 0 && (i - 200) + 1000 >= len) return;
-    const long long end = (i + 1000 < len) ? i + 1000 : len;
-    const int den = (int)(end - i);                                // :36
-    const int t = threadIdx.x;
-    const int car = bc[t] + bc[t + 1] + bc[t + 2] + bc[t + 3] + bc[t + 4];
-    if ((double)car / den >= A.thr) {                              // :37 (0/0 -> NaN -> false, as in C)
+    const cntw::Window w = cntw::tile_window(A.bitmap, A.bit_off[ctg], A.ctg_len[ctg], tile, bc, sw);
+    if (!w.visited) return;
+    const int den = w.end - w.start;                               // :36
+    if ((double)w.car / den >= A.thr) {                            // :37 (0/0 -> NaN -> false, as in C)
         const unsigned long long idx = atomicAdd(A.counter, 1ull);
-        if (idx < A.cap) A.out[idx] = make_int4(ctg, (int)i, (int)end, car);
+        if (idx < A.cap) A.out[idx] = make_int4(ctg, w.start, w.end, w.car);
     }
 }
 
@@ -1067,6 +1031,54 @@ int cn_telo_scan_impl(cornetto_accel_t *h, const cornetto_asm_t *a, const char *
         *hits = hh;
         *n_hits = nh;
     }
+    return rc;
+}
+
+// ---- the marks alone (internal.hpp): what cornetto_telo_ends builds its regions from ----------------------------------------------------
+int cn_telo_marks_impl(cornetto_accel_t *h, const cornetto_asm_t *a, const char *motif, const unsigned long long **d_marks)
+{
+    *d_marks = nullptr;
+    cornetto_asm_t *am = const_cast<cornetto_asm_t *>(a);   // only its cached tables are touched
+    const std::string m(motif ? motif : "");
+    const bool by_hits = has_border(m) || has_border(revcomp(m));
+    unsigned long long *d_bitmap = nullptr;
+    bool valid = false;
+    cornetto_hit_t *hh = nullptr;
+    int64_t nh = 0;
+    CN_TRY(telofind_impl(h, a, motif, by_hits ? &hh : nullptr, by_hits ? &nh : nullptr, !by_hits, &d_bitmap, &valid));
+    if (valid) {                                            // (a motif without a border: tf_scan wrote the marks beside its matches)
+        *d_marks = d_bitmap;
+        return CORNETTO_OK;
+    }
+    // a motif with a border (its marks are those of the greedy runs, not of every match), or an assembly without a base: the runs
+    // marked in the assembly's own window layout, as telowin_from_hits() marks them in the layout of a table of lengths
+    int rc = [&]() -> int {
+        if (!by_hits) CN_TRY(telofind_impl(h, a, motif, &hh, &nh, false, nullptr, nullptr));
+        CN_TRY(ensure_tw_layout(h, am));
+        cn_result_quiesce(h);                               // (a lazy handle copies large results on a stream of its own)
+        std::vector<int4> hv;
+        hv.reserve((size_t)nh);
+        for (int64_t i = 0; i < nh; ++i) {
+            const cornetto_hit_t &x = hh[i];
+            if (x.start >= x.end) continue;
+            const int64_t bo = am->tw_boff[x.ctg];
+            hv.push_back(make_int4((int)(uint32_t)(bo & 0xFFFFFFFFll), (int)(uint32_t)(bo >> 32), x.start, x.end));
+        }
+        unsigned long long *d_bm = (unsigned long long *)cn_ws(h, WS_TW_BITMAP, (size_t)am->tw_n_words * 8);
+        int4 *d_hits = (int4 *)cn_ws(h, WS_TW_HITS, hv.size() * sizeof(int4));
+        if (!d_bm || !d_hits) return cn_fail(h, CORNETTO_E_NOMEM, "telo_ends: workspace allocation failed");
+        CN_HIP(h, hipMemsetAsync(d_bm, 0, (size_t)am->tw_n_words * 8, h->stream));
+        if (!hv.empty()) {
+            CN_HIP(h, hipMemcpyAsync(d_hits, hv.data(), hv.size() * sizeof(int4), hipMemcpyHostToDevice, h->stream));
+            const unsigned nb = (unsigned)((hv.size() + 255) / 256);
+            CN_LAUNCH(h, "tw_fill", tw_fill<<<dim3(nb), dim3(256), 0, h->stream>>>(d_hits, (int64_t)hv.size(), d_bm));
+        }
+        CN_HIP(h, hipStreamSynchronize(h->stream));         // `hv` is a local
+        *d_marks = d_bm;
+        return CORNETTO_OK;
+    }();
+    cn_result_quiesce(h);
+    cornetto_free(hh);
     return rc;
 }
 

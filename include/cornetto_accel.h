@@ -207,6 +207,17 @@ int cornetto_telowin(cornetto_accel_t *h, const cornetto_hit_t *hits, int64_t n_
 int cornetto_telo_scan(cornetto_accel_t *h, const cornetto_asm_t *a, const char *motif, double thr_adj,
                        cornetto_hit_t **hits, int64_t *n_hits, cornetto_win_t **wins, int64_t *n_wins);
 
+/* The telomere regions at the contig ends, i.e. the rows of PREFIX.windows.0.4.50kb.ends.bed of scripts/telostats.sh:35-47, in one pass
+ * on the device:  telofind | telowin (thr_adj = cornetto_telowin_threshold(0.4, 99.9)) | bedtools merge -d merge_dist | bedtools
+ * intersect -wa against the end intervals of every contig — [0, ends) and [len - ends, len) if len > 2 ends, else [0, len) (:44).
+ * The qualifying windows of a contig (src/telomere_windows.c:31-41) are merged while the next one starts at most merge_dist behind the
+ * end of the last; a region is returned once per end interval it overlaps by at least one base (0, 1 or 2 times, the copies adjacent),
+ * regions by contig index, then by start.  Neither the hits nor the windows leave the device.  ends >= 1;
+ * 0 <= merge_dist <= CORNETTO_TELO_ENDS_MAX_DIST (CORNETTO_E_UNSUPPORTED beyond).  Release rows with cornetto_free(). */
+#define CORNETTO_TELO_ENDS_MAX_DIST 11799
+int cornetto_telo_ends(cornetto_accel_t *h, const cornetto_asm_t *a, const char *motif, double thr_adj, int32_t merge_dist, int32_t ends,
+                       cornetto_ivl_t **rows, int64_t *n_rows);
+
 /* ---------------------------------------------------------------------------------------------------
  * sdust
  * ------------------------------------------------------------------------------------------------- */
