@@ -36,6 +36,14 @@ class BgErr(C.Structure):
     _fields_ = [("kind", C.c_int32), ("record", C.c_int64), ("a", C.c_int32), ("b", C.c_int32)]
 
 
+class BgRunErr(C.Structure):
+    """cornetto_bgrunerr_t (include/cornetto_accel.h)"""
+    _fields_ = [("kind", C.c_int32), ("file", C.c_int32), ("record", C.c_int64), ("a", C.c_int32), ("b", C.c_int32)]
+
+
+BGRUN_TILE = 4096     # CORNETTO_BGRUN_TILE: positions per workgroup of the run expansion (checked against the library when it is loaded)
+
+
 class StepOpt(C.Structure):
     """cornetto_step_opt_t (include/cornetto_accel.h)"""
     _fields_ = [("motif", C.c_char_p), ("thr_adj", C.c_double), ("window_size", C.c_int32), ("window_inc", C.c_int32), ("low_cov", C.c_float),
@@ -46,11 +54,12 @@ SUMS_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_uint64), C.c_void_p)
 
 
 class BedgraphFormatError(ValueError):
-    """a check of the reference's get_depths() failed (kind / record / numbers as in cornetto_bgerr_t)"""
+    """a check of the reference's get_depths() failed (kind / record / numbers as in cornetto_bgerr_t), or one of the run-length reader
+    (cornetto_bgrunerr_t: `file` is 0 or 1 there, None for the per-base reader)"""
 
-    def __init__(self, kind, record, a, b):
-        super().__init__("bedgraph check %d failed at record %d (%d, %d)" % (kind, record, a, b))
-        self.kind, self.record, self.a, self.b = kind, record, a, b
+    def __init__(self, kind, record, a, b, file=None):
+        super().__init__("bedgraph check %d failed at record %d (%d, %d)%s" % (kind, record, a, b, "" if file is None else " of file %d" % file))
+        self.kind, self.record, self.a, self.b, self.file = kind, record, a, b, file
 
 
 class AccelError(RuntimeError):
@@ -156,11 +165,19 @@ def lib(dev=False):
         "cornetto_bgin_error": (C.POINTER(BgErr), [vp]),
         "cornetto_bgin_done": (C.c_int, [vp]),
         "cornetto_bgin_finish": (C.c_int, [vp, vp, pp, C.POINTER(i32), C.POINTER(C.POINTER(cp)), C.POINTER(i64)]),
+        "cornetto_bgrun_tile": (i32, []),
+        "cornetto_bgrun_open": (C.c_int, [vp, pp]),
+        "cornetto_bgrun_close": (None, [vp, vp]),
+        "cornetto_bgrun_feed": (C.c_int, [vp, vp, C.c_int, cp, i64, C.c_int]),
+        "cornetto_bgrun_error": (C.POINTER(BgRunErr), [vp]),
+        "cornetto_bgrun_finish": (C.c_int, [vp, vp, pp, C.POINTER(i32), C.POINTER(C.POINTER(cp)), C.POINTER(i64)]),
+        "cornetto_cov_download": (C.c_int, [vp, vp, i32, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
+    assert L.cornetto_bgrun_tile() == BGRUN_TILE
     L._declared = sorted(sig)
     _libs[path] = L
     return L
@@ -516,6 +533,13 @@ class Accel:
         cov.w, cov.inc = w, inc
         return int(sums[0]), int(sums[1]), int(sums[2])
 
+    def cov_download(self, cov, ctg):
+        """-> (depth, mq_depth) of contig `ctg`, position by position: cornetto_cov_download()"""
+        d = np.zeros(int(cov.lens[ctg]), dtype=np.uint16)
+        q = np.zeros(int(cov.lens[ctg]), dtype=np.uint16)
+        self._chk(self.L.cornetto_cov_download(self.h, cov.ptr, ctg, d.ctypes.data, q.ctypes.data))
+        return d, q
+
     def cov_regs(self, cov, ctg):
         n = self.L.cornetto_n_reg(int(cov.lens[ctg]), cov.w, cov.inc)
         out = np.zeros(n, dtype=REG_DT)
@@ -583,6 +607,48 @@ class Accel:
         return out
 
     # ---- bedgraph ingest ---------------------------------------------------------------------------
+    def _ingested(self, cov, nc, names, ncl):
+        """what cornetto_bgin_finish() / cornetto_bgrun_finish() hand over -> (resident coverage, [contig names], clamped count)"""
+        L = self.L
+        nm = [names[i] for i in range(nc.value)]
+        lens = [L.cornetto_cov_lens(cov)[i] for i in range(nc.value)]
+        # the name strings are malloc'd by the library: release them with libc free
+        libc = C.CDLL(None)
+        libc.free.argtypes = [C.c_void_p]
+        arr = C.cast(names, C.POINTER(C.c_void_p))
+        for i in range(nc.value):
+            libc.free(arr[i])
+        libc.free(C.cast(names, C.c_void_p))
+        return _Resident(self, cov, L.cornetto_cov_free, lens), nm, ncl.value
+
+    def bedgraph_runs_ingest(self, tot_pieces, mq_pieces, alternate=True):
+        """stream two RUN-LENGTH bedgraphs (iterables of bytes pieces, any split points) through cornetto_bgrun_*; returns what
+        bedgraph_ingest() returns for their per-base expansion.  alternate: the pieces of the two files take turns (else all of cov-total,
+        then all of cov-mq).  Raises BedgraphFormatError (kind, file, record, a, b of cornetto_bgrunerr_t)."""
+        L = self.L
+        bg = C.c_void_p()
+        self._chk(L.cornetto_bgrun_open(self.h, C.byref(bg)))
+        try:
+            pieces = [list(tot_pieces) or [b""], list(mq_pieces) or [b""]]
+            if alternate:
+                order = sorted((i, f) for f in (0, 1) for i in range(len(pieces[f])))
+            else:
+                order = [(i, f) for f in (0, 1) for i in range(len(pieces[f]))]
+
+            def check(rc):
+                if rc == -6:
+                    e = L.cornetto_bgrun_error(bg).contents
+                    raise BedgraphFormatError(e.kind, e.record, e.a, e.b, e.file)
+                self._chk(rc)
+            for i, f in order:
+                t = pieces[f][i]
+                check(L.cornetto_bgrun_feed(self.h, bg, f, t, len(t), 1 if i == len(pieces[f]) - 1 else 0))
+            cov, nc, names, ncl = C.c_void_p(), C.c_int32(), C.POINTER(C.c_char_p)(), C.c_int64()
+            check(L.cornetto_bgrun_finish(self.h, bg, C.byref(cov), C.byref(nc), C.byref(names), C.byref(ncl)))
+            return self._ingested(cov, nc, names, ncl)
+        finally:
+            L.cornetto_bgrun_close(self.h, bg)
+
     def bedgraph_ingest(self, tot_pieces, mq_pieces, prefetch=0):
         """stream the two per-base bedgraphs (iterables of bytes pieces, any split points) through the device
         parser; returns (resident coverage, [contig names], clamped count).  Raises BedgraphFormatError.
@@ -615,16 +681,7 @@ class Accel:
                     break
             cov, nc, names, ncl = C.c_void_p(), C.c_int32(), C.POINTER(C.c_char_p)(), C.c_int64()
             self._chk(L.cornetto_bgin_finish(self.h, bg, C.byref(cov), C.byref(nc), C.byref(names), C.byref(ncl)))
-            nm = [names[i] for i in range(nc.value)]
-            lens = [L.cornetto_cov_lens(cov)[i] for i in range(nc.value)]
-            # the name strings are malloc'd by the library: release them with libc free
-            libc = C.CDLL(None)
-            libc.free.argtypes = [C.c_void_p]
-            arr = C.cast(names, C.POINTER(C.c_void_p))
-            for i in range(nc.value):
-                libc.free(arr[i])
-            libc.free(C.cast(names, C.c_void_p))
-            return _Resident(self, cov, L.cornetto_cov_free, lens), nm, ncl.value
+            return self._ingested(cov, nc, names, ncl)
         finally:
             L.cornetto_bgin_close(self.h, bg)
 

@@ -8,7 +8,12 @@
  * Extension (not in the reference, off by default): `noboringbits ... --panel assembly.bed [--lowq lowQ.bed]` prints
  * what steps 1-9 of scripts/create-cornetto.sh:41-66 produce (the boring bits before `bigenough`) instead of the
  * window lines: the windows are merged on the device (bedtools merge -d 1000, >= 30 kb) and the rest of the bedtools /
- * awk glue is cornetto_panel_boring().  assembly.bed is the output of `cornetto fa2bed`. */
+ * awk glue is cornetto_panel_boring().  assembly.bed is the output of `cornetto fa2bed`.
+ *
+ * Extension (not in the reference, off by default): `--runs` reads both files as RUN-LENGTH bedgraphs (`name start end value`, one record per
+ * run of equal depth: mosdepth per-base output, `bedtools genomecov -bga`) and prints what the same command without it prints on their per-base
+ * expansion — a record `name s e v` stands for the lines `name p p+1 v`, p = s .. e-1.  The runs are expanded on the device (cornetto_bgrun_*);
+ * everything behind the ingest is the same code.  Without the option such a file is refused as in the reference (end=start+1). */
 #include <getopt.h>
 #include <math.h>
 #include <stdlib.h>
@@ -42,6 +47,8 @@ static void print_help(FILE *fp, const optp_t *o)
     fprintf(fp, "   -h                         help\n");
     fprintf(fp, "   --verbose INT              verbosity level [%d]\n", cli_log_level);
     fprintf(fp, "   --accel=yes|no             Running on accelerator [yes]\n");
+    fprintf(fp, "   --runs                     (extension) the depth files are run-length bedgraphs: name start end value,\n");
+    fprintf(fp, "                              one record per run (mosdepth, bedtools genomecov -bga); contigs start at 0, no gaps\n");
 }
 
 /* ---- --panel: steps 4-9 of scripts/create-cornetto.sh on the merged fun windows ---------------------------------- */
@@ -344,6 +351,78 @@ static void bg_job_check(const bg_job_t *g, const char *name_t, const char *name
         CLI_ERROR("%s", g->err);
         exit(EXIT_FAILURE);
     }
+}
+
+/* ---------------- --runs: two run-length bedgraphs, expanded on the device (cornetto_bgrun_*) ----------------
+ * The files are independent streams (their run boundaries differ): all of one, then the other — no lock step, no top-up.  A regular file is read by
+ * the pread() threads into one pinned slab while the device parses the other; anything else (FIFOs, $CORNETTO_BG_THREADS=0) with fread(). */
+static void runs_ingest(cornetto_accel_t *h, FILE *ft, FILE *fq, const char *const *paths, int64_t piece, int n_rd, cornetto_cov_t **cov, int32_t *n_ctg,
+                        char ***names, int64_t *n_clamped)
+{
+    FILE *fp[2] = {ft, fq};
+    char *slab[2] = {(char *)cornetto_pinned_alloc((size_t)piece), (char *)cornetto_pinned_alloc((size_t)piece)};
+    if (!slab[0] || !slab[1]) {
+        CLI_ERROR("%s", "cannot allocate pinned read buffers");
+        exit(EXIT_FAILURE);
+    }
+    cornetto_bgrun_t *bg = NULL;
+    cli_accel_check(h, cornetto_bgrun_open(h, &bg), "run-length bedgraph ingest");
+    int rc = CORNETTO_OK;
+    for (int f = 0; f < 2 && rc == CORNETTO_OK; ++f) {
+        struct stat st;
+        if (n_rd > 0 && fstat(fileno(fp[f]), &st) == 0 && S_ISREG(st.st_mode)) {
+            const int64_t size = (int64_t)st.st_size;
+            int64_t off = 0;
+            bg_round_t rd[2];
+            memset(rd, 0, sizeof(rd));
+            for (int i = 0; i < 2; ++i) {
+                rd[i].fd[0] = rd[i].fd[1] = fileno(fp[f]);
+                rd[i].dst[0] = slab[i];
+                rd[i].n_threads = n_rd;
+            }
+            rd[0].want[0] = size < piece ? size : piece;
+            bg_round_post(&rd[0]);
+            for (int k = 0, eof = 0; !eof && rc == CORNETTO_OK; ++k) {
+                bg_round_t *r = &rd[k & 1], *nx = &rd[(k + 1) & 1];
+                bg_round_join(r);
+                if (r->got[0] < 0) {
+                    CLI_ERROR("reading %s failed", paths[f]);
+                    exit(EXIT_FAILURE);
+                }
+                off += r->got[0];
+                eof = r->got[0] < r->want[0] || off >= size;
+                if (!eof) { /* the next piece is read while this one is parsed */
+                    nx->off[0] = off;
+                    nx->want[0] = size - off < piece ? size - off : piece;
+                    bg_round_post(nx);
+                }
+                rc = cornetto_bgrun_feed(h, bg, f, r->dst[0], r->got[0], eof);
+            }
+            for (int i = 0; i < 2; ++i)
+                if (rd[i].started) bg_round_join(&rd[i]); /* never leave a reader behind */
+        } else {
+            for (int eof = 0; !eof && rc == CORNETTO_OK;) {
+                const size_t got = fread(slab[0], 1, (size_t)piece, fp[f]);
+                if (got < (size_t)piece) {
+                    if (ferror(fp[f])) {
+                        CLI_ERROR("reading %s failed", paths[f]);
+                        exit(EXIT_FAILURE);
+                    }
+                    eof = 1;
+                }
+                rc = cornetto_bgrun_feed(h, bg, f, slab[0], (int64_t)got, eof);
+            }
+        }
+    }
+    if (rc == CORNETTO_OK) rc = cornetto_bgrun_finish(h, bg, cov, n_ctg, names, n_clamped);
+    if (rc == CORNETTO_E_FORMAT) {
+        const cornetto_bgrunerr_t *e = cornetto_bgrun_error(bg);
+        cli_runs_fail(paths[e->file], e->kind, (long long)e->record, e->a, e->b);
+    }
+    cli_accel_check(h, rc, "run-length bedgraph ingest");
+    cornetto_bgrun_close(h, bg);
+    cornetto_pinned_free(slab[0]);
+    cornetto_pinned_free(slab[1]);
 }
 
 /* ---------------- where to cut two per-base bedgraphs into shares of whole contigs ----------------
@@ -776,11 +855,12 @@ static void print_bits(char **names, const int32_t *lens, int32_t n_ctg, const c
 }
 
 /* --accel=no / CORNETTO_ACCEL=no: the whole sub-command on the host (cli/host_backend.c), the_boring_bits() :483-536 */
-static int host_bits(FILE *ft, FILE *fq, const optp_t *opt, int8_t boring, const char *panel_bed, const char *lowq_bed)
+static int host_bits(FILE *ft, FILE *fq, const optp_t *opt, int8_t boring, const char *panel_bed, const char *lowq_bed, const char *const *runs_paths)
 {
     double t0 = cli_realtime();
     cli_host_cov_t cov;
-    cli_host_get_depths(ft, fq, &cov);
+    if (runs_paths) cli_host_get_depths_runs(ft, fq, runs_paths[0], runs_paths[1], &cov);
+    else cli_host_get_depths(ft, fq, &cov);
     fclose(ft);
     fclose(fq);
     if (cov.n_clamped) CLI_WARNING("%lld depth values were truncated to 65535", (long long)cov.n_clamped);
@@ -832,12 +912,12 @@ int boringbits_main(int argc, char *argv[], int8_t boring)
         {"high-thresh", required_argument, 0, 'H'}, {"low-mq-thresh", required_argument, 0, 'Q'},
         {"min-ctg-len", required_argument, 0, 'm'}, {"edge-len", required_argument, 0, 'e'},
         {"panel", required_argument, 0, 0},       {"lowq", required_argument, 0, 0},
-        {"panel-params", required_argument, 0, 0},
+        {"panel-params", required_argument, 0, 0}, {"runs", no_argument, 0, 0},
         {0, 0, 0, 0}};
     optp_t opt = {2500, 50, 0.4f, 2.5f, 0.4f, 1000000, 100000}; /* :540-556 */
     const char *covmq = NULL, *panel_bed = NULL, *lowq_bed = NULL;
     FILE *fp_help = stderr;
-    int c, li = 0;
+    int c, li = 0, runs = 0;
     optind = 1;
     while ((c = getopt_long(argc, argv, "t:B:K:v:o:q:Q:H:L:w:i:e:m:hV", lo, &li)) >= 0) {
         if (c == 'K') {
@@ -884,6 +964,8 @@ int boringbits_main(int argc, char *argv[], int8_t boring)
                 CLI_ERROR("%s", "--panel-params wants seven integers: merge-d,min-fun-len,min-lowq-len,extend,edge-len,merge-d2,min-ctg-len (or nine: ...,extend-right,extend-gate)");
                 exit(EXIT_FAILURE);
             }
+        } else if (c == 0 && li == 21) {
+            runs = 1;
         } else if (c == 0 && li == 9) { /* --accel: the seam the reference left (src/boringbits_main.c:627-632) */
             if (strcmp(optarg, "no") == 0 || strcmp(optarg, "n") == 0) {
                 cli_host_set(1);       /* the host path of cli/host_backend.c: sequential parse, window sums, selection */
@@ -920,7 +1002,8 @@ int boringbits_main(int argc, char *argv[], int8_t boring)
         CLI_ERROR("Failed to open %s : No such file or directory.", covmq);
         exit(EXIT_FAILURE);
     }
-    if (cli_host_mode()) return host_bits(ft, fq, &opt, boring, panel_bed, lowq_bed);
+    const char *const run_paths[2] = {covtotal, covmq};
+    if (cli_host_mode()) return host_bits(ft, fq, &opt, boring, panel_bed, lowq_bed, runs ? run_paths : NULL);
     int devs[CLI_MAX_DEV];
     const int n_dev = cli_device_list(devs);
     if (n_dev >= 1) { /* the text is parsed on the first listed device */
@@ -941,7 +1024,7 @@ int boringbits_main(int argc, char *argv[], int8_t boring)
     if (getenv("CORNETTO_BG_PIECE") && atoll(getenv("CORNETTO_BG_PIECE")) > 0) piece = atoll(getenv("CORNETTO_BG_PIECE"));
     int64_t cut_t[CLI_MAX_DEV], cut_q[CLI_MAX_DEV];
     int n_sh = 1;
-    if (threaded) {
+    if (threaded && !runs) {
         int64_t shard_min = 64ll << 20;
         if (getenv("CORNETTO_BG_SHARD_MIN") && atoll(getenv("CORNETTO_BG_SHARD_MIN")) > 0) shard_min = atoll(getenv("CORNETTO_BG_SHARD_MIN"));
         if (n_dev >= 2 && !panel_bed && (int64_t)st_t.st_size >= shard_min * n_dev && (int64_t)st_q.st_size >= shard_min * n_dev)
@@ -964,7 +1047,10 @@ int boringbits_main(int argc, char *argv[], int8_t boring)
     cornetto_ivl_t *fun = NULL;
     int64_t n_recs = 0, n_fun = 0;
     int recs_are_malloced = 0, stage_done = 0;
-    if (threaded) {
+    if (runs) {
+        h = cli_accel_open_end();
+        runs_ingest(h, ft, fq, run_paths, piece, n_rd, &cov, &n_ctg, &names, &n_clamped);
+    } else if (threaded) {
         bg_job_t jobs[CLI_MAX_DEV];
         memset(jobs, 0, sizeof(jobs));
         for (int d = 0; d < n_sh; ++d) {

@@ -220,6 +220,11 @@ typedef struct {
     double sum_depth, sum_mq, positions; /* the reference's double accumulators (:283-285) */
 } cli_host_cov_t;
 void cli_host_get_depths(FILE *ft, FILE *fq, cli_host_cov_t *out);
+/* the same from two RUN-LENGTH bedgraphs (`--runs`, an extension): each file read to its end, the checks of cornetto_bgrun_feed() / _finish()
+ * in their order; exits through cli_runs_fail() on malformed input */
+void cli_host_get_depths_runs(FILE *ft, FILE *fq, const char *path_t, const char *path_q, cli_host_cov_t *out);
+/* the one CLI_ERROR line of a failed check of the run-length readers (kinds of cornetto_bgrunerr_t), then exit(EXIT_FAILURE) */
+void cli_runs_fail(const char *path, int kind, long long record, int a, int b);
 void cli_host_cov_free(cli_host_cov_t *c);
 /* get_regs() + the predicate of print_fun_bits (boring = 0) / print_boring_bits (1): the rows to print, malloc memory */
 void cli_host_cov_select(const cli_host_cov_t *c, int w, int inc, int32_t lo, int32_t hi, float low_mq, int32_t edge_len, int32_t min_ctg_len, int boring,

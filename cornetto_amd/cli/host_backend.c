@@ -527,6 +527,133 @@ void cli_host_get_depths(FILE *ft, FILE *fq, cli_host_cov_t *out)
     free(nb.s);
 }
 
+/* ------------------------------------------------------------------------------------------------ get_depths, run-length files
+ * `--runs` (an extension, see boringbits_main.c): a record `name s e v` stands for the per-base records `name p p+1 v`, p = s .. e-1.
+ * The two files are independent streams, each read to its end; the checks and their order are those of the device reader
+ * (csrc/bgrun.hip: rl_check, cornetto_bgrun_finish). */
+void cli_runs_fail(const char *path, int kind, long long record, int a, int b)
+{
+    if (kind == 1 || kind == 2) {
+        CLI_ERROR("%s: record %lld: a run-length depth record has 4 columns (name start end value). Had %d.", path, record, a);
+    } else if (kind == 6) {
+        CLI_ERROR("%s: record %lld: the first run of a contig should start at 0. Found %d", path, record, a);
+    } else if (kind == 7) {
+        CLI_ERROR("%s: record %lld: runs should follow each other without gap or overlap. Found end %d, then start %d "
+                  "(`bedtools genomecov -bg` leaves out the zero-depth runs: use -bga)", path, record, a, b);
+    } else if (kind == 8) {
+        CLI_ERROR("%s: record %lld: a run should have end > start. Found %d to %d", path, record, a, b);
+    } else if (kind == 9) {
+        CLI_ERROR("%s: record %lld: negative depth value %d", path, record, a);
+    } else {
+        CLI_ERROR("%s: contig %lld is not the same in the two depth files (name, or length %d against %d)", path, record, a, b);
+    }
+    exit(EXIT_FAILURE);
+}
+
+/* %d of a WHOLE token, as the device readers convert it (csrc/bgtok.hpp parse_int): optional sign, digits, nothing else */
+static int runs_int(const cli_str_t *t, int *v)
+{
+    size_t p = 0;
+    int neg = 0;
+    if (p < t->l && (t->s[p] == '-' || t->s[p] == '+')) neg = t->s[p++] == '-';
+    if (p >= t->l) return 0;
+    uint32_t x = 0;
+    for (; p < t->l; ++p) {
+        if (t->s[p] < '0' || t->s[p] > '9') return 0;
+        x = x * 10u + (uint32_t)(t->s[p] - '0');
+    }
+    if (neg) x = 0u - x;
+    memcpy(v, &x, sizeof(x));
+    return 1;
+}
+
+typedef struct {
+    int32_t n_ctg, cap_ctg;
+    char **names;
+    int32_t *lens;
+    uint16_t *d;
+    int64_t n_pos, cap_pos, n_clamped;
+    double sum;
+} runs_file_t;
+
+static void runs_read(FILE *fp, const char *path, int file, runs_file_t *o)
+{
+    bgs_t s = {fp, (unsigned char *)cli_xmalloc(1 << 20), 0, 0, 0};
+    cli_str_t name = {0, 0, 0}, tok = {0, 0, 0};
+    memset(o, 0, sizeof(*o));
+    int prev_end = 0;
+    for (long long rec = 0;; ++rec) {
+        int v[3] = {0, 0, 0}, conv = 1;
+        if (!bgs_string(&s, &name)) break;
+        while (conv < 4 && bgs_string(&s, &tok) && runs_int(&tok, &v[conv - 1])) ++conv;
+        if (conv != 4) cli_runs_fail(path, 1 + file, rec, conv, 0);
+        const int st = v[0], end = v[1];
+        int depth = v[2];
+        const int first = o->n_ctg == 0 || strcmp(name.s, o->names[o->n_ctg - 1]) != 0;
+        if (first && st != 0) cli_runs_fail(path, 6, rec, st, 0);
+        if (!first && st != prev_end) cli_runs_fail(path, 7, rec, prev_end, st);
+        if (end <= st) cli_runs_fail(path, 8, rec, st, end);
+        if (depth < 0) cli_runs_fail(path, 9, rec, depth, 0);
+        if (first) {
+            if (o->n_ctg == o->cap_ctg) {
+                o->cap_ctg = o->cap_ctg ? o->cap_ctg * 2 : 256;
+                o->names = (char **)cli_xrealloc(o->names, (size_t)o->cap_ctg * sizeof(char *));
+                o->lens = (int32_t *)cli_xrealloc(o->lens, (size_t)o->cap_ctg * sizeof(int32_t));
+            }
+            o->names[o->n_ctg] = cli_xstrdup(name.s);
+            o->lens[o->n_ctg++] = 0;
+        }
+        const int64_t len = (int64_t)end - st;
+        if (depth > 65535) {
+            depth = 65535;
+            o->n_clamped += len;
+        }
+        if (o->n_pos + len > o->cap_pos) {
+            while (o->n_pos + len > o->cap_pos) o->cap_pos = o->cap_pos ? o->cap_pos * 2 : 1 << 20;
+            o->d = (uint16_t *)cli_xrealloc(o->d, (size_t)o->cap_pos * sizeof(uint16_t));
+        }
+        for (int64_t i = 0; i < len; ++i) o->d[o->n_pos + i] = (uint16_t)depth;
+        o->n_pos += len;
+        o->lens[o->n_ctg - 1] = end;       /* (a contig starts at 0 and has no gaps: its length is its last end) */
+        o->sum += (double)depth * (double)len;
+        prev_end = end;
+    }
+    free(s.buf);
+    free(name.s);
+    free(tok.s);
+}
+
+void cli_host_get_depths_runs(FILE *ft, FILE *fq, const char *path_t, const char *path_q, cli_host_cov_t *out)
+{
+    runs_file_t a, b;
+    runs_read(ft, path_t, 0, &a);
+    runs_read(fq, path_q, 1, &b);
+    const int32_t n = a.n_ctg > b.n_ctg ? a.n_ctg : b.n_ctg;
+    for (int32_t k = 0; k < n; ++k) {
+        const int la = k < a.n_ctg ? a.lens[k] : 0, lb = k < b.n_ctg ? b.lens[k] : 0;
+        if (k >= a.n_ctg || k >= b.n_ctg || la != lb || strcmp(a.names[k], b.names[k]) != 0) cli_runs_fail(path_t, 10, k, la, lb);
+    }
+    memset(out, 0, sizeof(*out));
+    out->n_ctg = a.n_ctg;
+    out->names = a.names;
+    out->lens = a.lens;
+    out->depth = a.d;
+    out->mq = b.d;
+    out->n_pos = a.n_pos;
+    out->n_clamped = a.n_clamped + b.n_clamped;
+    out->sum_depth = a.sum;
+    out->sum_mq = b.sum;
+    out->positions = (double)a.n_pos;
+    if (a.n_ctg) {
+        out->first = (int64_t *)cli_xmalloc(((size_t)a.n_ctg + 1) * sizeof(int64_t));
+        out->first[0] = 0;
+        for (int32_t k = 0; k < a.n_ctg; ++k) out->first[k + 1] = out->first[k] + a.lens[k];
+    }
+    for (int32_t k = 0; k < b.n_ctg; ++k) free(b.names[k]);
+    free(b.names);
+    free(b.lens);
+}
+
 void cli_host_cov_free(cli_host_cov_t *c)
 {
     for (int32_t i = 0; i < c->n_ctg; ++i) free(c->names[i]);

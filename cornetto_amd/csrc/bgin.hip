@@ -3,7 +3,7 @@
 //
 // The reference reads both files with fscanf("%s\t%d\t%d\t%d\n"): a record is FOUR WHITESPACE-SEPARATED TOKENS,
 // whatever the line structure.  That is what is implemented here, on the device, for text resident in HBM:
-//   tk_count / tk_scatter  token starts (non-white byte after a white byte) of a text buffer: per 16-byte lane
+//   tk_count / tk_scatter  (bgtok.hpp, shared with the run-length reader bgrun.hip) token starts (non-white byte after a white byte) of a text buffer: per 16-byte lane
 //                          piece a white-space bit mask, popcount, block scan, device scan of the tile counts,
 //                          then the positions are scattered in order (two streaming reads of the text);
 //   bg_records             one thread per record index r: parses tokens 4r..4r+3 of BOTH files, applies the
@@ -18,133 +18,11 @@
 #include <algorithm>
 #include <string>
 
-#include "common.hpp"
-#include "scan.hpp"
+#include "bgtok.hpp"
 
 namespace {
 
-constexpr int TK_THREADS = 256;
-constexpr int TK_TILE = TK_THREADS * 16;
-
-__device__ __forceinline__ bool is_ws(uint32_t c) { return (c - 9u < 5u) | (c == 32u); }   // isspace() in the C locale
-
-// bit i = byte i of the 16-byte piece at `pos` is white space; bytes at or beyond n count as white space
-__device__ __forceinline__ uint32_t ws_mask16(const uint8_t *text, int64_t pos, int64_t n)
-{
-    uint32_t m = 0;
-    if (pos + 16 <= n) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(text + pos);
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int i = 0; i < 16; ++i) m |= (uint32_t)is_ws((w[i >> 2] >> (8 * (i & 3))) & 0xFFu) << i;
-    } else {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) m |= (uint32_t)(pos + i >= n || is_ws(text[pos + i])) << i;
-    }
-    return m;
-}
-
-__device__ __forceinline__ uint32_t tokstart_mask(const uint8_t *text, int64_t pos, int64_t n)
-{
-    if (pos >= n) return 0;
-    const uint32_t ws = ws_mask16(text, pos, n);
-    const uint32_t prev = pos == 0 ? 1u : (uint32_t)is_ws(text[pos - 1]);
-    return ~ws & ((ws << 1) | prev) & 0xFFFFu;
-}
-
-__global__ __launch_bounds__(TK_THREADS) void tk_count(const uint8_t *text, int64_t n, uint32_t *tile_cnt)
-{
-    __shared__ uint32_t w[TK_THREADS / 64];
-    const int64_t pos = ((int64_t)blockIdx.x * TK_THREADS + threadIdx.x) * 16;
-    uint32_t c = (uint32_t)__popc(tokstart_mask(text, pos, n));
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
-    if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = w[0] + w[1] + w[2] + w[3];
-}
-
-__global__ __launch_bounds__(TK_THREADS) void tk_scatter(const uint8_t *text, int64_t n, const uint32_t *tile_off, uint32_t *tok)
-{
-    __shared__ uint32_t wt[TK_THREADS / 64];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int64_t pos = ((int64_t)blockIdx.x * TK_THREADS + t) * 16;
-    uint32_t m = tokstart_mask(text, pos, n);
-    const uint32_t c = (uint32_t)__popc(m);
-    uint32_t inc = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) wt[wv] = inc;
-    __syncthreads();
-    uint32_t idx = tile_off[blockIdx.x] + inc - c;
-    for (int i = 0; i < wv; ++i) idx += wt[i];
-    while (m) {
-        const int b = __ffs((int)m) - 1;
-        m &= m - 1;
-        tok[idx++] = (uint32_t)(pos + b);
-    }
-}
-
 enum { BG_OK = 0, BG_COLUMNS_A = 1, BG_COLUMNS_B = 2, BG_ORDER = 3, BG_INCREMENTAL = 4, BG_ENDSTART = 5 };
-
-struct BgRec {
-    uint32_t name_off, name_len;
-    int32_t st, end, depth;
-    int32_t nfields;      // converted fields, like the return value of the reference's fscanf
-};
-
-// %d of one token: optional sign, digits up to the next white space; anything else fails the conversion
-__device__ __forceinline__ bool parse_int(const uint8_t *text, int64_t n, uint32_t pos, int32_t *out)
-{
-    int64_t p = pos;
-    bool neg = false;
-    if (p < n && (text[p] == '-' || text[p] == '+')) neg = text[p++] == '-';
-    if (p >= n || text[p] < '0' || text[p] > '9') return false;
-    uint32_t v = 0;
-    while (p < n && text[p] >= '0' && text[p] <= '9') v = v * 10u + (uint32_t)(text[p++] - '0');
-    if (p < n && !is_ws(text[p])) return false;
-    *out = (int32_t)(neg ? 0u - v : v);
-    return true;
-}
-
-__device__ __forceinline__ BgRec parse_rec(const uint8_t *text, int64_t n, const uint32_t *tok, int64_t r)
-{
-    BgRec x;
-    x.name_off = tok[4 * r];
-    uint32_t e = x.name_off;
-    while (e < n && !is_ws(text[e])) ++e;
-    x.name_len = e - x.name_off;
-    x.st = x.end = x.depth = 0;
-    x.nfields = 1;
-    if (parse_int(text, n, tok[4 * r + 1], &x.st)) {
-        x.nfields = 2;
-        if (parse_int(text, n, tok[4 * r + 2], &x.end)) {
-            x.nfields = 3;
-            if (parse_int(text, n, tok[4 * r + 3], &x.depth)) x.nfields = 4;
-        }
-    }
-    return x;
-}
-
-__device__ __forceinline__ bool same_name(const uint8_t *a, uint32_t ao, uint32_t al, const uint8_t *b, uint32_t bo, uint32_t bl)
-{
-    if (al != bl) return false;
-    for (uint32_t i = 0; i < al; ++i)
-        if (a[ao + i] != b[bo + i]) return false;
-    return true;
-}
-
-__device__ __forceinline__ uint32_t name_of(const uint8_t *text, int64_t n, const uint32_t *tok, int64_t r, uint32_t *len)
-{
-    const uint32_t o = tok[4 * r];
-    uint32_t e = o;
-    while (e < n && !is_ws(text[e])) ++e;
-    *len = e - o;
-    return o;
-}
 
 struct BgArgs {
     const uint8_t *ta, *tb;
@@ -245,19 +123,6 @@ __global__ __launch_bounds__(256) void bg_records(BgArgs A)
     }
 }
 
-// contig segments of the flat arrays -> 64-element aligned layout of cornetto_cov_t
-__global__ void bg_layout(const uint16_t *src, const int64_t *src_off, const int64_t *dst_off, const int32_t *len, int32_t n_ctg,
-                          uint16_t *dst)
-{
-    // grid.y is limited to 65535: contigs are taken with a grid stride (read-level coverage sets have more)
-    for (int c = blockIdx.y; c < n_ctg; c += gridDim.y) {
-        const int64_t n = len[c];
-        const uint16_t *s = src + src_off[c];
-        uint16_t *d = dst + dst_off[c];
-        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) d[i] = s[i];
-    }
-}
-
 }  // namespace
 
 struct cornetto_bgin {
@@ -289,34 +154,6 @@ struct cornetto_bgin {
     } pf[2];
     uint64_t pf_seq = 0;
 };
-
-namespace {
-
-int tokenize(cornetto_accel_t *h, const uint8_t *d_text, int64_t n, int slot_tok, int slot_cnt, uint32_t **tok_out, int64_t *ntok)
-{
-    *ntok = 0;
-    *tok_out = nullptr;
-    if (n <= 0) return CORNETTO_OK;
-    const int64_t nt = (n + TK_TILE - 1) / TK_TILE;
-    uint32_t *d_cnt = (uint32_t *)cn_ws(h, slot_cnt, ((size_t)2 * nt + (nt + 4095) / 4096 + 8) * 4 + 16);
-    unsigned long long *p_tot = (unsigned long long *)cn_pin(h, PIN_SMALL, 64);
-    if (!d_cnt || !p_tot) return cn_fail(h, CORNETTO_E_NOMEM, "bedgraph ingest: workspace allocation failed");
-    uint32_t *d_off = d_cnt + nt, *d_part = d_off + nt;
-    unsigned long long *d_tot = reinterpret_cast<unsigned long long *>(((uintptr_t)(d_part + (nt + 4095) / 4096 + 1) + 7) & ~(uintptr_t)7);
-    CN_LAUNCH(h, "tk_count", tk_count<<<dim3((unsigned)nt), dim3(TK_THREADS), 0, h->stream>>>(d_text, n, d_cnt));
-    CN_TRY(cnscan::exclusive_u32(h, "tk_scan", d_cnt, nt, 1, d_off, d_part, d_tot));
-    CN_HIP(h, hipMemcpyAsync(p_tot, d_tot, 8, hipMemcpyDeviceToHost, h->stream));
-    CN_HIP(h, hipStreamSynchronize(h->stream));
-    const int64_t total = (int64_t)p_tot[0];
-    uint32_t *d_tok = (uint32_t *)cn_ws(h, slot_tok, ((size_t)total + 8) * 4);
-    if (!d_tok) return cn_fail(h, CORNETTO_E_NOMEM, "bedgraph ingest: workspace allocation failed");
-    if (total) CN_LAUNCH(h, "tk_scatter", tk_scatter<<<dim3((unsigned)nt), dim3(TK_THREADS), 0, h->stream>>>(d_text, n, d_off, d_tok));
-    *tok_out = d_tok;
-    *ntok = total;
-    return CORNETTO_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -618,52 +455,19 @@ int cornetto_bgin_finish(cornetto_accel_t *h, cornetto_bgin_t *b, cornetto_cov_t
             if (nc) c->ctg_corr[2 * lo + (b->neg[i] & 1ull)] += b->neg[i + 1];
         }
     }
-    std::vector<int64_t> src_off(nc);
-    int64_t pos = 0;
+    std::vector<int64_t> src_off(nc), lens(nc);
     for (int32_t i = 0; i < nc; ++i) {
-        const int64_t s = b->breaks[i].index, e = i + 1 < nc ? b->breaks[i + 1].index : b->n_rec;
-        if (e - s > INT32_MAX) { delete c; return cn_fail(h, CORNETTO_E_UNSUPPORTED, "bgin_finish: contig %d has more than 2^31-1 positions", i); }
-        src_off[i] = s;
-        c->off.push_back(pos);
-        c->len.push_back((int32_t)(e - s));
-        c->total += e - s;
-        pos = cn_align_up(pos + (e - s), 64);
+        src_off[i] = b->breaks[i].index;
+        lens[i] = (i + 1 < nc ? b->breaks[i + 1].index : b->n_rec) - src_off[i];
     }
-    const size_t bytes = (size_t)(pos + 256) * sizeof(uint16_t);
-    size_t ntab = (size_t)(nc > 0 ? nc : 1);
-    int64_t *d_src = nullptr;
-    if (hipMalloc(&c->owned_d, bytes) != hipSuccess || hipMalloc(&c->owned_q, bytes) != hipSuccess ||
-        hipMalloc((void **)&c->d_off, ntab * 8) != hipSuccess || hipMalloc((void **)&c->d_len, ntab * 4) != hipSuccess ||
-        hipMalloc((void **)&d_src, ntab * 8) != hipSuccess) {
-        cornetto_cov_free(h, c);
-        return cn_fail(h, CORNETTO_E_NOMEM, "bgin_finish: device allocation failed");
-    }
-    c->d_depth = (const uint16_t *)c->owned_d;
-    c->d_mq = (const uint16_t *)c->owned_q;
-    hipError_t e = hipMemsetAsync(c->owned_d, 0, bytes, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(c->owned_q, 0, bytes, h->stream);
-    if (nc) {
-        if (e == hipSuccess) e = hipMemcpyAsync(c->d_off, c->off.data(), (size_t)nc * 8, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(c->d_len, c->len.data(), (size_t)nc * 4, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_src, src_off.data(), (size_t)nc * 8, hipMemcpyHostToDevice, h->stream);
-        if (e == hipSuccess) {
-            bg_layout<<<dim3(64, (unsigned)std::min<int32_t>(nc, 32768)), dim3(256), 0, h->stream>>>(b->d_a, d_src, c->d_off, c->d_len, nc, (uint16_t *)c->owned_d);
-            bg_layout<<<dim3(64, (unsigned)std::min<int32_t>(nc, 32768)), dim3(256), 0, h->stream>>>(b->d_b, d_src, c->d_off, c->d_len, nc, (uint16_t *)c->owned_q);
-            e = hipGetLastError();
-        }
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(d_src);
-    if (e != hipSuccess) {
-        cornetto_cov_free(h, c);
-        return cn_fail(h, CORNETTO_E_HIP, "bgin_finish: %s", hipGetErrorString(e));
-    }
+    const int rc = bg_cov_layout(h, "bgin_finish", c, b->d_a, b->d_b, src_off, lens);
+    if (rc != CORNETTO_OK) return rc;
     // the flat arrays are no longer needed
     (void)hipFree(b->d_a);
     (void)hipFree(b->d_b);
     b->d_a = b->d_b = nullptr;
     b->cap = 0;
-    char **nm = (char **)malloc(ntab * sizeof(char *));
+    char **nm = (char **)malloc((size_t)(nc > 0 ? nc : 1) * sizeof(char *));
     if (!nm) { cornetto_cov_free(h, c); return cn_fail(h, CORNETTO_E_NOMEM, "bgin_finish: host allocation failed"); }
     for (int32_t i = 0; i < nc; ++i) {
         nm[i] = (char *)malloc(b->breaks[i].name.size() + 1);

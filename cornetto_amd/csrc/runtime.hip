@@ -552,6 +552,17 @@ int32_t cornetto_cov_n(const cornetto_cov_t *c) { return c ? c->n : 0; }
 
 const int32_t *cornetto_cov_lens(const cornetto_cov_t *c) { return c ? c->len.data() : nullptr; }
 
+int cornetto_cov_download(cornetto_accel_t *h, const cornetto_cov_t *c, int32_t ctg, uint16_t *depth, uint16_t *mq_depth)
+{
+    if (!h || !c || ctg < 0 || ctg >= c->n) return cn_fail(h, CORNETTO_E_ARG, "cov_download: bad argument");
+    CN_HIP(h, hipSetDevice(h->device));
+    const size_t bytes = (size_t)c->len[ctg] * sizeof(uint16_t);
+    if (depth && bytes) CN_HIP(h, hipMemcpyAsync(depth, c->d_depth + c->off[ctg], bytes, hipMemcpyDeviceToHost, h->stream));
+    if (mq_depth && bytes) CN_HIP(h, hipMemcpyAsync(mq_depth, c->d_mq + c->off[ctg], bytes, hipMemcpyDeviceToHost, h->stream));
+    CN_HIP(h, hipStreamSynchronize(h->stream));
+    return CORNETTO_OK;
+}
+
 static int cov_finish_table(cornetto_accel_t *h, cornetto_cov_t *c)
 {
     size_t n = (size_t)(c->n > 0 ? c->n : 1);

@@ -250,17 +250,20 @@ def make_assembly(torch, dev, lens, seed, profile="uniform"):
     return bases, np.array(offs, dtype=np.int64)
 
 
-def make_coverage(torch, dev, lens, offs, seed):
-    """per-base depth / mq-depth (u16 stored as int16 bit patterns) — SURVEY 8d, C3"""
+def make_coverage(torch, dev, lens, offs, seed, profile="noise"):
+    """per-base depth / mq-depth (u16 stored as int16 bit patterns) — SURVEY 8d, C3.  profile "noise" (the bench's): a level per 1000 positions
+    plus noise at every base; "flat": the levels without the noise (runs of 1 kb); "readlike": a level per 300 positions, no noise (depth changes
+    where reads start and end) — the last two for tools/perf_bgruns.py, whose run-length files need runs"""
     g = torch.Generator(device=dev)
     g.manual_seed(seed + 1)
     total = int(offs[-1] + (lens[-1] + 63) // 64 * 64 + 256)
-    nk = (total + 999) // 1000
+    blk = 300 if profile == "readlike" else 1000
+    nk = (total + blk - 1) // blk
     base = torch.poisson(torch.full((nk,), 30.0, device=dev), generator=g).to(torch.int16)
-    depth = base.repeat_interleave(1000)[:total].contiguous()
+    depth = base.repeat_interleave(blk)[:total].contiguous()
     del base
     step = 1 << 28
-    for s in range(0, total, step):
+    for s in range(0, total, step) if profile == "noise" else ():
         e = min(total, s + step)
         depth[s:e] += torch.randint(-2, 3, (e - s,), dtype=torch.int16, device=dev, generator=g)
     depth.clamp_(min=0)

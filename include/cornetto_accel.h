@@ -280,6 +280,10 @@ int cornetto_cov_shard(cornetto_accel_t *h_src, const cornetto_cov_t *src, corne
 int32_t cornetto_cov_n(const cornetto_cov_t *c);
 const int32_t *cornetto_cov_lens(const cornetto_cov_t *c);
 
+/* the two arrays of contig `ctg`, position by position, into caller-provided depth[] and mq_depth[] (cornetto_cov_lens()[ctg] elements
+ * each; either may be NULL) */
+int cornetto_cov_download(cornetto_accel_t *h, const cornetto_cov_t *c, int32_t ctg, uint16_t *depth, uint16_t *mq_depth);
+
 /* number of windows of a contig: src/boringbits_main.c:338-339 */
 int32_t cornetto_n_reg(int32_t length, int32_t window_size, int32_t window_inc);
 
@@ -404,6 +408,47 @@ int cornetto_bgin_done(const cornetto_bgin_t *b);
  * depth values that were clamped to 65535 (the reference prints a WARNING for each, :261-268). */
 int cornetto_bgin_finish(cornetto_accel_t *h, cornetto_bgin_t *b, cornetto_cov_t **cov, int32_t *n_ctg, char ***names,
                          int64_t *n_clamped);
+
+/* ---------------------------------------------------------------------------------------------------
+ * run-length bedgraphs on the device: `(no)boringbits --runs`.  An EXTENSION: the reference reads one line per base only
+ * (src/boringbits_main.c:256-259 refuses anything else); mosdepth and `bedtools genomecov -bga` write one record per run of equal depth.
+ * Defined by expansion: a record `name s e v` stands for the per-base records `name p p+1 v`, p = s .. e-1, and the coverage object is
+ * the one cornetto_bgin_finish() gives for the expanded pair.
+ * ------------------------------------------------------------------------------------------------- */
+
+typedef struct cornetto_bgrun cornetto_bgrun_t; /* streaming state of one pair of run-length bedgraphs */
+
+/* which check failed: within one file the record with the smallest index decides, within a record the order below */
+typedef struct {
+    int32_t kind;   /* 1 / 2: a record of cov-total / cov-mq has fewer than 4 converted fields (a = converted fields): header and `track`
+                              lines, float values, 1-3 tokens left at the end of the file
+                       6: the first run of a contig does not start at 0 (a = start)
+                       7: start != previous end within a contig, a gap or an overlap (a = previous end, b = start)
+                       8: end <= start (a = start, b = end)
+                       9: negative value (a = value)
+                       10: at finish, the files disagree: contig `record` is missing in one of them (its length there: 0) or differs in
+                           name or length (a, b = its length in cov-total, cov-mq) */
+    int32_t file;   /* 0: cov-total, 1: cov-mq */
+    int64_t record; /* 0-based index of the record in its file (kind 10: of the contig) */
+    int32_t a, b;
+} cornetto_bgrunerr_t;
+
+/* positions per workgroup of the expansion kernel (tests plant run and contig seams at its multiples) */
+#define CORNETTO_BGRUN_TILE 4096
+int32_t cornetto_bgrun_tile(void);
+
+int cornetto_bgrun_open(cornetto_accel_t *h, cornetto_bgrun_t **out);
+void cornetto_bgrun_close(cornetto_accel_t *h, cornetto_bgrun_t *b);
+/* The next n bytes of file 0 (cov-total) or 1 (cov-mq), ordinary or pinned memory: any split points (inside a token too), the two files in
+ * any interleaving; final != 0: the last bytes of that file.  A record is four white-space separated tokens and its numbers convert as in
+ * cornetto_bgin_feed().  A record starts a contig iff its name differs from the previous record's in the same file.  Values above 65535
+ * are clamped (every position of the run counts as clamped).  CORNETTO_E_FORMAT: cornetto_bgrun_error(). */
+int cornetto_bgrun_feed(cornetto_accel_t *h, cornetto_bgrun_t *b, int file, const char *text, int64_t n, int final);
+const cornetto_bgrunerr_t *cornetto_bgrun_error(const cornetto_bgrun_t *b);
+/* After the final feed of both files: checks them against each other (kind 10), then as cornetto_bgin_finish() — the same kind of
+ * object, ready for cornetto_cov_prepare(), the same ownership of the names. */
+int cornetto_bgrun_finish(cornetto_accel_t *h, cornetto_bgrun_t *b, cornetto_cov_t **cov, int32_t *n_ctg, char ***names,
+                          int64_t *n_clamped);
 
 /* ---------------------------------------------------------------------------------------------------
  * FASTQ reads: record framing of `cornetto seq` / `cornetto sdust reads.fastq` on the device
