@@ -104,68 +104,34 @@ __global__ void rl_detail(RlArgs A, int64_t r, int32_t *out)
 }
 
 // ---- exclusive scan of 64-bit run lengths: tile-local scan, scan of the tile totals by one workgroup, offset add --------------------------
-__device__ __forceinline__ unsigned long long wave_incl64(unsigned long long v, int lane)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long o = __shfl_up(v, d);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
+// (three launches: a 64-bit value does not fit the packed state of scan.hpp's look-back; the pieces inside a tile are the same)
 constexpr int RS_ITEMS = 8;                         // run lengths per thread of the scan
 constexpr int RS_TILE = RL_THREADS * RS_ITEMS;
+static_assert(RL_THREADS == cnscan::SC_THREADS, "cnscan::tile_excl scans a workgroup of SC_THREADS");
 
-__global__ __launch_bounds__(RL_THREADS) void rl_scan_local(unsigned long long *io, int64_t n, unsigned long long *partial)
+__global__ __launch_bounds__(RL_THREADS) void rl_scan_tile(unsigned long long *io, int64_t n, unsigned long long *partial)
 {
-    __shared__ unsigned long long wtot[RL_THREADS / 64];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int64_t base = (int64_t)blockIdx.x * RS_TILE + (int64_t)t * RS_ITEMS;
-    unsigned long long v[RS_ITEMS], s = 0;
-#pragma unroll
-    for (int k = 0; k < RS_ITEMS; ++k) {
-        v[k] = base + k < n ? io[base + k] : 0ull;
-        s += v[k];
-    }
-    const unsigned long long inc = wave_incl64(s, lane);
-    if (lane == 63) wtot[wv] = inc;
-    __syncthreads();
-    unsigned long long pre = inc - s;
-#pragma unroll
-    for (int w = 0; w < RL_THREADS / 64; ++w)
-        if (w < wv) pre += wtot[w];
-#pragma unroll
-    for (int k = 0; k < RS_ITEMS; ++k) {
-        if (base + k < n) io[base + k] = pre;
-        pre += v[k];
-    }
-    if (t == RL_THREADS - 1) partial[blockIdx.x] = pre;
+    const int64_t base = (int64_t)blockIdx.x * RS_TILE + (int64_t)threadIdx.x * RS_ITEMS;
+    unsigned long long v[RS_ITEMS], total;
+    const unsigned long long pre = cnscan::tile_excl(io, base, n, 1, v, total);
+    cnscan::tile_write(io, base, n, pre, v);
+    if (threadIdx.x == 0) partial[blockIdx.x] = total;
 }
 
-__global__ __launch_bounds__(1024) void rl_scan_partials(unsigned long long *partial, int64_t np, unsigned long long *total)
+__global__ __launch_bounds__(1024) void rl_scan_totals(unsigned long long *partial, int64_t np, unsigned long long *total)
 {
-    __shared__ unsigned long long sh[1024];
     const int t = threadIdx.x;
     const int64_t per = (np + 1023) / 1024;
     const int64_t lo = (int64_t)t * per, hi = lo + per < np ? lo + per : np;
-    unsigned long long s = 0;
+    unsigned long long s = 0, all;
     for (int64_t i = lo; i < hi; ++i) s += partial[i];
-    sh[t] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const unsigned long long o = t >= d ? sh[t - d] : 0ull;
-        __syncthreads();
-        sh[t] += o;
-        __syncthreads();
-    }
-    unsigned long long run = sh[t] - s;
+    unsigned long long run = cnscan::block_excl<unsigned long long, 1024>(s, all);
     for (int64_t i = lo; i < hi; ++i) {
         const unsigned long long x = partial[i];
         partial[i] = run;
         run += x;
     }
-    if (t == 1023) *total = sh[t];
+    if (t == 0) *total = all;
 }
 
 __global__ __launch_bounds__(RL_THREADS) void rl_scan_add(unsigned long long *io, int64_t n, const unsigned long long *partial)
@@ -401,8 +367,8 @@ int cornetto_bgrun_feed(cornetto_accel_t *h, cornetto_bgrun_t *b, int file, cons
             return rl_format_error(h, b, (int)(p_small[0] & 15), file, rec, det[0], det[1]);
         }
         const unsigned long long clamped = p_small[2];
-        CN_LAUNCH(h, "rl_scan", rl_scan_local<<<dim3((unsigned)np), dim3(RL_THREADS), 0, h->stream>>>(d_off, fresh, d_part));
-        CN_LAUNCH(h, "rl_scan", rl_scan_partials<<<dim3(1), dim3(1024), 0, h->stream>>>(d_part, np, d_small + 3));
+        CN_LAUNCH(h, "rl_scan", rl_scan_tile<<<dim3((unsigned)np), dim3(RL_THREADS), 0, h->stream>>>(d_off, fresh, d_part));
+        CN_LAUNCH(h, "rl_scan", rl_scan_totals<<<dim3(1), dim3(1024), 0, h->stream>>>(d_part, np, d_small + 3));
         CN_LAUNCH(h, "rl_scan", rl_scan_add<<<dim3((unsigned)np), dim3(RL_THREADS), 0, h->stream>>>(d_off, fresh, d_part));
         unsigned long long *d_bpos = reinterpret_cast<unsigned long long *>(d_brk + break_cap);
         if (nb) {

@@ -6,12 +6,9 @@
 #include <string>
 
 #include "common.hpp"
-#include "scan.hpp"
+#include "marks.hpp"
 
 namespace {   // internal linkage: every translation unit that includes this gets its own copy
-
-constexpr int TK_THREADS = 256;
-constexpr int TK_TILE = TK_THREADS * 16;
 
 __device__ __forceinline__ bool is_ws(uint32_t c) { return (c - 9u < 5u) | (c == 32u); }   // isspace() in the C locale
 
@@ -37,42 +34,6 @@ __device__ __forceinline__ uint32_t tokstart_mask(const uint8_t *text, int64_t p
     const uint32_t ws = ws_mask16(text, pos, n);
     const uint32_t prev = pos == 0 ? 1u : (uint32_t)is_ws(text[pos - 1]);
     return ~ws & ((ws << 1) | prev) & 0xFFFFu;
-}
-
-__global__ __launch_bounds__(TK_THREADS) void tk_count(const uint8_t *text, int64_t n, uint32_t *tile_cnt)
-{
-    __shared__ uint32_t w[TK_THREADS / 64];
-    const int64_t pos = ((int64_t)blockIdx.x * TK_THREADS + threadIdx.x) * 16;
-    uint32_t c = (uint32_t)__popc(tokstart_mask(text, pos, n));
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
-    if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = w[0] + w[1] + w[2] + w[3];
-}
-
-__global__ __launch_bounds__(TK_THREADS) void tk_scatter(const uint8_t *text, int64_t n, const uint32_t *tile_off, uint32_t *tok)
-{
-    __shared__ uint32_t wt[TK_THREADS / 64];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int64_t pos = ((int64_t)blockIdx.x * TK_THREADS + t) * 16;
-    uint32_t m = tokstart_mask(text, pos, n);
-    const uint32_t c = (uint32_t)__popc(m);
-    uint32_t inc = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) wt[wv] = inc;
-    __syncthreads();
-    uint32_t idx = tile_off[blockIdx.x] + inc - c;
-    for (int i = 0; i < wv; ++i) idx += wt[i];
-    while (m) {
-        const int b = __ffs((int)m) - 1;
-        m &= m - 1;
-        tok[idx++] = (uint32_t)(pos + b);
-    }
 }
 
 // %d of one token: optional sign, digits up to the next white space; anything else fails the conversion
@@ -144,27 +105,16 @@ __global__ void bg_layout(const uint16_t *src, const int64_t *src_off, const int
     }
 }
 
+// the token starts of d_text[0, n), in order
 int tokenize(cornetto_accel_t *h, const uint8_t *d_text, int64_t n, int slot_tok, int slot_cnt, uint32_t **tok_out, int64_t *ntok)
 {
     *ntok = 0;
     *tok_out = nullptr;
     if (n <= 0) return CORNETTO_OK;
-    const int64_t nt = (n + TK_TILE - 1) / TK_TILE;
-    uint32_t *d_cnt = (uint32_t *)cn_ws(h, slot_cnt, ((size_t)2 * nt + (nt + 4095) / 4096 + 8) * 4 + 16);
-    unsigned long long *p_tot = (unsigned long long *)cn_pin(h, PIN_SMALL, 64);
-    if (!d_cnt || !p_tot) return cn_fail(h, CORNETTO_E_NOMEM, "bedgraph ingest: workspace allocation failed");
-    uint32_t *d_off = d_cnt + nt, *d_part = d_off + nt;
-    unsigned long long *d_tot = reinterpret_cast<unsigned long long *>(((uintptr_t)(d_part + (nt + 4095) / 4096 + 1) + 7) & ~(uintptr_t)7);
-    CN_LAUNCH(h, "tk_count", tk_count<<<dim3((unsigned)nt), dim3(TK_THREADS), 0, h->stream>>>(d_text, n, d_cnt));
-    CN_TRY(cnscan::exclusive_u32(h, "tk_scan", d_cnt, nt, 1, d_off, d_part, d_tot));
-    CN_HIP(h, hipMemcpyAsync(p_tot, d_tot, 8, hipMemcpyDeviceToHost, h->stream));
-    CN_HIP(h, hipStreamSynchronize(h->stream));
-    const int64_t total = (int64_t)p_tot[0];
-    uint32_t *d_tok = (uint32_t *)cn_ws(h, slot_tok, ((size_t)total + 8) * 4);
-    if (!d_tok) return cn_fail(h, CORNETTO_E_NOMEM, "bedgraph ingest: workspace allocation failed");
-    if (total) CN_LAUNCH(h, "tk_scatter", tk_scatter<<<dim3((unsigned)nt), dim3(TK_THREADS), 0, h->stream>>>(d_text, n, d_off, d_tok));
-    *tok_out = d_tok;
-    *ntok = total;
+    cnmarks::Marks mk;
+    CN_TRY(cnmarks::count<tokstart_mask>(h, "bedgraph ingest", "tk_count", "tk_scan", d_text, n, slot_cnt, 0, &mk));
+    CN_TRY(cnmarks::scatter<tokstart_mask>(h, "bedgraph ingest", "tk_scatter", d_text, n, mk, slot_tok, (size_t)mk.total, tok_out));
+    *ntok = mk.total;
     return CORNETTO_OK;
 }
 

@@ -49,28 +49,6 @@ struct CbArgs {
     ulonglong2 *tile_tot64;    // exact tile totals
 };
 
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane)
-{
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        uint32_t o = __shfl_up(v, d);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
-// the same scan in six DPP additions (row shifts, then the two row broadcasts)
-__device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t v)
-{
-    int x = (int)v;
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, true);      // row_shr:1
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, true);      // row_shr:2
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, true);      // row_shr:4
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, true);      // row_shr:8
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xA, 0xF, false);     // row_bcast:15 into rows 1 and 3
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, false);     // row_bcast:31 into rows 2 and 3
-    return (uint32_t)x;
-}
 typedef unsigned short cb_us2 __attribute__((ext_vector_type(2)));
 // acc + both halves of a dword of two u16 values: one instruction (v_dot2_u32_u16 with a vector of ones)
 __device__ __forceinline__ uint32_t add_u16x2(uint32_t acc, uint32_t pair)
@@ -235,11 +213,11 @@ __global__ __launch_bounds__(CB_THREADS) void cov_blocks(CbArgs A)
     uint32_t sdv, sqv;
     unsigned long long td = 0, tq = 0;
     if (STAGE) {
-        sdv = wave_incl_scan_dpp(fd);
-        sqv = wave_incl_scan_dpp(fq);
+        sdv = cnwave::wave_incl_dpp(fd);
+        sqv = cnwave::wave_incl_dpp(fq);
     } else {
-        sdv = wave_incl_scan(fd, lane);
-        sqv = wave_incl_scan(fq, lane);
+        sdv = cnwave::wave_incl(fd, lane);
+        sqv = cnwave::wave_incl(fq, lane);
         td = xd;
         tq = xq;
 #pragma unroll
@@ -585,12 +563,11 @@ int cn_cov_prepare_impl(cornetto_accel_t *h, cornetto_cov_t *c, int32_t w, int32
     CN_TRACE("cov_prepare: tables");
     const size_t nt = (size_t)c->n_cb_tiles;
     if (nt == 0) return CORNETTO_OK;
-    uint2 *d_t32 = (uint2 *)cn_ws(h, WS_CB_T32, nt * sizeof(uint2) + ((nt + 4095) / 4096 + 1) * 4 * 2);
+    uint2 *d_t32 = (uint2 *)cn_ws(h, WS_CB_T32, nt * sizeof(uint2));
     ulonglong2 *d_t64 = (ulonglong2 *)cn_ws(h, WS_CB_T64, nt * sizeof(ulonglong2));
     unsigned long long *d_grand = (unsigned long long *)cn_ws(h, WS_CB_GRAND, 16);
     unsigned long long *p_grand = (unsigned long long *)cn_pin(h, PIN_SMALL, 64);
     if (!d_t32 || !d_t64 || !d_grand || !p_grand) return cn_fail(h, CORNETTO_E_NOMEM, "cov_prepare: workspace allocation failed");
-    uint32_t *d_part = reinterpret_cast<uint32_t *>(d_t32 + nt);
     uint2 *d_pre = reinterpret_cast<uint2 *>(c->d_blk), *d_head = d_pre + c->n_blk;
     uint32_t *d_toff_d = reinterpret_cast<uint32_t *>(d_head + c->n_blk), *d_toff_q = d_toff_d + nt;
     CN_TRACE("cov_prepare: workspaces");
@@ -618,7 +595,7 @@ int cn_cov_prepare_impl(cornetto_accel_t *h, cornetto_cov_t *c, int32_t w, int32
     }
     {
         uint32_t *const outs[2] = {d_toff_d, d_toff_q};
-        CN_TRY(cnscan::exclusive_u32_multi(h, "cov_tilescan", reinterpret_cast<const uint32_t *>(d_t32), (int64_t)nt, 2, 2, outs, d_part, nullptr));
+        CN_TRY(cnscan::exclusive_u32_multi(h, "cov_tilescan", reinterpret_cast<const uint32_t *>(d_t32), (int64_t)nt, 2, 2, outs, nullptr));
     }
     const unsigned nb64 = (unsigned)std::min<size_t>(1024, (nt + 255) / 256);
     CN_LAUNCH(h, "cov_total64", cov_total64<<<dim3(nb64), dim3(256), 0, h->stream>>>(d_t64, (int64_t)nt, d_grand));
@@ -703,11 +680,11 @@ static int cov_run_windows(cornetto_accel_t *h, cornetto_cov_t *c, int32_t only_
     const uint2 *d_pre = reinterpret_cast<const uint2 *>(c->d_blk), *d_head = d_pre + c->n_blk;
     const uint32_t *d_toff_d = reinterpret_cast<const uint32_t *>(d_head + c->n_blk), *d_toff_q = d_toff_d + nt_blk;
     unsigned long long *d_cnt = (unsigned long long *)cn_ws(h, WS_CW_CNT, 16);
-    // per tile: {base,count} (8 B) + ordered offset (4 B) + scan partials
-    uint2 *d_tres = (uint2 *)cn_ws(h, WS_CW_TRES, nt * 12 + ((nt + 4095) / 4096 + 1) * 4);
+    // per tile: {base,count} (8 B) + ordered offset (4 B)
+    uint2 *d_tres = (uint2 *)cn_ws(h, WS_CW_TRES, nt * 12);
     unsigned long long *p_cnt = spec ? spec->p_cnt : (unsigned long long *)cn_pin(h, PIN_SMALL, 64);
     if (!d_cnt || !d_tres || !p_cnt) return cn_fail(h, CORNETTO_E_NOMEM, "cov: workspace allocation failed");
-    uint32_t *d_ooff = reinterpret_cast<uint32_t *>(d_tres + nt), *d_part = d_ooff + nt;
+    uint32_t *d_ooff = reinterpret_cast<uint32_t *>(d_tres + nt);
     CwArgs A{};
     A.pre = d_pre; A.head = d_head; A.toff_d = d_toff_d; A.toff_q = d_toff_q; A.blk_off = c->d_blk_off; A.ctg_len = c->d_len; A.n_reg = c->d_n_reg;
     A.tiles = c->d_cw_tiles; A.w = w; A.inc = inc; A.q = q; A.r = r; A.mode = mode; A.lo = lo; A.hi = hi; A.edge = edge;
@@ -754,7 +731,7 @@ static int cov_run_windows(cornetto_accel_t *h, cornetto_cov_t *c, int32_t only_
         A.pk = raw_packed ? reinterpret_cast<cornetto_regpk_t *>(d_raw) : nullptr;
         CN_LAUNCH(h, "cov_windows", cov_windows<<<dim3((unsigned)nt), dim3(256), 0, h->stream>>>(A));
         // tiles are in (contig, window) order: exclusive scan of their counts = final position of each segment; its total = the number selected
-        CN_TRY(cnscan::exclusive_u32(h, "cov_order", reinterpret_cast<const uint32_t *>(d_tres) + 1, (int64_t)nt, 2, d_ooff, d_part, d_cnt));
+        CN_TRY(cnscan::exclusive_u32(h, "cov_order", reinterpret_cast<const uint32_t *>(d_tres) + 1, (int64_t)nt, 2, d_ooff, d_cnt));
         const unsigned nb = (unsigned)((nt + 3) / 4);
         hipEvent_t ea = cn_event(h), eb = cn_event(h);
         (void)hipEventRecord(ea, h->stream);

@@ -4,7 +4,7 @@
 // The reference frames records with klib's kseq, one byte-stream state machine on one core (~0.5 Gbases/s).  ONT /
 // PacBio FASTQ is written as plain four-line records, and for such a record the state machine reduces to local rules
 // on the four lines — so the text is indexed in parallel instead:
-//   fq_nl_count / fq_nl_scatter   newline positions of the piece (16 bytes per thread, ballot-free bit tricks,
+//   nl_mask16 + marks.hpp         newline positions of the piece (16 bytes per thread, ballot-free bit tricks,
 //                                 per-tile counts -> scan -> ordered scatter), ~1 B/byte read, HBM bound
 //   fq_records                    one thread per four lines: the checks under which kseq_read (src/kseq.h:184-224)
 //                                 reads exactly these four lines as one record, the name / comment split of
@@ -17,12 +17,10 @@
 // for record — tests/test_gpu_fastq.py against the oracle's kseq restatement) or the caller is told where it stops
 // being one.
 #include "common.hpp"
-#include "scan.hpp"
+#include "marks.hpp"
 
 namespace {
 
-constexpr int FQ_THREADS = 256;
-constexpr int FQ_TILE = FQ_THREADS * 16;
 
 // bit i = byte i of the 16-byte piece at `pos` is '\n'
 __device__ __forceinline__ uint32_t nl_mask16(const uint8_t *text, int64_t pos, int64_t n)
@@ -42,42 +40,6 @@ __device__ __forceinline__ uint32_t nl_mask16(const uint8_t *text, int64_t pos, 
         for (int i = 0; i < 16; ++i) m |= (uint32_t)(pos + i < n && text[pos + i] == '\n') << i;
     }
     return m;
-}
-
-__global__ __launch_bounds__(FQ_THREADS) void fq_nl_count(const uint8_t *text, int64_t n, uint32_t *tile_cnt)
-{
-    __shared__ uint32_t w[FQ_THREADS / 64];
-    const int64_t pos = ((int64_t)blockIdx.x * FQ_THREADS + threadIdx.x) * 16;
-    uint32_t c = pos < n ? (uint32_t)__popc(nl_mask16(text, pos, n)) : 0u;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
-    if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = w[0] + w[1] + w[2] + w[3];
-}
-
-__global__ __launch_bounds__(FQ_THREADS) void fq_nl_scatter(const uint8_t *text, int64_t n, const uint32_t *tile_off, uint32_t *nl)
-{
-    __shared__ uint32_t wt[FQ_THREADS / 64];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int64_t pos = ((int64_t)blockIdx.x * FQ_THREADS + t) * 16;
-    uint32_t m = pos < n ? nl_mask16(text, pos, n) : 0u;
-    const uint32_t c = (uint32_t)__popc(m);
-    uint32_t inc = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) wt[wv] = inc;
-    __syncthreads();
-    uint32_t idx = tile_off[blockIdx.x] + inc - c;
-    for (int i = 0; i < wv; ++i) idx += wt[i];
-    while (m) {
-        const int b = __ffs((int)m) - 1;
-        m &= m - 1;
-        nl[idx++] = (uint32_t)(pos + b);
-    }
 }
 
 __device__ __forceinline__ bool fq_space(uint8_t c) { return c == ' ' || (c >= '\t' && c <= '\r'); }   // isspace(), C locale
@@ -238,24 +200,12 @@ __global__ __launch_bounds__(256) void fa_linedst(FaLines A, const uint32_t *H, 
 }
 
 // one pass over the text, 16 bytes per thread: the line of the first byte is the number of newlines in front of it
-// (per-tile offsets of the newline index + an in-tile scan, exactly as fq_nl_scatter finds its output slot)
-__global__ __launch_bounds__(FQ_THREADS) void fa_copy(FaLines A, const uint32_t *tile_off, const int64_t *dst, uint8_t *bases)
+// (per-tile offsets of the newline index + the in-tile rank the scatter of the index itself used)
+__global__ __launch_bounds__(cnmarks::MK_THREADS) void fa_copy(FaLines A, const uint32_t *tile_off, const int64_t *dst, uint8_t *bases)
 {
-    __shared__ uint32_t wt[FQ_THREADS / 64];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int64_t pos = ((int64_t)blockIdx.x * FQ_THREADS + t) * 16;
-    uint32_t m = pos < A.n ? nl_mask16(A.text, pos, A.n) : 0u;
-    const uint32_t c = (uint32_t)__popc(m);
-    uint32_t inc = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) wt[wv] = inc;
-    __syncthreads();
-    int64_t k = (int64_t)tile_off[blockIdx.x] + inc - c;
-    for (int i = 0; i < wv; ++i) k += wt[i];
+    const int64_t pos = ((int64_t)blockIdx.x * cnmarks::MK_THREADS + threadIdx.x) * 16;
+    const uint32_t m = pos < A.n ? nl_mask16(A.text, pos, A.n) : 0u;
+    int64_t k = cnmarks::mark_rank(m, tile_off);
     if (pos >= A.n) return;
     int64_t s = fa_line_start(A.nl, k);
     int64_t d = dst[k];
@@ -307,31 +257,25 @@ extern "C" int cornetto_fastq_split(cornetto_accel_t *h, const char *text, int64
     uint8_t *d_text = nullptr;
     cornetto_fqrec_t *d_recs = nullptr;
     if (n > 0) {
-        const int64_t nt = (n + FQ_TILE - 1) / FQ_TILE;
         d_text = (uint8_t *)cn_ws(h, WS_FQ_TEXT, (size_t)n + 64);
-        uint32_t *d_cnt = (uint32_t *)cn_ws(h, WS_FQ_CNT, ((size_t)2 * nt + (nt + 4095) / 4096 + 16) * 4 + 32);
         unsigned long long *p_small = (unsigned long long *)cn_pin(h, PIN_SMALL, 64);
-        if (!d_text || !d_cnt || !p_small) return cn_fail(h, CORNETTO_E_NOMEM, "fastq_split: workspace allocation failed");
-        uint32_t *d_off = d_cnt + nt, *d_part = d_off + nt;
-        unsigned long long *d_tot = reinterpret_cast<unsigned long long *>(((uintptr_t)(d_part + (nt + 4095) / 4096 + 1) + 7) & ~(uintptr_t)7);
-        uint32_t *d_bad = reinterpret_cast<uint32_t *>(d_tot + 1);
+        if (!d_text || !p_small) return cn_fail(h, CORNETTO_E_NOMEM, "fastq_split: workspace allocation failed");
         CN_HIP(h, hipMemcpyAsync(d_text, text, (size_t)n, hipMemcpyHostToDevice, h->stream));
-        CN_LAUNCH(h, "fq_nl_count", fq_nl_count<<<dim3((unsigned)nt), dim3(FQ_THREADS), 0, h->stream>>>(d_text, n, d_cnt));
-        CN_TRY(cnscan::exclusive_u32(h, "fq_scan", d_cnt, nt, 1, d_off, d_part, d_tot));
-        CN_HIP(h, hipMemcpyAsync(p_small, d_tot, 8, hipMemcpyDeviceToHost, h->stream));
-        CN_HIP(h, hipStreamSynchronize(h->stream));
-        const int64_t n_nl = (int64_t)p_small[0];
+        cnmarks::Marks mk;
+        CN_TRY(cnmarks::count<nl_mask16>(h, "fastq_split", "fq_nl_count", "fq_scan", d_text, n, WS_FQ_CNT, 8, &mk));
+        uint32_t *d_bad = reinterpret_cast<uint32_t *>(mk.extra);
+        const int64_t n_nl = mk.total;
         const bool virt = final && text[n - 1] != '\n';
         const int64_t n_lines = n_nl + (virt ? 1 : 0);
         const int64_t n_rec = n_lines / 4;
         if (n_rec > 0x7fffffffLL) return cn_fail(h, CORNETTO_E_ARG, "fastq_split: more than 2^31-1 records in one piece");
         if (n_rec > 0) {
-            uint32_t *d_nl = (uint32_t *)cn_ws(h, WS_FQ_NL, ((size_t)n_nl + 8) * 4);
+            uint32_t *d_nl = nullptr;
             d_recs = (cornetto_fqrec_t *)cn_ws(h, WS_FQ_RECS, (size_t)n_rec * sizeof(cornetto_fqrec_t));
             uint32_t *d_ends = (uint32_t *)cn_ws(h, WS_FQ_ENDS, (size_t)n_rec * 4);
-            if (!d_nl || !d_recs || !d_ends) return cn_fail(h, CORNETTO_E_NOMEM, "fastq_split: workspace allocation failed");
+            if (!d_recs || !d_ends) return cn_fail(h, CORNETTO_E_NOMEM, "fastq_split: workspace allocation failed");
             CN_HIP(h, hipMemsetAsync(d_bad, 0xFF, 4, h->stream));
-            if (n_nl) CN_LAUNCH(h, "fq_nl_scatter", fq_nl_scatter<<<dim3((unsigned)nt), dim3(FQ_THREADS), 0, h->stream>>>(d_text, n, d_off, d_nl));
+            CN_TRY(cnmarks::scatter<nl_mask16>(h, "fastq_split", "fq_nl_scatter", d_text, n, mk, WS_FQ_NL, (size_t)n_nl, &d_nl));
             FqArgs A{d_text, n, d_nl, n_nl, n_rec, min_len, d_recs, d_bad, d_ends};
             CN_LAUNCH(h, "fq_records", fq_records<<<dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, h->stream>>>(A));
             uint32_t *p_bad = reinterpret_cast<uint32_t *>(p_small + 1);
@@ -416,43 +360,38 @@ static int fasta_split_core(cornetto_accel_t *h, const char *text_in, uint8_t *d
     CN_HIP(h, hipSetDevice(h->device));
     cn_timing_begin(h);
     CN_TRACE("fasta_split: enter");
-    const int64_t nt = (n + FQ_TILE - 1) / FQ_TILE;
     uint8_t *d_text = d_text_in ? d_text_in : (uint8_t *)cn_ws(h, WS_FQ_TEXT, (size_t)n + 64);
-    uint32_t *d_cnt = (uint32_t *)cn_ws(h, WS_FQ_CNT, ((size_t)2 * nt + (nt + 4095) / 4096 + 16) * 4 + 64);
     unsigned long long *p_small = (unsigned long long *)cn_pin(h, PIN_SMALL, 64);
-    if (!d_text || !d_cnt || !p_small) return cn_fail(h, CORNETTO_E_NOMEM, "fasta_split: workspace allocation failed");
+    if (!d_text || !p_small) return cn_fail(h, CORNETTO_E_NOMEM, "fasta_split: workspace allocation failed");
     CN_TRACE("fasta_split: text workspace");
-    uint32_t *d_off = d_cnt + nt, *d_part = d_off + nt;
-    unsigned long long *d_tot = reinterpret_cast<unsigned long long *>(((uintptr_t)(d_part + (nt + 4095) / 4096 + 1) + 7) & ~(uintptr_t)7);
-    uint32_t *d_bad = reinterpret_cast<uint32_t *>(d_tot + 3);
     if (text_in) CN_HIP(h, hipMemcpyAsync(d_text, text_in, (size_t)n, hipMemcpyHostToDevice, h->stream));
-    CN_LAUNCH(h, "fq_nl_count", fq_nl_count<<<dim3((unsigned)nt), dim3(FQ_THREADS), 0, h->stream>>>(d_text, n, d_cnt));
-    CN_TRY(cnscan::exclusive_u32(h, "fq_scan", d_cnt, nt, 1, d_off, d_part, d_tot));
-    CN_HIP(h, hipMemcpyAsync(p_small, d_tot, 8, hipMemcpyDeviceToHost, h->stream));
-    CN_HIP(h, hipStreamSynchronize(h->stream));
+    cnmarks::Marks mk;      // behind the counts: the totals of the two line scans, the first line that is not plain
+    CN_TRY(cnmarks::count<nl_mask16>(h, "fasta_split", "fq_nl_count", "fq_scan", d_text, n, WS_FQ_CNT, 24, &mk));
+    unsigned long long *d_tot = reinterpret_cast<unsigned long long *>(mk.extra);
+    uint32_t *d_bad = reinterpret_cast<uint32_t *>(d_tot + 2);
     CN_TRACE("fasta_split: text up, newlines counted");
-    const int64_t n_nl = (int64_t)p_small[0];
+    const int64_t n_nl = mk.total;
     const bool virt = last_ch != '\n';     // the bytes behind the last newline are a line too (complete only if `final`)
     const int64_t n_lines = n_nl + (virt ? 1 : 0);
     // per line: newline offset, header flag, payload, their exclusive scans (n_lines + 1 entries: the last holds the totals),
     // destination; per record: header line
     const size_t nl1 = (size_t)n_lines + 1;
-    uint32_t *d_nl = (uint32_t *)cn_ws(h, WS_FQ_NL, (nl1 + 8) * 4);
-    uint32_t *d_lw = (uint32_t *)cn_ws(h, WS_FQ_ENDS, (5 * nl1 + 2 * ((nl1 + 4095) / 4096 + 2) + 16) * 4);
+    uint32_t *d_nl = nullptr;
+    uint32_t *d_lw = (uint32_t *)cn_ws(h, WS_FQ_ENDS, (5 * nl1 + 16) * 4);
     int64_t *d_dst = seqs ? (int64_t *)cn_ws(h, WS_FQ_SRC, nl1 * 8) : nullptr;   // (fa_linedst's, only when the bases are wanted)
-    if (!d_nl || !d_lw || (seqs && !d_dst)) return cn_fail(h, CORNETTO_E_NOMEM, "fasta_split: workspace allocation failed");
-    uint32_t *d_hdr = d_lw, *d_pay = d_hdr + nl1, *d_H = d_pay + nl1, *d_P = d_H + nl1, *d_hl = d_P + nl1, *d_pp = d_hl + nl1;
+    if (!d_lw || (seqs && !d_dst)) return cn_fail(h, CORNETTO_E_NOMEM, "fasta_split: workspace allocation failed");
+    uint32_t *d_hdr = d_lw, *d_pay = d_hdr + nl1, *d_H = d_pay + nl1, *d_P = d_H + nl1, *d_hl = d_P + nl1;
     CN_HIP(h, hipMemsetAsync(d_bad, 0xFF, 4, h->stream));
-    if (n_nl) CN_LAUNCH(h, "fq_nl_scatter", fq_nl_scatter<<<dim3((unsigned)nt), dim3(FQ_THREADS), 0, h->stream>>>(d_text, n, d_off, d_nl));
+    CN_TRY(cnmarks::scatter<nl_mask16>(h, "fasta_split", "fq_nl_scatter", d_text, n, mk, WS_FQ_NL, nl1, &d_nl));
     FaLines A{d_text, n, d_nl, n_nl, n_lines, d_hdr, d_pay, d_bad};
     const unsigned nbl = (unsigned)((nl1 + 255) / 256);
     CN_LAUNCH(h, "fa_lines", fa_lines<<<dim3(nbl), dim3(256), 0, h->stream>>>(A));
-    CN_TRY(cnscan::exclusive_u32(h, "fa_scan", d_hdr, (int64_t)nl1, 1, d_H, d_pp, d_tot + 1));
-    CN_TRY(cnscan::exclusive_u32(h, "fa_scan", d_pay, (int64_t)nl1, 1, d_P, d_pp, d_tot + 2));
+    CN_TRY(cnscan::exclusive_u32(h, "fa_scan", d_hdr, (int64_t)nl1, 1, d_H, d_tot));
+    CN_TRY(cnscan::exclusive_u32(h, "fa_scan", d_pay, (int64_t)nl1, 1, d_P, d_tot + 1));
     CN_LAUNCH(h, "fa_heads", fa_heads<<<dim3(nbl), dim3(256), 0, h->stream>>>(A, d_H, d_P, d_hl, 0));
     CN_LAUNCH(h, "fa_heads", fa_heads<<<dim3(nbl), dim3(256), 0, h->stream>>>(A, d_H, d_P, d_hl, 1));
     uint32_t *p_u = reinterpret_cast<uint32_t *>(p_small + 4);
-    CN_HIP(h, hipMemcpyAsync(p_small, d_tot + 1, 16, hipMemcpyDeviceToHost, h->stream));
+    CN_HIP(h, hipMemcpyAsync(p_small, d_tot, 16, hipMemcpyDeviceToHost, h->stream));
     CN_HIP(h, hipMemcpyAsync(p_u, d_bad, 4, hipMemcpyDeviceToHost, h->stream));
     CN_HIP(h, hipStreamSynchronize(h->stream));
     CN_TRACE("fasta_split: lines, heads");
@@ -511,7 +450,7 @@ static int fasta_split_core(cornetto_accel_t *h, const char *text_in, uint8_t *d
             fa_linedst<<<dim3(nbl), dim3(256), 0, h->stream>>>(A, d_H, d_P, d_hl, a->d_off, n_use, d_dst);
             (void)hipEventRecord(r1.b, h->stream);
             (void)hipEventRecord(r2.a, h->stream);
-            fa_copy<<<dim3((unsigned)nt), dim3(FQ_THREADS), 0, h->stream>>>(A, d_off, d_dst, (uint8_t *)a->owned);
+            fa_copy<<<dim3((unsigned)mk.nt), dim3(cnmarks::MK_THREADS), 0, h->stream>>>(A, mk.tile_off, d_dst, (uint8_t *)a->owned);
             (void)hipEventRecord(r2.b, h->stream);
             h->recs.push_back(r1);
             h->recs.push_back(r2);

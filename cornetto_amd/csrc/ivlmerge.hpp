@@ -141,7 +141,6 @@ __device__ __forceinline__ unsigned long long st_wave_max(unsigned long long v)
 __global__ __launch_bounds__(ST_THREADS) void st_fused(StArgs A)
 {
     __shared__ unsigned long long wmax[ST_THREADS / 64];
-    __shared__ uint32_t wcnt[ST_THREADS / 64];
     __shared__ unsigned long long s_in;
     __shared__ uint32_t s_tile, s_base;
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
@@ -238,42 +237,11 @@ __global__ __launch_bounds__(ST_THREADS) void st_fused(StArgs A)
             kinc[i] = kp;
         }
     }
-    uint32_t pre = cnscan::wave_incl(hc, lane);
-    if (lane == 63) wcnt[wv] = pre;
-    __syncthreads();
-    pre -= hc;
-    uint32_t tcnt = 0;
-#pragma unroll
-    for (int i = 0; i < ST_THREADS / 64; ++i) {
-        if (i < wv) pre += wcnt[i];
-        tcnt += wcnt[i];
-    }
-    if (wv == 0) {
-        const unsigned long long ctag = (unsigned long long)(A.epoch & 0x3FFFFFFFu) << 32;
-        uint32_t excl = 0;
-        if (tile > 0) {
-            if (lane == 0) __hip_atomic_store(&st[4 * tile + 3], (1ull << 62) | ctag | tcnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            for (int64_t pos = tile - 1;; pos -= 64) {
-                const int64_t idx = pos - lane;
-                unsigned long long c;
-                for (;;) {
-                    c = idx >= 0 ? __hip_atomic_load(&st[4 * idx + 3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ((2ull << 62) | ctag);
-                    const bool ready = (c >> 62) != 0 && (c & (0x3FFFFFFFull << 32)) == ctag;
-                    if (__builtin_amdgcn_ballot_w64(!ready) == 0) break;
-                    __builtin_amdgcn_s_sleep(1);
-                }
-                const unsigned long long incl = __builtin_amdgcn_ballot_w64((c >> 62) == 2);
-                const uint32_t val = (uint32_t)c;
-                if (incl) {
-                    const int first = __builtin_ctzll(incl);
-                    excl += cnscan::wave_sum(lane <= first ? val : 0u);
-                    break;
-                }
-                excl += cnscan::wave_sum(val);
-            }
-        }
+    uint32_t tcnt;
+    const uint32_t pre = cnscan::block_excl<uint32_t, ST_THREADS>(hc, tcnt);
+    if (wv == 0) {                                    // the head count's look-back is the scan's (scan.hpp), its state the fourth word of a tile
+        const uint32_t excl = cnscan::lookback_excl(st + 3, 4, tile, A.epoch, tcnt, lane);
         if (lane == 0) {
-            __hip_atomic_store(&st[4 * tile + 3], (2ull << 62) | ctag | (excl + tcnt), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             s_base = excl;
             if (tile == (n - 1) / ST_TILE && A.d_count) *A.d_count = (unsigned long long)excl + tcnt;
         }
@@ -326,7 +294,7 @@ static inline int merge_fused(cornetto_accel_t *h, const char *name, const corne
 static inline size_t ws_bytes(size_t n)
 {
     const size_t nt = (n + ST_TILE - 1) / ST_TILE;
-    return n * 16 + (nt + 1) * 8 + ((n + 4095) / 4096 + 1) * 4 + 64;
+    return n * 16 + (nt + 1) * 8 + 64;       // kprev [n] u64, tile maxima [nt + 1] u64, head and rank [n] u32 each
 }
 
 // d_in[0..n) -> d_out[0..*d_count): merged list; d_count is a device u64 (also readable after the stream is synchronised)
@@ -336,12 +304,12 @@ static inline int merge(cornetto_accel_t *h, const char *name, const cornetto_iv
     if (n_in <= 0) return CORNETTO_OK;
     const size_t n = (size_t)n_in, nt = (n + ST_TILE - 1) / ST_TILE;
     unsigned long long *d_k = (unsigned long long *)ws, *d_tile = d_k + n;
-    uint32_t *d_head = (uint32_t *)(d_tile + nt + 1), *d_rank = d_head + n, *d_hp = d_rank + n;
+    uint32_t *d_head = (uint32_t *)(d_tile + nt + 1), *d_rank = d_head + n;
     const unsigned nbn = (unsigned)((n + 255) / 256);
     CN_LAUNCH(h, name, st_local<<<dim3((unsigned)nt), dim3(ST_THREADS), 0, h->stream>>>(d_in, n_in, d_k, d_tile));
     CN_LAUNCH(h, name, st_tiles<<<dim3(1), dim3(1024), 0, h->stream>>>(d_tile, (int64_t)nt));
     CN_LAUNCH(h, name, st_heads<<<dim3(nbn), dim3(256), 0, h->stream>>>(d_in, n_in, d_k, d_tile, d_head, dist));
-    CN_TRY(cnscan::exclusive_u32(h, name, d_head, n_in, 1, d_rank, d_hp, d_count));
+    CN_TRY(cnscan::exclusive_u32(h, name, d_head, n_in, 1, d_rank, d_count));
     CN_LAUNCH(h, name, st_emit<<<dim3(nbn), dim3(256), 0, h->stream>>>(d_in, n_in, d_k, d_head, d_rank, d_out));
     return CORNETTO_OK;
 }

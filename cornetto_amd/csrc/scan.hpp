@@ -3,9 +3,11 @@
 // scan of the tile totals, offset add — at a 395 Mb share a step is made of such launches, ~10 us of stream time each): every
 // workgroup scans its 4096 items, publishes its total, and looks back over the states of the tiles in front of it until it meets
 // one whose inclusive prefix is known ("decoupled look-back").  A tile's number is the order in which it STARTED (a ticket), so
-// everything it waits for is already running.  CORNETTO_SCAN=3 asks for the three launches (A/B, tests).
+// everything it waits for is already running.  The pieces (the scan inside a tile, the look-back) are device functions: the 64-bit
+// scan of bgrun.hip and the head count of ivlmerge.hpp's fused merge are built from the same ones.
 #pragma once
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace cnscan {
 namespace {   // internal linkage: every translation unit that includes this gets its own copy
@@ -14,156 +16,102 @@ constexpr int SC_THREADS = 256;
 constexpr int SC_ITEMS = 16;                       // per thread
 constexpr int SC_TILE = SC_THREADS * SC_ITEMS;     // 4096
 
-__device__ __forceinline__ uint32_t wave_incl(uint32_t v, int lane)
+// One value per thread of a workgroup of THREADS -> the sum over the threads in front of it; total = the sum over all of them.
+// (Holds a barrier and the workgroup's wave totals: once per kernel.)
+template <typename T, int THREADS>
+__device__ __forceinline__ T block_excl(T s, T &total)
 {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        uint32_t o = __shfl_up(v, d);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
-// out[i] = sum_{k < i, same tile} in[k * stride]; partial[tile] = tile total
-__global__ __launch_bounds__(SC_THREADS) void scan_local(const uint32_t *in, int64_t n, int stride, uint32_t *out, uint32_t *partial)
-{
-    __shared__ uint32_t wtot[SC_THREADS / 64];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int64_t base = (int64_t)blockIdx.x * SC_TILE + (int64_t)t * SC_ITEMS;
-    uint32_t v[SC_ITEMS], s = 0;
-#pragma unroll
-    for (int k = 0; k < SC_ITEMS; ++k) {
-        const int64_t i = base + k;
-        v[k] = i < n ? in[i * stride] : 0u;
-        s += v[k];
-    }
-    const uint32_t inc = wave_incl(s, lane);
+    __shared__ T wtot[THREADS / 64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const T inc = cnwave::wave_incl(s, lane);
     if (lane == 63) wtot[wv] = inc;
     __syncthreads();
-    uint32_t pre = inc - s;
+    T pre = inc - s;
+    total = 0;
 #pragma unroll
-    for (int w = 0; w < SC_THREADS / 64; ++w)
+    for (int w = 0; w < THREADS / 64; ++w) {
         if (w < wv) pre += wtot[w];
+        total += wtot[w];
+    }
+    return pre;
+}
+
+// The scan inside a tile of SC_THREADS * ITEMS values: v[k] = in[(base + k) * stride] (0 at and beyond n), returns the sum of the tile's
+// values in front of v[0]; total = the tile's sum.
+template <typename T, int ITEMS>
+__device__ __forceinline__ T tile_excl(const T *in, int64_t base, int64_t n, int stride, T (&v)[ITEMS], T &total)
+{
+    T s = 0;
 #pragma unroll
-    for (int k = 0; k < SC_ITEMS; ++k) {
+    for (int k = 0; k < ITEMS; ++k) {
+        const int64_t i = base + k;
+        v[k] = i < n ? in[i * stride] : (T)0;
+        s += v[k];
+    }
+    return block_excl<T, SC_THREADS>(s, total);
+}
+
+// out[base + k] = pre + v[0] + ... + v[k - 1]
+template <typename T, int ITEMS>
+__device__ __forceinline__ void tile_write(T *out, int64_t base, int64_t n, T pre, const T (&v)[ITEMS])
+{
+#pragma unroll
+    for (int k = 0; k < ITEMS; ++k) {
         const int64_t i = base + k;
         if (i < n) out[i] = pre;
         pre += v[k];
     }
-    if (t == SC_THREADS - 1) partial[blockIdx.x] = pre;
 }
 
-// exclusive scan of up to 1024 * per partials by one workgroup, in place; total -> *total
-__global__ __launch_bounds__(1024) void scan_partials(uint32_t *partial, int64_t np, unsigned long long *total)
+// ---- decoupled look-back ------------------------------------------------------------------------------------------------------
+// state of a tile: [63:62] 1 = the tile's own total, 2 = the inclusive prefix up to and including it; [61:32] the epoch of the call
+// that wrote it; [31:0] the value.  The state of tile t lives at st[t * stride].  States are never cleared: a word of another epoch
+// is "not written yet".
+//
+// Called by the first wave of tile `tile` with the tile's own total: returns the sum of the totals of the tiles in front of it.
+// Publish the own total, poll 64 predecessors per round, stop at the nearest one whose inclusive prefix is known, publish the
+// inclusive prefix.  Why the wait ends, and what therefore stays as it is:
+//   - `tile` is a TICKET, the order in which the workgroups started: every tile polled here is running already, whatever order the
+//     hardware hands out block indices in;
+//   - the own total is published BEFORE the wait and the inclusive prefix after it: a running tile owes its total to nobody (tile 0
+//     waits for nobody), so every poll meets at least totals, and the prefix of the nearest finished tile cuts the walk short;
+//   - the polls are relaxed atomic loads at agent scope: issued again in every round (nothing the compiler may keep in a register)
+//     and served where the stores of the other compute units arrive; the value travels in the state word itself, so no fence;
+//   - s_sleep(1) between two polls leaves the issue slots to the waves that still have their totals to compute.
+__device__ __forceinline__ uint32_t lookback_excl(unsigned long long *st, int64_t stride, int64_t tile, uint32_t epoch, uint32_t own, int lane)
 {
-    __shared__ uint32_t sh[1024];
-    const int t = threadIdx.x;
-    const int64_t per = (np + 1023) / 1024;
-    const int64_t lo = (int64_t)t * per, hi = lo + per < np ? lo + per : np;
-    uint32_t s = 0;
-    for (int64_t i = lo; i < hi; ++i) s += partial[i];
-    sh[t] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const uint32_t o = t >= d ? sh[t - d] : 0u;
-        __syncthreads();
-        sh[t] += o;
-        __syncthreads();
+    const unsigned long long tag = (unsigned long long)(epoch & 0x3FFFFFFFu) << 32;
+    uint32_t excl = 0;
+    if (tile > 0) {
+        if (lane == 0) __hip_atomic_store(&st[tile * stride], (1ull << 62) | tag | own, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int64_t pos = tile - 1;; pos -= 64) {
+            const int64_t idx = pos - lane;
+            unsigned long long x;
+            for (;;) {
+                x = idx >= 0 ? __hip_atomic_load(&st[idx * stride], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ((2ull << 62) | tag);
+                const bool ready = (x >> 62) != 0 && (x & (0x3FFFFFFFull << 32)) == tag;
+                if (__builtin_amdgcn_ballot_w64(!ready) == 0) break;
+                __builtin_amdgcn_s_sleep(1);
+            }
+            const unsigned long long incl = __builtin_amdgcn_ballot_w64((x >> 62) == 2);
+            const uint32_t val = (uint32_t)x;
+            if (incl) {
+                const int first = __builtin_ctzll(incl);          // the nearest tile whose prefix is complete
+                excl += cnwave::wave_sum(lane <= first ? val : 0u);
+                break;
+            }
+            excl += cnwave::wave_sum(val);
+        }
     }
-    uint32_t run = sh[t] - s;
-    for (int64_t i = lo; i < hi; ++i) {
-        const uint32_t x = partial[i];
-        partial[i] = run;
-        run += x;
-    }
-    if (t == 1023 && total) *total = sh[t];
+    if (lane == 0) __hip_atomic_store(&st[tile * stride], (2ull << 62) | tag | (excl + own), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return excl;
 }
 
-__global__ __launch_bounds__(SC_THREADS) void scan_add(uint32_t *out, int64_t n, const uint32_t *partial)
-{
-    const uint32_t add = partial[blockIdx.x];
-    const int64_t base = (int64_t)blockIdx.x * SC_TILE;
-    for (int k = threadIdx.x; k < SC_TILE; k += SC_THREADS) {
-        const int64_t i = base + k;
-        if (i < n) out[i] += add;
-    }
-}
-
-// The same for up to four counters that sit side by side in one record (in[i * stride + q], q < m): blockIdx.y = q, three launches for all
-// of them instead of three each (a 395 Mb share is made of launches: 12 -> 3 in front of telofind's gather).
+// Up to four counters that sit side by side in one record (in[i * stride + q], q < m) are scanned by one launch (a 395 Mb share is made
+// of launches: 12 -> 3 -> 1 in front of telofind's gather): tile t of counter q draws the ticket q * np + t.
 struct Outs4 {
     uint32_t *o[4];
 };
-__global__ __launch_bounds__(SC_THREADS) void scan_local_m(const uint32_t *in, int64_t n, int stride, Outs4 outs, uint32_t *partial, int64_t np)
-{
-    __shared__ uint32_t wtot[SC_THREADS / 64];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6, q = blockIdx.y;
-    const int64_t base = (int64_t)blockIdx.x * SC_TILE + (int64_t)t * SC_ITEMS;
-    uint32_t *const out = outs.o[q];
-    uint32_t v[SC_ITEMS], s = 0;
-#pragma unroll
-    for (int k = 0; k < SC_ITEMS; ++k) {
-        const int64_t i = base + k;
-        v[k] = i < n ? in[i * stride + q] : 0u;
-        s += v[k];
-    }
-    const uint32_t inc = wave_incl(s, lane);
-    if (lane == 63) wtot[wv] = inc;
-    __syncthreads();
-    uint32_t pre = inc - s;
-#pragma unroll
-    for (int w = 0; w < SC_THREADS / 64; ++w)
-        if (w < wv) pre += wtot[w];
-#pragma unroll
-    for (int k = 0; k < SC_ITEMS; ++k) {
-        const int64_t i = base + k;
-        if (i < n) out[i] = pre;
-        pre += v[k];
-    }
-    if (t == SC_THREADS - 1) partial[(int64_t)q * np + blockIdx.x] = pre;
-}
-
-__global__ __launch_bounds__(1024) void scan_partials_m(uint32_t *partial_all, int64_t np, unsigned long long *total)
-{
-    __shared__ uint32_t sh[1024];
-    const int t = threadIdx.x, q = blockIdx.x;
-    uint32_t *const partial = partial_all + (int64_t)q * np;
-    const int64_t per = (np + 1023) / 1024;
-    const int64_t lo = (int64_t)t * per, hi = lo + per < np ? lo + per : np;
-    uint32_t s = 0;
-    for (int64_t i = lo; i < hi; ++i) s += partial[i];
-    sh[t] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const uint32_t o = t >= d ? sh[t - d] : 0u;
-        __syncthreads();
-        sh[t] += o;
-        __syncthreads();
-    }
-    uint32_t run = sh[t] - s;
-    for (int64_t i = lo; i < hi; ++i) {
-        const uint32_t x = partial[i];
-        partial[i] = run;
-        run += x;
-    }
-    if (t == 1023 && total) total[q] = sh[t];
-}
-
-__global__ __launch_bounds__(SC_THREADS) void scan_add_m(Outs4 outs, int64_t n, const uint32_t *partial, int64_t np)
-{
-    const int q = blockIdx.y;
-    uint32_t *const out = outs.o[q];
-    const uint32_t add = partial[(int64_t)q * np + blockIdx.x];
-    const int64_t base = (int64_t)blockIdx.x * SC_TILE;
-    for (int k = threadIdx.x; k < SC_TILE; k += SC_THREADS) {
-        const int64_t i = base + k;
-        if (i < n) out[i] += add;
-    }
-}
-
-// ---- single pass -------------------------------------------------------------------------------------------------------------
-// state of tile t of counter q: [63:62] 1 = the tile's own total, 2 = the inclusive prefix up to and including it; [61:32] the epoch
-// of the call that wrote it; [31:0] the value
 struct LbArgs {
     const uint32_t *in;
     int64_t n, np;
@@ -175,16 +123,8 @@ struct LbArgs {
     unsigned long long *total;     // [m] or null
 };
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
 __global__ __launch_bounds__(SC_THREADS) void scan_lookback(LbArgs A)
 {
-    __shared__ uint32_t wtot[SC_THREADS / 64];
     __shared__ uint32_t s_gid, s_excl;
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     if (t == 0) s_gid = atomicAdd(A.ticket, 1u) - A.ticket_base;
@@ -194,73 +134,28 @@ __global__ __launch_bounds__(SC_THREADS) void scan_lookback(LbArgs A)
     const int q = (int)(gid / A.np);
     const int64_t tile = gid - (int64_t)q * A.np;
     const int64_t base = tile * SC_TILE + (int64_t)t * SC_ITEMS;
-    uint32_t *const out = A.outs.o[q];
-    uint32_t v[SC_ITEMS], s = 0;
-#pragma unroll
-    for (int k = 0; k < SC_ITEMS; ++k) {
-        const int64_t i = base + k;
-        v[k] = i < A.n ? A.in[i * A.stride + q] : 0u;
-        s += v[k];
-    }
-    const uint32_t inc = wave_incl(s, lane);
-    if (lane == 63) wtot[wv] = inc;
-    __syncthreads();
-    uint32_t pre = inc - s, bt = 0;
-#pragma unroll
-    for (int w = 0; w < SC_THREADS / 64; ++w) {
-        if (w < wv) pre += wtot[w];
-        bt += wtot[w];
-    }
+    uint32_t v[SC_ITEMS], bt;
+    uint32_t pre = tile_excl(A.in + q, base, A.n, A.stride, v, bt);
     if (wv == 0) {
-        unsigned long long *const st = A.state + (int64_t)q * A.np;
-        const unsigned long long tag = (unsigned long long)(A.epoch & 0x3FFFFFFFu) << 32;
-        uint32_t excl = 0;
-        if (tile > 0) {
-            if (lane == 0) __hip_atomic_store(&st[tile], (1ull << 62) | tag | bt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            for (int64_t pos = tile - 1;; pos -= 64) {
-                const int64_t idx = pos - lane;
-                unsigned long long x;
-                for (;;) {
-                    x = idx >= 0 ? __hip_atomic_load(&st[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ((2ull << 62) | tag);
-                    const bool ready = (x >> 62) != 0 && (x & (0x3FFFFFFFull << 32)) == tag;
-                    if (__builtin_amdgcn_ballot_w64(!ready) == 0) break;
-                    __builtin_amdgcn_s_sleep(1);
-                }
-                const unsigned long long incl = __builtin_amdgcn_ballot_w64((x >> 62) == 2);
-                uint32_t val = (uint32_t)x;
-                if (incl) {
-                    const int first = __builtin_ctzll(incl);          // the nearest tile whose prefix is complete
-                    excl += wave_sum(lane <= first ? val : 0u);
-                    break;
-                }
-                excl += wave_sum(val);
-            }
-        }
+        const uint32_t excl = lookback_excl(A.state + (int64_t)q * A.np, 1, tile, A.epoch, bt, lane);
         if (lane == 0) {
-            __hip_atomic_store(&st[tile], (2ull << 62) | tag | (excl + bt), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             s_excl = excl;
             if (A.total && tile == A.np - 1) A.total[q] = (unsigned long long)excl + bt;
         }
     }
     __syncthreads();
     pre += s_excl;
-#pragma unroll
-    for (int k = 0; k < SC_ITEMS; ++k) {
-        const int64_t i = base + k;
-        if (i < A.n) out[i] = pre;
-        pre += v[k];
-    }
+    tile_write(A.outs.o[q], base, A.n, pre, v);
 }
 
-static inline int scan_mode()
+// outs[q][i] = exclusive prefix of in[i * stride + q] for q < m (<= 4); d_total (optional): m grand totals (u64 each).
+static inline int exclusive_u32_multi(cornetto_accel_t *h, const char *name, const uint32_t *in, int64_t n, int stride, int m, uint32_t *const *outs,
+                                      unsigned long long *d_total)
 {
-    static const int mode = CN_DEV_INT("CORNETTO_SCAN", 1);
-    return mode;
-}
-
-static inline int lookback_launch(cornetto_accel_t *h, const char *name, const uint32_t *in, int64_t n, int stride, int m, const Outs4 &o,
-                                  unsigned long long *d_total)
-{
+    if (n <= 0 || m <= 0) return CORNETTO_OK;
+    if (m > 4) m = 4;
+    Outs4 o{};
+    for (int q = 0; q < m; ++q) o.o[q] = outs[q];
     const int64_t np = (n + SC_TILE - 1) / SC_TILE;
     const size_t need = 64 + (size_t)m * (size_t)np * 8;
     const bool fresh = h->dev[WS_SCAN].bytes < need;
@@ -284,38 +179,10 @@ static inline int lookback_launch(cornetto_accel_t *h, const char *name, const u
     return rc;
 }
 
-// outs[q][i] = exclusive prefix of in[i * stride + q] for q < m (<= 4); d_total (optional): m grand totals (u64 each).
-// `partial` must hold m * ceil(n / 4096) u32.
-static inline int exclusive_u32_multi(cornetto_accel_t *h, const char *name, const uint32_t *in, int64_t n, int stride, int m, uint32_t *const *outs,
-                                      uint32_t *partial, unsigned long long *d_total)
-{
-    if (n <= 0 || m <= 0) return CORNETTO_OK;
-    const int64_t np = (n + SC_TILE - 1) / SC_TILE;
-    Outs4 o{};
-    for (int q = 0; q < m && q < 4; ++q) o.o[q] = outs[q];
-    if (scan_mode() != 3) return lookback_launch(h, name, in, n, stride, m < 4 ? m : 4, o, d_total);
-    CN_LAUNCH(h, name, scan_local_m<<<dim3((unsigned)np, (unsigned)m), dim3(SC_THREADS), 0, h->stream>>>(in, n, stride, o, partial, np));
-    CN_LAUNCH(h, name, scan_partials_m<<<dim3((unsigned)m), dim3(1024), 0, h->stream>>>(partial, np, d_total));
-    CN_LAUNCH(h, name, scan_add_m<<<dim3((unsigned)np, (unsigned)m), dim3(SC_THREADS), 0, h->stream>>>(o, n, partial, np));
-    return CORNETTO_OK;
-}
-
 // out[i] (u32) = exclusive prefix of in[i*stride]; d_total (optional, device u64) = grand total.
-// `partial` must hold ceil(n / 4096) u32.
-static inline int exclusive_u32(cornetto_accel_t *h, const char *name, const uint32_t *in, int64_t n, int stride, uint32_t *out,
-                                uint32_t *partial, unsigned long long *d_total)
+static inline int exclusive_u32(cornetto_accel_t *h, const char *name, const uint32_t *in, int64_t n, int stride, uint32_t *out, unsigned long long *d_total)
 {
-    if (n <= 0) return CORNETTO_OK;
-    if (scan_mode() != 3) {
-        Outs4 o{};
-        o.o[0] = out;
-        return lookback_launch(h, name, in, n, stride, 1, o, d_total);
-    }
-    const int64_t np = (n + SC_TILE - 1) / SC_TILE;
-    CN_LAUNCH(h, name, scan_local<<<dim3((unsigned)np), dim3(SC_THREADS), 0, h->stream>>>(in, n, stride, out, partial));
-    CN_LAUNCH(h, name, scan_partials<<<dim3(1), dim3(1024), 0, h->stream>>>(partial, np, d_total));
-    CN_LAUNCH(h, name, scan_add<<<dim3((unsigned)np), dim3(SC_THREADS), 0, h->stream>>>(out, n, partial));
-    return CORNETTO_OK;
+    return exclusive_u32_multi(h, name, in, n, stride, 1, &out, d_total);
 }
 
 }  // namespace

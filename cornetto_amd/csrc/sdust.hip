@@ -1864,12 +1864,12 @@ int sdust_asm_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, int32_t T, i
     stamp("chunk table");
     if (nc > 0) {
         const SdChunk *d_chunks = reinterpret_cast<const SdChunk *>(a->d_sd_chunks);
-        // per chunk: count (4 B) + ordered offset (4 B) + scan partials; then {total u64, ovf u32}
-        uint32_t *d_cnt = (uint32_t *)cn_ws(h, WS_SD_CNT, nc * 8 + ((nc + 4095) / 4096 + 1) * 4);
+        // per chunk: count (4 B) + ordered offset (4 B)
+        uint32_t *d_cnt = (uint32_t *)cn_ws(h, WS_SD_CNT, nc * 8 + 4);
         unsigned long long *d_tot = (unsigned long long *)cn_ws(h, WS_SD_STATS, 2048 + 64 * 64);   // (+ the chunk counters of sd_sift)   // [0] total [1] overflow | table request [2..6] stats [7] flagged [8] queue
         unsigned long long *p_tot = (unsigned long long *)cn_pin(h, PIN_SMALL, 2048);
         if (!d_cnt || !d_tot || !p_tot) return cn_fail(h, CORNETTO_E_NOMEM, "sdust: workspace allocation failed");
-        uint32_t *d_off = d_cnt + nc, *d_part = d_off + nc;
+        uint32_t *d_off = d_cnt + nc;
         stamp("small workspaces");
         const bool env_stats = CN_DEV_INT("CORNETTO_SDUST_STATS", 0) != 0;
         const bool want_stats = env_stats || h->sd_stats != 0;
@@ -1914,16 +1914,16 @@ int sdust_asm_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, int32_t T, i
                 int lmin = 1;
                 while (5 * (lmin + 1) <= T && lmin < 16) ++lmin;
                 // the chunks that are walked base by base, kept with the assembly's chunk table (see SiftArgs):
-                // [0] count [1] pad | list [nc] | flags [nc] | rank [nc] | order [nc] | scan partials
+                // [0] count [1] pad | list [nc] | flags [nc] | rank [nc] | order [nc]
                 const bool walk_known = a->d_sd_walk && a->sd_walk_key == key;
-                const size_t walk_words = 2 + 4 * nc + ((nc + 4095) / 4096 + 2);
+                const size_t walk_words = 2 + 4 * nc + 2;
                 if (!walk_known) {
                     if (a->d_sd_walk) { (void)hipFree(a->d_sd_walk); a->d_sd_walk = nullptr; }
                     a->sd_walk_key = -1;
                     if (cn_obj_malloc(h, (void **)&a->d_sd_walk, walk_words * 4) != hipSuccess) return cn_fail(h, CORNETTO_E_NOMEM, "sdust: device allocation failed");
                     CN_HIP(h, hipMemsetAsync(a->d_sd_walk, 0, (2 + 2 * nc) * 4, h->stream));
                 }
-                uint32_t *d_wflag = a->d_sd_walk + 2 + nc, *d_wrank = d_wflag + nc, *d_worder = d_wrank + nc, *d_wpart = d_worder + nc;
+                uint32_t *d_wflag = a->d_sd_walk + 2 + nc, *d_wrank = d_wflag + nc, *d_worder = d_wrank + nc;
                 SiftArgs S{a->d_bases, a->d_off, a->d_len, d_chunks, (int32_t)nc, T, W, lds_wave, reg_cap,
                            walk_known ? d_worder : nullptr, walk_known ? nullptr : a->d_sd_walk, walk_known ? nullptr : d_wflag,
                            reinterpret_cast<uint32_t *>(d_tot + 256), T / 10 + 1, lmin, CN_DEV_INT("CORNETTO_SIFT_ABL", 0),
@@ -2000,15 +2000,15 @@ int sdust_asm_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, int32_t T, i
                     stamp(helped ? "kernel done (helped)" : "kernel done (polled)");
                 }
                 if (sift_walk_pending) {
-                    CN_TRY(cnscan::exclusive_u32(h, "sdust_order", d_wflag, (int64_t)nc, 1, d_wrank, d_wpart, nullptr));
+                    CN_TRY(cnscan::exclusive_u32(h, "sdust_order", d_wflag, (int64_t)nc, 1, d_wrank, nullptr));
                     CN_LAUNCH(h, "sdust_order", sd_make_order<<<dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, h->stream>>>(a->d_sd_walk, d_wflag, d_wrank, (int32_t)nc, d_worder));
                 }
             } else if (use_w64) {
                 // warm-up starts, the order of the queue, the claim flags:
-                // flag (nc) + rank (nc) + claim (nc) + perm (nc + 80) + dense list (nc) + scan partials
-                uint32_t *d_flag = (uint32_t *)cn_ws(h, WS_SD_PERM, (nc * 5 + 160) * 4 + ((nc + 4095) / 4096 + 1) * 4);
+                // flag (nc) + rank (nc) + claim (nc) + perm (nc + 80) + dense list (nc)
+                uint32_t *d_flag = (uint32_t *)cn_ws(h, WS_SD_PERM, (nc * 5 + 160) * 4 + 4);
                 if (!d_flag) return cn_fail(h, CORNETTO_E_NOMEM, "sdust: workspace allocation failed");
-                uint32_t *d_rank = d_flag + nc, *d_claim = d_rank + nc, *d_perm = d_claim + nc, *d_list = d_perm + nc + 160, *d_pp = d_list + nc;
+                uint32_t *d_rank = d_flag + nc, *d_claim = d_rank + nc, *d_perm = d_claim + nc, *d_list = d_perm + nc + 160;
                 const unsigned nbs = (unsigned)((nc + 255) / 256);
                 A.claim = d_claim;
                 A.q_len = (int32_t)nc;
@@ -2044,7 +2044,7 @@ int sdust_asm_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, int32_t T, i
                             std::sort(key2.begin(), key2.end());
                             for (uint32_t t = 0; t < ps.P; ++t) ps.turn[key2[t].second] = (uint8_t)t;
                         }
-                        CN_TRY(cnscan::exclusive_u32(h, "sdust_prep", d_flag, (int64_t)nc, 1, d_rank, d_pp, d_tot + 7));
+                        CN_TRY(cnscan::exclusive_u32(h, "sdust_prep", d_flag, (int64_t)nc, 1, d_rank, d_tot + 7));
                         // The number of flagged chunks comes back to the host: it decides whether the dense kernel is worth its
                         // latency (one job = one chunk = several milliseconds for a wave)
                         CN_HIP(h, hipMemcpyAsync(p_tot + 200, d_tot + 7, 8, hipMemcpyDeviceToHost, h->stream));
@@ -2135,7 +2135,7 @@ int sdust_asm_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, int32_t T, i
                 dense_pending = false;                 // (joined on the device: the stream's later work waits for it)
             }
             // ordered position of every chunk's intervals (chunks are in contig order) + grand total
-            CN_TRY(cnscan::exclusive_u32(h, "sdust_scan", d_cnt, (int64_t)nc, 1, d_off, d_part, d_tot));
+            CN_TRY(cnscan::exclusive_u32(h, "sdust_scan", d_cnt, (int64_t)nc, 1, d_off, d_tot));
             // ---- the rest of the call in one go when the last call for this table left its counts behind (round 4): gather, merge (one
             // launch that reads the number of rows from the device) and the result copy are sized by them, ONE synchronisation, and
             // the counts are checked afterwards — anything that does not fit takes the steps below as before
@@ -2205,17 +2205,16 @@ int sdust_asm_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, int32_t T, i
                 std::vector<int64_t> base(a->n + 1, 0);
                 for (int32_t c = 0; c < a->n; ++c) base[c + 1] = base[c] + a->len[c] / SD_WBLK + 2;
                 a->n_wblocks = base[a->n];
-                const size_t npart = ((size_t)a->n_wblocks + 4095) / 4096 + 1;
                 uint32_t *d_wcnt = nullptr;
                 if (hipMalloc((void **)&a->d_wtab, ((size_t)a->n_wblocks + 1) * 4) != hipSuccess ||
                     hipMalloc((void **)&a->d_wtab_base, ((size_t)a->n + 1) * 8) != hipSuccess ||
-                    hipMalloc((void **)&d_wcnt, ((size_t)a->n_wblocks + npart + 1) * 4) != hipSuccess)
+                    hipMalloc((void **)&d_wcnt, ((size_t)a->n_wblocks + 1) * 4) != hipSuccess)
                     return cn_fail(h, CORNETTO_E_NOMEM, "sdust: word-count table allocation failed");
                 CN_HIP(h, hipMemcpyAsync(a->d_wtab_base, base.data(), ((size_t)a->n + 1) * 8, hipMemcpyHostToDevice, h->stream));
                 const unsigned nbw = (unsigned)((a->n_wblocks + 255) / 256);
                 CN_LAUNCH(h, "sd_wordcount", sd_wordcount<<<dim3(nbw), dim3(256), 0, h->stream>>>(a->d_bases, a->d_off, a->d_len, a->d_wtab_base, a->n,
                                                                                          a->n_wblocks, d_wcnt));
-                int rc = cnscan::exclusive_u32(h, "sd_wordscan", d_wcnt, a->n_wblocks, 1, a->d_wtab, d_wcnt + a->n_wblocks, nullptr);
+                int rc = cnscan::exclusive_u32(h, "sd_wordscan", d_wcnt, a->n_wblocks, 1, a->d_wtab, nullptr);
                 hipError_t e = hipStreamSynchronize(h->stream);   // `base` is a local
                 (void)hipFree(d_wcnt);
                 if (rc != CORNETTO_OK) return rc;

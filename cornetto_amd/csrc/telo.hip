@@ -78,19 +78,6 @@ __device__ __forceinline__ unsigned long long smear(unsigned long long cur, unsi
     return hi;
 }
 
-// inclusive scan over the wave in six DPP additions (row shifts, then the two row broadcasts)
-__device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t v)
-{
-    int x = (int)v;
-    x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x114, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x118, 0xF, 0xF, true);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xA, 0xF, false);
-    x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, false);
-    return (uint32_t)x;
-}
-
 // TF_NT consecutive tiles per workgroup (round 5).  One tile per workgroup loaded its 80 bytes per thread, waited for them, then computed: beside
 // the resident sdust waves only two such waves fit on a SIMD (their registers), and with all of a wave's loads ahead of all of its work the
 // scan was bound by the round trips — 1.6 ms in the bench step against 0.71 alone.  Now the 16 bytes a thread has just used up are re-loaded
@@ -275,7 +262,7 @@ __global__ __launch_bounds__(TF_THREADS) void tf_scan(TfArgs A)
                             ((unsigned long long)__popcll(q2) << 32) | ((unsigned long long)__popcll(q3) << 48);
     // (two 16-bit counters per half, each below 2^15 for a whole tile: the halves scan independently, no carry between them)
     const int lane = t & 63, wv = t >> 6;
-    const unsigned long long inc = (unsigned long long)wave_incl_scan_dpp((uint32_t)pk) | ((unsigned long long)wave_incl_scan_dpp((uint32_t)(pk >> 32)) << 32);
+    const unsigned long long inc = (unsigned long long)cnwave::wave_incl_dpp((uint32_t)pk) | ((unsigned long long)cnwave::wave_incl_dpp((uint32_t)(pk >> 32)) << 32);
     if (lane == 63) wtot[wv] = inc;
     __syncthreads();
     unsigned long long wpre = 0, total = 0;
@@ -748,17 +735,16 @@ int telofind_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, const char *m
     cornetto_hit_t *out = nullptr;
     int64_t n_out = 0;
     if (nt > 0) {
-        const size_t np = 4 * ((nt + 4095) / 4096) + 4;   // (scan partials of the four counters)
         uint2 *d_lut = (uint2 *)cn_ws(h, WS_TF_LUT, 256 * sizeof(uint2) + 2 * (size_t)k + 16);
         uint8_t *d_mot = reinterpret_cast<uint8_t *>(d_lut + 256);
         // small device block: totals[4] u64, ovf u32, err u32
         unsigned long long *d_cnt = (unsigned long long *)cn_ws(h, WS_TF_CNT, 64);
         uint4 *d_tc = (uint4 *)cn_ws(h, WS_TF_TC, nt * sizeof(uint4));
-        // 4 scanned offset arrays + scan partials
-        uint32_t *d_off = (uint32_t *)cn_ws(h, WS_TF_TB, (4 * nt + np) * sizeof(uint32_t));
+        // 4 scanned offset arrays
+        uint32_t *d_off = (uint32_t *)cn_ws(h, WS_TF_TB, 4 * nt * sizeof(uint32_t));
         unsigned long long *p_cnt = (unsigned long long *)cn_pin(h, PIN_SMALL, 64);
         if (!d_lut || !d_cnt || !d_tc || !d_off || !p_cnt) return cn_fail(h, CORNETTO_E_NOMEM, "telofind: workspace allocation failed");
-        uint32_t *d_offq[4] = {d_off, d_off + nt, d_off + 2 * nt, d_off + 3 * nt}, *d_part = d_off + 4 * nt;
+        uint32_t *d_offq[4] = {d_off, d_off + nt, d_off + 2 * nt, d_off + 3 * nt};
         uint32_t *d_ovf = reinterpret_cast<uint32_t *>(d_cnt + 4), *d_err = d_ovf + 1;
         const std::string both = motif + rc;          // (pageable host memory: the copy has left it when the call returns)
         if (h->tf_lut_key != both || h->tf_lut_ptr != d_lut) {   // (the tables of the last call's motif are still there otherwise)
@@ -818,7 +804,7 @@ int telofind_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, const char *m
         if (bitmap_valid) *bitmap_valid = want_bitmap;
         if (hits) {
             // place of every tile in the dense, contig-ordered lists + list totals
-            CN_TRY(cnscan::exclusive_u32_multi(h, "tf_order", reinterpret_cast<const uint32_t *>(d_tc), (int64_t)nt, 4, 4, d_offq, d_part, d_cnt));
+            CN_TRY(cnscan::exclusive_u32_multi(h, "tf_order", reinterpret_cast<const uint32_t *>(d_tc), (int64_t)nt, 4, 4, d_offq, d_cnt));
             CN_HIP(h, hipMemcpyAsync(p_cnt, d_cnt, 64, hipMemcpyDeviceToHost, h->stream));
             CN_HIP(h, hipStreamSynchronize(h->stream));   // also covers the `lut` upload
             CN_TRACE("telofind: counts on the host");
@@ -1094,17 +1080,16 @@ int cn_telo_spec_queue(cornetto_accel_t *h, cornetto_asm_t *a, const char *motif
     const std::string rc = revcomp(motif), both = motif + rc;
     if (has_border(motif) || has_border(rc)) return CORNETTO_OK;
     const size_t nt = (size_t)a->tf_n_tiles;
-    const size_t np = 4 * ((nt + 4095) / 4096) + 4;
     uint2 *d_lut = (uint2 *)cn_ws(h, WS_TF_LUT, 256 * sizeof(uint2) + 2 * (size_t)k + 16);
     if (!d_lut || h->tf_lut_key != both || h->tf_lut_ptr != d_lut) return CORNETTO_OK;      // (the tables of this motif are not on the device: the exact call uploads them)
     const int H = k <= 8 ? 7 : (k <= 16 ? 15 : 31);
     unsigned long long *d_cnt = (unsigned long long *)cn_ws(h, WS_TF_CNT, 64);
     uint4 *d_tc = (uint4 *)cn_ws(h, WS_TF_TC, nt * sizeof(uint4));
-    uint32_t *d_off = (uint32_t *)cn_ws(h, WS_TF_TB, (4 * nt + np) * sizeof(uint32_t));
+    uint32_t *d_off = (uint32_t *)cn_ws(h, WS_TF_TB, 4 * nt * sizeof(uint32_t));
     const size_t words = (size_t)a->tw_n_words;
     unsigned long long *d_bitmap = (unsigned long long *)cn_ws(h, WS_TF_BITMAP, words * 8);
     if (!d_cnt || !d_tc || !d_off || !d_bitmap) return cn_fail(h, CORNETTO_E_NOMEM, "telo_scan: workspace allocation failed");
-    uint32_t *d_offq[4] = {d_off, d_off + nt, d_off + 2 * nt, d_off + 3 * nt}, *d_part = d_off + 4 * nt;
+    uint32_t *d_offq[4] = {d_off, d_off + nt, d_off + 2 * nt, d_off + 3 * nt};
     uint32_t *d_ovf = reinterpret_cast<uint32_t *>(d_cnt + 4), *d_err = d_ovf + 1;
     int32_t *d_rows[4];
     for (int q = 0; q < 4; ++q) {
@@ -1159,7 +1144,7 @@ int cn_telo_spec_queue(cornetto_accel_t *h, cornetto_asm_t *a, const char *motif
     CN_HIP(h, hipMemsetAsync(d_twcnt, 0, 8, h->stream));
     TwArgs W{d_bitmap, a->d_tw_boff, a->d_len, a->d_tw_tiles, thr_adj, d_wout, d_twcnt, (uint32_t)std::min<size_t>(win_ws_cap, 0x7fffffff)};
     CN_LAUNCH(h, "tw_scan", tw_scan<<<dim3((unsigned)a->tw_n_tiles), dim3(256), 0, h->stream>>>(W));
-    CN_TRY(cnscan::exclusive_u32_multi(h, "tf_order", reinterpret_cast<const uint32_t *>(d_tc), (int64_t)nt, 4, 4, d_offq, d_part, d_cnt));
+    CN_TRY(cnscan::exclusive_u32_multi(h, "tf_order", reinterpret_cast<const uint32_t *>(d_tc), (int64_t)nt, 4, 4, d_offq, d_cnt));
     const uint4 caps = make_uint4((uint32_t)seg[0], (uint32_t)seg[1], (uint32_t)seg[2], (uint32_t)seg[3]);
     CN_LAUNCH(h, "tf_gather", tf_gather<<<dim3((unsigned)((nt + 3) / 4)), dim3(256), 0, h->stream>>>(d_rows[0], d_rows[1], d_rows[2], d_rows[3], d_tc, d_offq[0], d_offq[1],
                                                                                                     d_offq[2], d_offq[3], d_list[0], d_list[1], d_list[2], d_list[3], caps,

@@ -215,9 +215,8 @@ int cornetto_telobreaks(cornetto_accel_t *h, const int32_t *ctg_len, int32_t n_c
     cornetto_ivl_t *o = nullptr;
     int64_t n = 0;
     if (W > 0 && n_tel > 0 && n_sd > 0) {
-        // bitsets | word offsets | lengths | tiles | counts + offsets + scan partials | records in
-        const size_t npart = (nt + 4095) / 4096 + 1;
-        const size_t bytes = W * 16 + ((size_t)n_ctg + 1) * 8 + (size_t)n_ctg * 4 + 8 + nt * sizeof(TbTile) + (nt * 4 + npart) * 4 + 64 +
+        // bitsets | word offsets | lengths | tiles | counts + offsets | records in
+        const size_t bytes = W * 16 + ((size_t)n_ctg + 1) * 8 + (size_t)n_ctg * 4 + 8 + nt * sizeof(TbTile) + (nt * 4 + 1) * 4 + 64 +
                              (size_t)n_sd * sizeof(cornetto_ivl_t) + (size_t)n_tel * sizeof(cornetto_telrow_t) + 64;
         uint8_t *ws = (uint8_t *)cn_ws(h, WS_TB, bytes);
         unsigned long long *d_small = (unsigned long long *)cn_ws(h, WS_TB_SMALL, 64);
@@ -226,8 +225,8 @@ int cornetto_telobreaks(cornetto_accel_t *h, const int32_t *ctg_len, int32_t n_c
         unsigned long long *d_bits = (unsigned long long *)ws, *d_fin = d_bits + W;
         int64_t *d_woff = (int64_t *)(d_fin + W);
         TbTile *d_tiles = (TbTile *)(d_woff + n_ctg + 1);
-        uint32_t *d_ns = (uint32_t *)(d_tiles + nt), *d_ne = d_ns + nt, *d_os = d_ne + nt, *d_oe = d_os + nt, *d_part = d_oe + nt;
-        int32_t *d_len = (int32_t *)(d_part + npart);
+        uint32_t *d_ns = (uint32_t *)(d_tiles + nt), *d_ne = d_ns + nt, *d_os = d_ne + nt, *d_oe = d_os + nt;
+        int32_t *d_len = (int32_t *)(d_oe + nt);
         cornetto_ivl_t *d_sd = (cornetto_ivl_t *)(d_len + n_ctg + 1);
         cornetto_telrow_t *d_tel = (cornetto_telrow_t *)(d_sd + n_sd);
         TbArgs A{d_len, d_woff, n_ctg, d_bits, d_fin, reinterpret_cast<uint32_t *>(d_small + 2)};
@@ -243,8 +242,8 @@ int cornetto_telobreaks(cornetto_accel_t *h, const int32_t *ctg_len, int32_t n_c
             CN_LAUNCH(h, "tb_fill", tb_fill<<<dim3((unsigned)((n_sd + 255) / 256)), dim3(256), 0, h->stream>>>(A, d_sd, n_sd));
             CN_LAUNCH(h, "tb_mark", tb_mark<<<dim3((unsigned)((n_tel + 255) / 256)), dim3(256), 0, h->stream>>>(A, d_tel, n_tel));
             CN_LAUNCH(h, "tb_count", tb_count<<<dim3((unsigned)nt), dim3(256), 0, h->stream>>>(A, d_tiles, d_ns, d_ne));
-            CN_TRY(cnscan::exclusive_u32(h, "tb_scan", d_ns, (int64_t)nt, 1, d_os, d_part, d_small));
-            CN_TRY(cnscan::exclusive_u32(h, "tb_scan", d_ne, (int64_t)nt, 1, d_oe, d_part, d_small + 1));
+            CN_TRY(cnscan::exclusive_u32(h, "tb_scan", d_ns, (int64_t)nt, 1, d_os, d_small));
+            CN_TRY(cnscan::exclusive_u32(h, "tb_scan", d_ne, (int64_t)nt, 1, d_oe, d_small + 1));
             CN_HIP(h, hipMemcpyAsync(p_small, d_small, 64, hipMemcpyDeviceToHost, h->stream));
             return CORNETTO_OK;
         }();

@@ -178,40 +178,38 @@ int telo_ends_stage(cornetto_accel_t *h, const cornetto_asm_t *a, const unsigned
     size_t n_out = 0;
     if (nt > 0) {
         if (nw > 0x7fffffffull) return cn_fail(h, CORNETTO_E_UNSUPPORTED, "telo_ends: too many window tiles");
-        const size_t npw = 2 * ((nw + 4095) / 4096) + 4;            // (scan partials of the two counters)
-        uint8_t *ws = (uint8_t *)cn_ws(h, WS_TE_WORDS, nw * (3 * 8 + sizeof(uint2) + 2 * 4) + npw * 4);
+        uint8_t *ws = (uint8_t *)cn_ws(h, WS_TE_WORDS, nw * (3 * 8 + sizeof(uint2) + 2 * 4) + 4 * 4);
         unsigned long long *d_tot = (unsigned long long *)cn_ws(h, WS_TE_CNT, 64);
         unsigned long long *p_tot = (unsigned long long *)cn_pin(h, PIN_SMALL, 64);
         if (!ws || !d_tot || !p_tot) return cn_fail(h, CORNETTO_E_NOMEM, "telo_ends: workspace allocation failed");
         unsigned long long *d_flags = reinterpret_cast<unsigned long long *>(ws), *d_heads = d_flags + nw, *d_tails = d_heads + nw;
         uint2 *d_cnt = reinterpret_cast<uint2 *>(d_tails + nw);
-        uint32_t *d_off[2] = {reinterpret_cast<uint32_t *>(d_cnt + nw), reinterpret_cast<uint32_t *>(d_cnt + nw) + nw}, *d_part = d_off[1] + nw;
+        uint32_t *d_off[2] = {reinterpret_cast<uint32_t *>(d_cnt + nw), reinterpret_cast<uint32_t *>(d_cnt + nw) + nw};
         CN_HIP(h, hipMemsetAsync(d_tot, 0, 64, h->stream));
         TeQualArgs Q{d_marks, a->d_tw_boff, a->d_len, a->d_tw_tiles, thr, d_flags};
         CN_LAUNCH(h, "te_qual", te_qual<<<dim3((unsigned)nt), dim3(256), 0, h->stream>>>(Q));
         TeRunArgs R{d_flags, a->d_tw_tiles, (int64_t)nt, G, d_heads, d_tails, d_cnt};
         CN_LAUNCH(h, "te_runs", te_runs<<<dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, h->stream>>>(R));
-        CN_TRY(cnscan::exclusive_u32_multi(h, "te_order", reinterpret_cast<const uint32_t *>(d_cnt), (int64_t)nw, 2, 2, d_off, d_part, d_tot));
+        CN_TRY(cnscan::exclusive_u32_multi(h, "te_order", reinterpret_cast<const uint32_t *>(d_cnt), (int64_t)nw, 2, 2, d_off, d_tot));
         // the region list: room for what the last call on this handle needed
         size_t cap = std::max<size_t>(4096, h->te_cap);
         const int force = CN_DEV_INT("CORNETTO_TE_CAP_FORCE", 0);   // (tests: an estimate that does not hold)
         if (force > 0) cap = (size_t)force;
         for (int attempt = 0; attempt < 2; ++attempt) {
-            const size_t npk = (cap + 4095) / 4096 + 4;
-            uint8_t *wr = (uint8_t *)cn_ws(h, WS_TE_REG, cap * (sizeof(int2) + 3 * 4) + npk * 4);
+            uint8_t *wr = (uint8_t *)cn_ws(h, WS_TE_REG, cap * (sizeof(int2) + 3 * 4) + 4 * 4);
             cornetto_ivl_t *d_rows = (cornetto_ivl_t *)cn_ws(h, WS_TE_ROWS, 2 * cap * sizeof(cornetto_ivl_t));
             const size_t spec = std::min<size_t>(2 * cap, 8192);    // the count and, with it, the first rows (an assembly has a few hundred): one round trip
             cornetto_ivl_t *p_rows = (cornetto_ivl_t *)cn_pin(h, PIN_TE, spec * sizeof(cornetto_ivl_t));
             if (!wr || !d_rows || !p_rows) return cn_fail(h, CORNETTO_E_NOMEM, "telo_ends: workspace allocation failed");
             int2 *d_rs = reinterpret_cast<int2 *>(wr);
             int32_t *d_re = reinterpret_cast<int32_t *>(d_rs + cap);
-            uint32_t *d_kk = reinterpret_cast<uint32_t *>(d_re + cap), *d_offk = d_kk + cap, *d_partk = d_offk + cap;
+            uint32_t *d_kk = reinterpret_cast<uint32_t *>(d_re + cap), *d_offk = d_kk + cap;
             TePlaceArgs P{d_heads, d_tails, d_off[0], d_off[1], a->d_tw_tiles, a->d_len, (int64_t)nt, (uint32_t)cap, d_rs, d_re};
             CN_LAUNCH(h, "te_place", te_place<<<dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, h->stream>>>(P));
             TeEndArgs E{d_rs, d_re, a->d_len, d_tot, (uint32_t)cap, ends, d_kk, d_offk, d_rows};
             const unsigned nb = (unsigned)((cap + 255) / 256);
             CN_LAUNCH(h, "te_ends", te_ends<<<dim3(nb), dim3(256), 0, h->stream>>>(E));
-            CN_TRY(cnscan::exclusive_u32(h, "te_order", d_kk, (int64_t)cap, 1, d_offk, d_partk, d_tot + 2));
+            CN_TRY(cnscan::exclusive_u32(h, "te_order", d_kk, (int64_t)cap, 1, d_offk, d_tot + 2));
             CN_LAUNCH(h, "te_emit", te_emit<<<dim3(nb), dim3(256), 0, h->stream>>>(E));
             CN_HIP(h, hipMemcpyAsync(p_tot, d_tot, 32, hipMemcpyDeviceToHost, h->stream));
             CN_HIP(h, hipMemcpyAsync(p_rows, d_rows, spec * sizeof(cornetto_ivl_t), hipMemcpyDeviceToHost, h->stream));

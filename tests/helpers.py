@@ -110,6 +110,23 @@ def read_bedgraph_pair(tot_path, mq_path):
     return out
 
 
+def token_at(text, at, nlines=None):
+    """the (first nlines) lines of a bedgraph with two spaces between the fields, and as many behind one contig name as it takes for the
+    field behind it to start at byte `at` of the text"""
+    out, pos, done = [], 0, False
+    for ln in text.splitlines()[:nlines]:
+        f = ln.split()
+        line = b"  ".join(f) + b"\n"
+        if not done and pos + len(line) + len(f[0]) + 2 > at:        # the last line whose second field can still be moved there
+            line = f[0] + b" " * (at - pos - len(f[0])) + b"  ".join(f[1:]) + b"\n"
+            done = True
+        out.append(line)
+        pos += len(line)
+    text = b"".join(out)
+    assert done and text[at - 1:at] == b" " and not text[at:at + 1].isspace()
+    return text
+
+
 def fmt_telofind(name, length, hits):
     """src/find_telomere.c:51,56"""
     return b"".join(b"%s\t%d\t%d\t%d\t%d\t%d\n" % (name, length, h["strand"], h["start"], h["end"], h["end"] - h["start"])

@@ -100,6 +100,44 @@ def test_pieces_any_split_point(acc):
         assert pend == b"" and got == [(n, c, s, q) for n, c, s, q in exp], piece
 
 
+def seam_text(n, p, fasta):
+    """exactly n bytes of one-line-payload records whose headers are padded so that a newline is byte p of the text: the last newline of
+    the first record, behind which a second record fills the text.  Where a second record does not fit, FASTA: the header's newline, with
+    the bytes that are left as a payload without its newline; FASTQ: the bytes that are left are the beginning of a cut-off record."""
+    head, body = (b">c%d ", b"ACGTACGT\n") if fasta else (b"@r%d ", b"ACGTACGT\n+\nIIIIIIII\n")
+    rec = lambda i, size: head % i + b"x" * (size - 5 - len(body)) + b"\n" + body
+    rest = n - (p + 1)
+    if rest == 0 or rest >= 5 + len(body):
+        text = rec(0, p + 1) + (rec(1, rest) if rest else b"")
+    elif fasta:
+        text = head % 0 + b"x" * (p - 4) + b"\n" + b"A" * rest
+    else:
+        text = rec(0, p + 1) + b"@" * rest
+    assert len(text) == n and text[p:p + 1] == b"\n"
+    return text
+
+
+# the index of the newlines counts and scatters in tiles of 4096 bytes: a newline as the last byte of a tile, as the first byte of the
+# next one, and as the very last byte of the text
+SEAMS = [(n, p) for n in (4095, 4096, 4097, 8192) for p in sorted({4095, 4096, n - 1}) if p < n]
+
+
+@pytest.mark.parametrize("n,p", SEAMS)
+def test_fastq_newline_at_a_tile_seam(acc, n, p):
+    text = seam_text(n, p, fasta=False)
+    recs, used, plain, exp = check_prefix(acc, text)
+    assert len(recs) == len(exp) == text.count(b"@r") and [int(x) for x in recs["len"]] == [8] * len(recs)
+    assert used == (n if text.endswith(b"\n") else p + 1) and plain == text.endswith(b"\n")
+
+
+@pytest.mark.parametrize("n,p", SEAMS)
+def test_fasta_newline_at_a_tile_seam(acc, n, p):
+    text = seam_text(n, p, fasta=True)
+    recs, used, plain, exp = check_fasta(acc, text)
+    assert len(recs) == len(exp) == text.count(b">c") and [int(x) for x in recs["len"]] == [len(s) for _, _, s, _ in exp]
+    assert used == n and plain
+
+
 def test_empty_and_tiny_inputs(acc):
     for text in (b"", b"\n", b"@", b"@r\n", b"@r\nA\n+\n", b"@r\nA\n+\nI", b"@r\nA\n+\nI\n", b"@r\n\n+\n\n", b"\n\n\n\n"):
         check_prefix(acc, text)

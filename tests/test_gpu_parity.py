@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import oracle_bind as ob
-from helpers import (fmt_sdust, fmt_telofind, fmt_telowin, golden, read_bedgraph_pair, read_fastx)
+from helpers import (fmt_sdust, fmt_telofind, fmt_telowin, golden, read_bedgraph_pair, read_fastx, token_at)
 
 pytestmark = pytest.mark.gpu
 
@@ -929,9 +929,14 @@ def test_bedgraph_ingest_matches_host_parse(acc, golden_dir, bg_ctgs, mean):
         t = b"".join(t.splitlines(True)[:nlines])
         q = b"".join(q.splitlines(True)[:nlines])
     rng = np.random.default_rng(mean)
-    cov, names, ncl = acc.bedgraph_ingest(_split(t, rng, mean), _split(q, rng, mean + 7))
-    exp = bg_ctgs
-    if mean < 1000:
+    got = acc.bedgraph_ingest(_split(t, rng, mean), _split(q, rng, mean + 7))
+    _check_ingest(acc, got, t, q, None if mean < 1000 else bg_ctgs)
+
+
+def _check_ingest(acc, got, t, q, exp=None):
+    """the coverage of an ingest of the texts t and q against the host parse of the same texts (exp: that parse, when the caller has it)"""
+    cov, names, ncl = got
+    if exp is None:
         import tempfile
         with tempfile.TemporaryDirectory() as d:
             open(os.path.join(d, "t.bg"), "wb").write(t)
@@ -950,6 +955,14 @@ def test_bedgraph_ingest_matches_host_parse(acc, golden_dir, bg_ctgs, mean):
         assert np.array_equal(got, ex.astype(got.dtype)), ci
     assert ncl == sum(int((np.array(v) > 65535).sum()) for v in _raw_depths(t, q))
     cov.close()
+
+
+@pytest.mark.parametrize("at", [4095, 4096])
+def test_bedgraph_ingest_token_at_a_tile_seam(acc, golden_dir, at):
+    """a token that starts at the last byte of a tile of the tokeniser (4096 bytes) and at the first byte of the next one, behind a
+    run of spaces"""
+    t, q = (token_at(x, at, 400) for x in _bg_text(golden_dir))
+    _check_ingest(acc, acc.bedgraph_ingest([t], [q]), t, q)
 
 
 @pytest.mark.parametrize("mode", [1, 2])

@@ -14,7 +14,7 @@ import pytest
 
 import cornetto_amd
 from cornetto_amd import BGRUN_TILE as T, BedgraphFormatError
-from helpers import PANEL, PANEL_ABORT, golden, panel_argv
+from helpers import PANEL, PANEL_ABORT, golden, panel_argv, token_at
 from runs_cases import expand, expand_arrays, fmt, parse, to_runs
 
 pytestmark = pytest.mark.gpu
@@ -121,6 +121,25 @@ def test_feed_splits_do_not_matter(acc):
                 first = got
             for (d, m), (d0, m0) in zip(got, first):
                 assert np.array_equal(d, d0) and np.array_equal(m, m0)
+
+
+@pytest.mark.parametrize("at", [4095, 4096])
+def test_token_at_a_tile_seam_of_the_tokeniser(acc, at):
+    """one feed in which a token starts at the last byte of a tile of the tokeniser (4096 bytes) and at the first byte of the next one,
+    behind a run of spaces"""
+    contigs = [[(1 + i % 5, (7 * i) % 60) for i in range(130)] for _ in range(3)]
+    t = token_at(text_of(contigs, prefix=b"contig_"), at)
+    assert len(t) > at + 100
+    check_parity(acc, t, text_of(recut(contigs, 37), prefix=b"contig_"))
+
+
+@pytest.mark.parametrize("n", [2047, 2048, 2049])
+def test_records_at_the_tile_seam_of_the_offset_scan(acc, n):
+    """one feed of exactly n fresh records: one tile of the 64-bit scan of the run lengths less one record, a whole tile, one record more"""
+    contigs = [[(1 + i % 3, i % 50) for i in range(n)]]
+    t = text_of(contigs)
+    assert len(parse(t)) == n
+    check_parity(acc, t, text_of(recut(contigs, 37)))
 
 
 @pytest.mark.parametrize("head", [1, 7, 9])

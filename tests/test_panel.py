@@ -223,7 +223,9 @@ def acc():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("seed,n,dist", [(1, 1, 0), (2, 50, 0), (3, 5000, 10), (4, 200_000, 1000), (5, 1_000_000, 0), (6, 70_000, 200_000)])
+@pytest.mark.parametrize("seed,n,dist", [(1, 1, 0), (2, 50, 0), (3, 5000, 10), (4, 200_000, 1000), (5, 1_000_000, 0), (6, 70_000, 200_000),
+                                         # the tile seams of the max-scan (1024 intervals) and of the add-scan of the heads (4096)
+                                         (7, 1023, 0), (8, 1024, 0), (9, 1025, 0), (10, 4095, 0), (11, 4096, 0), (12, 4097, 0)])
 def test_ivl_merge_vs_oracle(acc, seed, n, dist):
     rng = np.random.default_rng(seed)
     ctg = np.sort(rng.integers(0, max(1, n // 1000 + 3), size=n)).astype(np.int32)
