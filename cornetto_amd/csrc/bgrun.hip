@@ -142,6 +142,16 @@ __global__ __launch_bounds__(RL_THREADS) void rl_scan_add(unsigned long long *io
         if (base + k < n) io[base + k] += add;
 }
 
+// io[0 .. n) -> its exclusive prefix in place, *d_total = the sum; partial: room for ceil(n / RS_TILE) words
+static int rl_scan(cornetto_accel_t *h, unsigned long long *io, int64_t n, unsigned long long *partial, unsigned long long *d_total)
+{
+    const int64_t np = (n + RS_TILE - 1) / RS_TILE;
+    CN_LAUNCH(h, "rl_scan", rl_scan_tile<<<dim3((unsigned)np), dim3(RL_THREADS), 0, h->stream>>>(io, n, partial));
+    CN_LAUNCH(h, "rl_scan", rl_scan_totals<<<dim3(1), dim3(1024), 0, h->stream>>>(partial, np, d_total));
+    CN_LAUNCH(h, "rl_scan", rl_scan_add<<<dim3((unsigned)np), dim3(RL_THREADS), 0, h->stream>>>(io, n, partial));
+    return CORNETTO_OK;
+}
+
 // contig starts: record -> first position of the record in the span
 __global__ void rl_break_pos(const uint4 *breaks, uint32_t n, const unsigned long long *off, unsigned long long *pos)
 {
@@ -367,9 +377,7 @@ int cornetto_bgrun_feed(cornetto_accel_t *h, cornetto_bgrun_t *b, int file, cons
             return rl_format_error(h, b, (int)(p_small[0] & 15), file, rec, det[0], det[1]);
         }
         const unsigned long long clamped = p_small[2];
-        CN_LAUNCH(h, "rl_scan", rl_scan_tile<<<dim3((unsigned)np), dim3(RL_THREADS), 0, h->stream>>>(d_off, fresh, d_part));
-        CN_LAUNCH(h, "rl_scan", rl_scan_totals<<<dim3(1), dim3(1024), 0, h->stream>>>(d_part, np, d_small + 3));
-        CN_LAUNCH(h, "rl_scan", rl_scan_add<<<dim3((unsigned)np), dim3(RL_THREADS), 0, h->stream>>>(d_off, fresh, d_part));
+        CN_TRY(rl_scan(h, d_off, fresh, d_part, d_small + 3));
         unsigned long long *d_bpos = reinterpret_cast<unsigned long long *>(d_brk + break_cap);
         if (nb) {
             rl_break_pos<<<dim3((nb + 255) / 256), dim3(256), 0, h->stream>>>(d_brk, nb, d_off, d_bpos);
@@ -497,5 +505,27 @@ int cornetto_bgrun_finish(cornetto_accel_t *h, cornetto_bgrun_t *b, cornetto_cov
     *names = nm;
     return CORNETTO_OK;
 }
+
+#ifdef CN_DEV
+// development build only (selftest.hip, tests/test_gpu_scan.py): the 64-bit scan of the feed path on its own — io[0 .. n) (host) becomes
+// its exclusive prefix, *total the sum
+int cn_selftest_scan_u64(cornetto_accel_t *h, unsigned long long *io, int64_t n, unsigned long long *total)
+{
+    if (!h || !io || !total || n <= 0 || n > ((int64_t)1 << 28)) return cn_fail(h, CORNETTO_E_ARG, "selftest_scan_u64: bad argument");
+    CN_HIP(h, hipSetDevice(h->device));
+    cn_timing_begin(h);
+    const int64_t np = (n + RS_TILE - 1) / RS_TILE;
+    DevBuf d;
+    if (d.alloc(((size_t)n + (size_t)np + 1) * 8) != hipSuccess) return cn_fail(h, CORNETTO_E_NOMEM, "selftest: device allocation failed");
+    unsigned long long *d_io = d.as<unsigned long long>(), *d_part = d_io + n;
+    CN_HIP(h, hipMemcpyAsync(d_io, io, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+    CN_TRY(rl_scan(h, d_io, n, d_part, d_part + np));
+    CN_HIP(h, hipMemcpyAsync(io, d_io, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+    CN_HIP(h, hipMemcpyAsync(total, d_part + np, 8, hipMemcpyDeviceToHost, h->stream));
+    CN_HIP(h, hipStreamSynchronize(h->stream));
+    cn_timing_end(h);
+    return CORNETTO_OK;
+}
+#endif
 
 }  // extern "C"

@@ -269,7 +269,7 @@ static inline int merge_fused(cornetto_accel_t *h, const char *name, const corne
     if (n_cap <= 0) return CORNETTO_OK;
     const int64_t nt = (n_cap + ST_TILE - 1) / ST_TILE;
     const size_t need = 64 + (size_t)nt * 32;
-    const bool fresh = h->dev[WS_STITCH].bytes < need;
+    const bool fresh = h->dev[WS_STITCH].bytes < need || h->st_epoch >= 0x3FFFFFFFu;   // (as scan.hpp: after the last epoch the states are cleared)
     uint8_t *ws = (uint8_t *)cn_ws(h, WS_STITCH, need);
     if (!ws) return cn_fail(h, CORNETTO_E_NOMEM, "merge: workspace allocation failed");
     const int rc = [&]() -> int {
@@ -278,8 +278,7 @@ static inline int merge_fused(cornetto_accel_t *h, const char *name, const corne
             h->st_tickets = 0;
             h->st_epoch = 0;
         }
-        uint32_t epoch = (h->st_epoch + 1) & 0x3FFFFFFFu;
-        if (epoch == 0) epoch = 1;
+        const uint32_t epoch = h->st_epoch + 1;      // 1 .. 0x3FFFFFFF
         StArgs A{d_in, d_n, n_cap, dist, reinterpret_cast<unsigned long long *>(ws + 64), reinterpret_cast<uint32_t *>(ws), h->st_tickets, epoch, d_out, d_count};
         CN_LAUNCH(h, name, st_fused<<<dim3((unsigned)nt), dim3(ST_THREADS), 0, h->stream>>>(A));
         h->st_epoch = epoch;                         // (the device's ticket counter advances iff the kernel was queued)
@@ -302,6 +301,8 @@ static inline int merge(cornetto_accel_t *h, const char *name, const cornetto_iv
                         cornetto_ivl_t *d_out, unsigned long long *d_count)
 {
     if (n_in <= 0) return CORNETTO_OK;
+    // (the ranks are the 32-bit scan of the head flags, exact while their sum — at most n_in — is below 2^32: scan.hpp)
+    if (n_in > 0xFFFFFFFFll) return cn_fail(h, CORNETTO_E_UNSUPPORTED, "%s: %lld intervals, at most 2^32-1 are merged in one call", name, (long long)n_in);
     const size_t n = (size_t)n_in, nt = (n + ST_TILE - 1) / ST_TILE;
     unsigned long long *d_k = (unsigned long long *)ws, *d_tile = d_k + n;
     uint32_t *d_head = (uint32_t *)(d_tile + nt + 1), *d_rank = d_head + n;

@@ -149,6 +149,10 @@ __global__ __launch_bounds__(SC_THREADS) void scan_lookback(LbArgs A)
 }
 
 // outs[q][i] = exclusive prefix of in[i * stride + q] for q < m (<= 4); d_total (optional): m grand totals (u64 each).
+// The contract of the 32-bit arithmetic: the offsets are the prefixes mod 2^32 — exact as long as the sum of everything in front of an
+// item is below 2^32 —, and a grand total is (u64)(exclusive prefix of the last tile, 32 bits) + the last tile's sum (32 bits): exact
+// only while the sum of all items is below 2^32, and never above 2^33 - 2.  Every caller bounds its sum by what it counts (DESIGN 4.3:
+// the table of call sites); nothing here checks it.
 static inline int exclusive_u32_multi(cornetto_accel_t *h, const char *name, const uint32_t *in, int64_t n, int stride, int m, uint32_t *const *outs,
                                       unsigned long long *d_total)
 {
@@ -158,17 +162,18 @@ static inline int exclusive_u32_multi(cornetto_accel_t *h, const char *name, con
     for (int q = 0; q < m; ++q) o.o[q] = outs[q];
     const int64_t np = (n + SC_TILE - 1) / SC_TILE;
     const size_t need = 64 + (size_t)m * (size_t)np * 8;
-    const bool fresh = h->dev[WS_SCAN].bytes < need;
+    // (the epoch has 30 bits in a state: after the last one the states are cleared like new memory — epoch 1 of the next round would
+    // otherwise meet the words that the first epoch 1 left in the tiles no call since has reached, and take them for prefixes)
+    const bool fresh = h->dev[WS_SCAN].bytes < need || h->scan_epoch >= 0x3FFFFFFFu;
     uint8_t *ws = (uint8_t *)cn_ws(h, WS_SCAN, need);
     if (!ws) return cn_fail(h, CORNETTO_E_NOMEM, "scan: workspace allocation failed");
     const int rc = [&]() -> int {
-        if (fresh) {                                 // new memory: no state of any epoch in it, the ticket counter starts again
+        if (fresh) {                                 // new memory, or every epoch used: no state of any epoch in it, the ticket counter starts again
             CN_HIP(h, hipMemsetAsync(ws, 0, h->dev[WS_SCAN].bytes, h->stream));
             h->scan_tickets = 0;
             h->scan_epoch = 0;
         }
-        uint32_t epoch = (h->scan_epoch + 1) & 0x3FFFFFFFu;
-        if (epoch == 0) epoch = 1;
+        const uint32_t epoch = h->scan_epoch + 1;    // 1 .. 0x3FFFFFFF
         LbArgs A{in, n, np, stride, m, o, reinterpret_cast<unsigned long long *>(ws + 64), reinterpret_cast<uint32_t *>(ws), h->scan_tickets, epoch, d_total};
         CN_LAUNCH(h, name, scan_lookback<<<dim3((unsigned)(m * np)), dim3(SC_THREADS), 0, h->stream>>>(A));
         h->scan_epoch = epoch;                       // the device's ticket counter advances iff the kernel was queued: the host's copy only then

@@ -1,0 +1,205 @@
+// selftest.hip — the scan primitives of wave.hpp / scan.hpp / ivlmerge.hpp behind plain C entry points, DEVELOPMENT BUILD ONLY (-DCN_DEV:
+// the product object of this file is empty, tests/test_abi.py looks for the prefix in both libraries).  tests/test_gpu_scan.py
+// (tests/selftest_bind.py) compares them with numpy on inputs the product entry points cannot produce: prepared tile states for the
+// look-back, full-range values, strides and counter sets at more than one tile, epochs next to the wrap.  Not part of the C ABI: no
+// declaration in include/cornetto_accel.h.  Every entry takes host pointers, allocates, copies and synchronises by itself.
+#ifdef CN_DEV
+#include "common.hpp"
+#include "ivlmerge.hpp"
+#include "scan.hpp"
+#include "wave.hpp"
+
+namespace {
+
+using u64 = unsigned long long;
+
+// one value per lane, one wave per 64 values
+template <int WHICH>
+__global__ __launch_bounds__(256) void selftest_wave(const void *in, void *out, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;                                // (n is a multiple of 64: whole waves leave)
+    const int lane = threadIdx.x & 63;
+    if (WHICH == 0) static_cast<uint32_t *>(out)[i] = cnwave::wave_incl<uint32_t>(static_cast<const uint32_t *>(in)[i], lane);
+    if (WHICH == 1) static_cast<u64 *>(out)[i] = cnwave::wave_incl<u64>(static_cast<const u64 *>(in)[i], lane);
+    if (WHICH == 2) static_cast<uint32_t *>(out)[i] = cnwave::wave_incl_dpp(static_cast<const uint32_t *>(in)[i]);
+    if (WHICH == 3) static_cast<uint32_t *>(out)[i] = cnwave::wave_sum(static_cast<const uint32_t *>(in)[i]);
+}
+
+// one value per thread, one block_excl per workgroup (and per kernel)
+template <typename T, int THREADS>
+__global__ __launch_bounds__(THREADS) void selftest_block_excl(const T *in, T *pre, T *totals)
+{
+    const int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    T total;
+    pre[i] = cnscan::block_excl<T, THREADS>(in[i], total);
+    if (threadIdx.x == THREADS - 1) totals[blockIdx.x] = total;
+}
+
+// ONE wave walks over prepared states
+__global__ __launch_bounds__(64) void selftest_walk(u64 *st, int64_t stride, int64_t tile, uint32_t epoch, uint32_t own, uint32_t *out)
+{
+    const uint32_t excl = cnscan::lookback_excl(st, stride, tile, epoch, own, (int)threadIdx.x);
+    if (threadIdx.x == 0) *out = excl;
+}
+
+// The look-back of scan.hpp restated on the host: true when the walk of `tile` over these words ENDS — every word that a round it
+// reaches polls carries the epoch and a kind, so no poll is repeated.  (A word that is not ready makes the wave spin until somebody
+// writes it, and nobody would.)
+bool walk_ends(const u64 *w, int64_t stride, int64_t tile, uint32_t epoch)
+{
+    const u64 tag = (u64)(epoch & 0x3FFFFFFFu) << 32;
+    for (int64_t pos = tile - 1; tile > 0; pos -= 64) {
+        bool incl = false;
+        for (int lane = 0; lane < 64; ++lane) {
+            const int64_t idx = pos - lane;
+            if (idx < 0) {                             // the sentinel: an inclusive prefix of 0
+                incl = true;
+                continue;
+            }
+            const u64 x = w[idx * stride];
+            if ((x >> 62) == 0 || (x & (0x3FFFFFFFull << 32)) != tag) return false;
+            if ((x >> 62) == 2) incl = true;
+        }
+        if (incl) break;
+    }
+    return true;
+}
+
+template <typename T, int THREADS>
+int run_block_excl(cornetto_accel_t *h, const void *in, void *pre_out, void *totals_out, int64_t n_blocks)
+{
+    const size_t n = (size_t)n_blocks * THREADS;
+    DevBuf d_in, d_pre, d_tot;
+    if (d_in.alloc(n * sizeof(T)) != hipSuccess || d_pre.alloc(n * sizeof(T)) != hipSuccess || d_tot.alloc((size_t)n_blocks * sizeof(T)) != hipSuccess)
+        return cn_fail(h, CORNETTO_E_NOMEM, "selftest: device allocation failed");
+    CN_HIP(h, hipMemcpyAsync(d_in.p, in, n * sizeof(T), hipMemcpyHostToDevice, h->stream));
+    selftest_block_excl<T, THREADS><<<dim3((unsigned)n_blocks), dim3(THREADS), 0, h->stream>>>(d_in.as<T>(), d_pre.as<T>(), d_tot.as<T>());
+    CN_HIP(h, hipGetLastError());
+    CN_HIP(h, hipMemcpyAsync(pre_out, d_pre.p, n * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+    CN_HIP(h, hipMemcpyAsync(totals_out, d_tot.p, (size_t)n_blocks * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+    CN_HIP(h, hipStreamSynchronize(h->stream));
+    return CORNETTO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// out[i] = the primitive `which` over the wave of in[i]: 0 wave_incl<uint32_t>, 1 wave_incl<unsigned long long> (in and out 64-bit),
+// 2 wave_incl_dpp, 3 wave_sum.  n: a multiple of 64.
+int cn_selftest_wave(cornetto_accel_t *h, int which, const void *in, void *out, int64_t n)
+{
+    if (!h || !in || !out || n <= 0 || n % 64 || which < 0 || which > 3) return cn_fail(h, CORNETTO_E_ARG, "selftest_wave: bad argument");
+    CN_HIP(h, hipSetDevice(h->device));
+    const size_t bytes = (size_t)n * (which == 1 ? 8 : 4);
+    DevBuf d_in, d_out;
+    if (d_in.alloc(bytes) != hipSuccess || d_out.alloc(bytes) != hipSuccess) return cn_fail(h, CORNETTO_E_NOMEM, "selftest: device allocation failed");
+    CN_HIP(h, hipMemcpyAsync(d_in.p, in, bytes, hipMemcpyHostToDevice, h->stream));
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (which == 0) selftest_wave<0><<<grid, block, 0, h->stream>>>(d_in.p, d_out.p, n);
+    if (which == 1) selftest_wave<1><<<grid, block, 0, h->stream>>>(d_in.p, d_out.p, n);
+    if (which == 2) selftest_wave<2><<<grid, block, 0, h->stream>>>(d_in.p, d_out.p, n);
+    if (which == 3) selftest_wave<3><<<grid, block, 0, h->stream>>>(d_in.p, d_out.p, n);
+    CN_HIP(h, hipGetLastError());
+    CN_HIP(h, hipMemcpyAsync(out, d_out.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    CN_HIP(h, hipStreamSynchronize(h->stream));
+    return CORNETTO_OK;
+}
+
+// pre_out[b * threads + t], totals_out[b] = block_excl<T, threads> of in[b * threads + t]; threads: 256 or 1024; T: 64-bit when is64
+int cn_selftest_block_excl(cornetto_accel_t *h, int threads, int is64, const void *in, void *pre_out, void *totals_out, int64_t n_blocks)
+{
+    if (!h || !in || !pre_out || !totals_out || n_blocks <= 0 || n_blocks > 65536 || (threads != 256 && threads != 1024))
+        return cn_fail(h, CORNETTO_E_ARG, "selftest_block_excl: bad argument");
+    CN_HIP(h, hipSetDevice(h->device));
+    if (threads == 256) return is64 ? run_block_excl<u64, 256>(h, in, pre_out, totals_out, n_blocks) : run_block_excl<uint32_t, 256>(h, in, pre_out, totals_out, n_blocks);
+    return is64 ? run_block_excl<u64, 1024>(h, in, pre_out, totals_out, n_blocks) : run_block_excl<uint32_t, 1024>(h, in, pre_out, totals_out, n_blocks);
+}
+
+// cnscan::lookback_excl by one wave over the prepared states `words` (updated in place), the state of tile t at words[t * stride + stride - 1]
+// (stride 1: scan_lookback's layout; stride 4: st_fused's, the head count's state is the fourth word of a tile's record).
+// CORNETTO_E_ARG, and NO launch, unless the walk provably ends on these words (walk_ends above).
+int cn_selftest_walk(cornetto_accel_t *h, unsigned long long *words, int64_t n_words, int64_t stride, int64_t tile, uint32_t epoch, uint32_t own, uint32_t *excl_out)
+{
+    if (!h || !words || !excl_out || stride < 1 || stride > 64 || tile < 0 || tile > (1 << 20) || n_words < (tile + 1) * stride)
+        return cn_fail(h, CORNETTO_E_ARG, "selftest_walk: bad argument");
+    if (!walk_ends(words + (stride - 1), stride, tile, epoch))
+        return cn_fail(h, CORNETTO_E_ARG, "selftest_walk: a state the walk of tile %lld polls is not ready: it would not end", (long long)tile);
+    CN_HIP(h, hipSetDevice(h->device));
+    DevBuf d_w, d_o;
+    if (d_w.alloc((size_t)n_words * 8) != hipSuccess || d_o.alloc(8) != hipSuccess) return cn_fail(h, CORNETTO_E_NOMEM, "selftest: device allocation failed");
+    CN_HIP(h, hipMemcpyAsync(d_w.p, words, (size_t)n_words * 8, hipMemcpyHostToDevice, h->stream));
+    selftest_walk<<<dim3(1), dim3(64), 0, h->stream>>>(d_w.as<u64>() + (stride - 1), stride, tile, epoch, own, d_o.as<uint32_t>());
+    CN_HIP(h, hipGetLastError());
+    CN_HIP(h, hipMemcpyAsync(words, d_w.p, (size_t)n_words * 8, hipMemcpyDeviceToHost, h->stream));
+    CN_HIP(h, hipMemcpyAsync(excl_out, d_o.p, 4, hipMemcpyDeviceToHost, h->stream));
+    CN_HIP(h, hipStreamSynchronize(h->stream));
+    return CORNETTO_OK;
+}
+
+// cnscan::exclusive_u32_multi itself, on the handle's own WS_SCAN, epoch and tickets: in holds n records of `stride` words, counter q is
+// word first + q of a record (first + m <= stride); outs: m arrays of n words one after the other; totals: m x u64, or null
+int cn_selftest_scan_u32(cornetto_accel_t *h, const uint32_t *in, int64_t n, int stride, int first, int m, uint32_t *outs, unsigned long long *totals)
+{
+    if (!h || !in || !outs || n <= 0 || n > ((int64_t)1 << 28) || stride < 1 || first < 0 || m < 1 || m > 4 || first + m > stride)
+        return cn_fail(h, CORNETTO_E_ARG, "selftest_scan_u32: bad argument");
+    CN_HIP(h, hipSetDevice(h->device));
+    cn_timing_begin(h);
+    DevBuf d_in, d_out, d_tot;
+    if (d_in.alloc((size_t)n * stride * 4) != hipSuccess || d_out.alloc((size_t)n * m * 4) != hipSuccess || d_tot.alloc(4 * 8) != hipSuccess)
+        return cn_fail(h, CORNETTO_E_NOMEM, "selftest: device allocation failed");
+    CN_HIP(h, hipMemcpyAsync(d_in.p, in, (size_t)n * stride * 4, hipMemcpyHostToDevice, h->stream));
+    uint32_t *o[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int q = 0; q < m; ++q) o[q] = d_out.as<uint32_t>() + (size_t)q * n;
+    CN_TRY(cnscan::exclusive_u32_multi(h, "selftest_scan", d_in.as<uint32_t>() + first, n, stride, m, o, totals ? d_tot.as<u64>() : nullptr));
+    CN_HIP(h, hipMemcpyAsync(outs, d_out.p, (size_t)n * m * 4, hipMemcpyDeviceToHost, h->stream));
+    if (totals)
+        CN_HIP(h, hipMemcpyAsync(totals, d_tot.p, (size_t)m * 8, hipMemcpyDeviceToHost, h->stream));
+    CN_HIP(h, hipStreamSynchronize(h->stream));
+    cn_timing_end(h);
+    return CORNETTO_OK;
+}
+
+// the host's epoch of the scans / of the fused merge alone: the ticket bases stay in step with the device's counters
+int cn_selftest_scan_set_epoch(cornetto_accel_t *h, uint32_t epoch)
+{
+    if (!h) return CORNETTO_E_ARG;
+    h->scan_epoch = epoch;
+    return CORNETTO_OK;
+}
+
+int cn_selftest_st_set_epoch(cornetto_accel_t *h, uint32_t epoch)
+{
+    if (!h) return CORNETTO_E_ARG;
+    h->st_epoch = epoch;
+    return CORNETTO_OK;
+}
+
+// cnivl::merge_fused itself (no public entry point reaches it without sdust in front), on the handle's own WS_STITCH, epoch and tickets:
+// in[0 .. n) ordered by (contig, start) -> out[0 .. *n_out), out with room for n rows; the grid is sized for n_cap >= n rows
+int cn_selftest_merge_fused(cornetto_accel_t *h, const cornetto_ivl_t *in, int64_t n, int64_t n_cap, int32_t dist, cornetto_ivl_t *out, int64_t *n_out)
+{
+    if (!h || !in || !out || !n_out || n <= 0 || n_cap < n || n_cap > ((int64_t)1 << 28) || dist < 0) return cn_fail(h, CORNETTO_E_ARG, "selftest_merge_fused: bad argument");
+    CN_HIP(h, hipSetDevice(h->device));
+    cn_timing_begin(h);
+    DevBuf d_in, d_out, d_small;
+    if (d_in.alloc((size_t)n_cap * sizeof(cornetto_ivl_t)) != hipSuccess || d_out.alloc((size_t)n_cap * sizeof(cornetto_ivl_t)) != hipSuccess || d_small.alloc(16) != hipSuccess)
+        return cn_fail(h, CORNETTO_E_NOMEM, "selftest: device allocation failed");
+    unsigned long long small[2] = {(unsigned long long)n, ~0ull};       // the number of rows | the count (kept when the merge declines)
+    CN_HIP(h, hipMemcpyAsync(d_in.p, in, (size_t)n * sizeof(cornetto_ivl_t), hipMemcpyHostToDevice, h->stream));
+    CN_HIP(h, hipMemcpyAsync(d_small.p, small, 16, hipMemcpyHostToDevice, h->stream));
+    CN_HIP(h, hipStreamSynchronize(h->stream));                         // (`small` is pageable memory of this frame)
+    CN_TRY(cnivl::merge_fused(h, "selftest_merge", d_in.as<cornetto_ivl_t>(), d_small.as<u64>(), n_cap, dist, d_out.as<cornetto_ivl_t>(), d_small.as<u64>() + 1));
+    CN_HIP(h, hipMemcpyAsync(small, d_small.p, 16, hipMemcpyDeviceToHost, h->stream));
+    CN_HIP(h, hipStreamSynchronize(h->stream));
+    cn_timing_end(h);
+    if (small[1] > (unsigned long long)n) return cn_fail(h, CORNETTO_E_HIP, "selftest_merge_fused: no count");
+    CN_HIP(h, hipMemcpyAsync(out, d_out.p, (size_t)small[1] * sizeof(cornetto_ivl_t), hipMemcpyDeviceToHost, h->stream));
+    CN_HIP(h, hipStreamSynchronize(h->stream));
+    *n_out = (int64_t)small[1];
+    return CORNETTO_OK;
+}
+
+}  // extern "C"
+#endif

@@ -511,6 +511,16 @@ bool has_border(const std::string &m)
     return false;
 }
 
+// tf_order scans the entries of each of the four lists with 32-bit sums (scan.hpp: exact below 2^32, and the check of the totals against
+// 2^31 - 1 relies on that).  The most entries a list of this assembly can have: a bordered motif lists every match, one per start position;
+// otherwise the heads / tails of runs, and of two positions k apart at most one is a head (its match is not preceded by one k in front of
+// it) — k of any 2k positions, at most len / 2 + k per contig.
+bool tf_lists_fit_u32(const cornetto_asm_t *a, int k, bool bordered)
+{
+    const unsigned long long most = bordered ? (unsigned long long)a->total : (unsigned long long)a->total / 2 + (unsigned long long)a->n * (unsigned long long)k;
+    return most <= 0xFFFFFFFFull;
+}
+
 struct WinLayout {
     std::vector<int64_t> bit_off;
     std::vector<int2> tiles;
@@ -803,6 +813,8 @@ int telofind_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, const char *m
         CN_TRACE("telofind: tf_scan queued");
         if (bitmap_valid) *bitmap_valid = want_bitmap;
         if (hits) {
+            if (!tf_lists_fit_u32(a, k, bordered))
+                return cn_fail(h, CORNETTO_E_UNSUPPORTED, "telofind: %lld bases can hold more than 2^32-1 list entries of this motif", (long long)a->total);
             // place of every tile in the dense, contig-ordered lists + list totals
             CN_TRY(cnscan::exclusive_u32_multi(h, "tf_order", reinterpret_cast<const uint32_t *>(d_tc), (int64_t)nt, 4, 4, d_offq, d_cnt));
             CN_HIP(h, hipMemcpyAsync(p_cnt, d_cnt, 64, hipMemcpyDeviceToHost, h->stream));
@@ -1079,6 +1091,7 @@ int cn_telo_spec_queue(cornetto_accel_t *h, cornetto_asm_t *a, const char *motif
     if (k < 1 || k > MAX_MOTIF || a->tf_n_tiles <= 0 || a->tw_n_words < 0 || a->tw_n_tiles <= 0) return CORNETTO_OK;
     const std::string rc = revcomp(motif), both = motif + rc;
     if (has_border(motif) || has_border(rc)) return CORNETTO_OK;
+    if (!tf_lists_fit_u32(a, k, false)) return CORNETTO_OK;      // (the exact call refuses)
     const size_t nt = (size_t)a->tf_n_tiles;
     uint2 *d_lut = (uint2 *)cn_ws(h, WS_TF_LUT, 256 * sizeof(uint2) + 2 * (size_t)k + 16);
     if (!d_lut || h->tf_lut_key != both || h->tf_lut_ptr != d_lut) return CORNETTO_OK;      // (the tables of this motif are not on the device: the exact call uploads them)

@@ -200,6 +200,8 @@ int cornetto_telobreaks(cornetto_accel_t *h, const int32_t *ctg_len, int32_t n_c
         return cn_fail(h, CORNETTO_E_ARG, "telobreaks: bad argument");
     *out = nullptr;
     *n_out = 0;
+    // (tb_scan counts run starts and run ends with 32-bit sums, exact below 2^32 — scan.hpp —: every run starts where an interval does)
+    if (n_sd > 0xFFFFFFFFll) return cn_fail(h, CORNETTO_E_UNSUPPORTED, "telobreaks: %lld low-complexity intervals, at most 2^32-1 are supported", (long long)n_sd);
     CN_HIP(h, hipSetDevice(h->device));
     cn_timing_begin(h);
     // word layout and tiles

@@ -188,7 +188,11 @@ void cornetto_asm_free(cornetto_accel_t *h, cornetto_asm_t *a);
  * called per record at :103-104.  motif: any length from 1 byte (up to 32 bytes: the fast path; longer ones are compared
  * byte by byte), compared as the reference does (sequence
  * upper-cased, motif not).  hits come out in the reference's print order: by contig, all strand-0 runs by
- * position, then all strand-1 runs. */
+ * position, then all strand-1 runs.
+ * The hits are placed by 32-bit counts, so an assembly that could hold more than 2^32 - 1 entries of one list is refused
+ * by its size alone, whatever it holds (CORNETTO_E_UNSUPPORTED): more than 2^32 - 1 bases for a motif that overlaps a
+ * copy of itself or of its reverse complement (AAAA, ACACA) or is longer than 32 bytes, more than about 2^33 bases for
+ * any other (bases / 2 + contigs x motif length > 2^32 - 1).  cornetto_telo_scan() with hits has the same limit. */
 int cornetto_telofind(cornetto_accel_t *h, const cornetto_asm_t *a, const char *motif,
                       cornetto_hit_t **hits, int64_t *n_hits);
 

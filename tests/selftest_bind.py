@@ -1,0 +1,103 @@
+"""ctypes binding of the cn_selftest_* entry points (cornetto_amd/csrc/selftest.hip, bgrun.hip): the scan primitives of wave.hpp /
+scan.hpp / ivlmerge.hpp on their own, in the DEVELOPMENT build of the library only.  Not part of the C ABI; used by test_gpu_scan.py.
+Every function takes an `Accel(0, dev=True)` (the `dacc` fixture) and numpy arrays."""
+import ctypes as C
+
+import numpy as np
+
+import cornetto_amd
+
+WAVE_INCL_U32, WAVE_INCL_U64, WAVE_INCL_DPP, WAVE_SUM = 0, 1, 2, 3
+E_ARG = -3
+
+_bound = {}
+
+
+def _lib():
+    L = cornetto_amd.lib(dev=True)
+    if id(L) in _bound:
+        return L
+    vp, i32, i64, u32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32
+    sig = {
+        "cn_selftest_wave": [vp, C.c_int, vp, vp, i64],
+        "cn_selftest_block_excl": [vp, C.c_int, C.c_int, vp, vp, vp, i64],
+        "cn_selftest_walk": [vp, vp, i64, i64, i64, u32, u32, C.POINTER(u32)],
+        "cn_selftest_scan_u32": [vp, vp, i64, C.c_int, C.c_int, C.c_int, vp, vp],
+        "cn_selftest_scan_set_epoch": [vp, u32],
+        "cn_selftest_st_set_epoch": [vp, u32],
+        "cn_selftest_merge_fused": [vp, vp, i64, i64, i32, vp, C.POINTER(i64)],
+        "cn_selftest_scan_u64": [vp, vp, i64, C.POINTER(C.c_uint64)],
+    }
+    for name, args in sig.items():
+        fn = getattr(L, name)
+        fn.restype = C.c_int
+        fn.argtypes = args
+    _bound[id(L)] = True
+    return L
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def wave(acc, which, v):
+    """the wave primitive `which` over every 64 values of v (uint64 for WAVE_INCL_U64, else uint32)"""
+    dt = np.uint64 if which == WAVE_INCL_U64 else np.uint32
+    v = np.ascontiguousarray(v, dtype=dt)
+    assert v.size % 64 == 0
+    out = np.empty_like(v)
+    acc._chk(_lib().cn_selftest_wave(acc.h, which, _p(v), _p(out), v.size))
+    return out
+
+
+def block_excl(acc, threads, v):
+    """block_excl<T, threads> per `threads` values of v (uint32 or uint64): (prefixes, totals)"""
+    assert v.dtype in (np.uint32, np.uint64) and v.size % threads == 0
+    v = np.ascontiguousarray(v)
+    pre, tot = np.empty_like(v), np.empty(v.size // threads, dtype=v.dtype)
+    acc._chk(_lib().cn_selftest_block_excl(acc.h, threads, int(v.dtype == np.uint64), _p(v), _p(pre), _p(tot), v.size // threads))
+    return pre, tot
+
+
+def walk_rc(acc, words, stride, tile, epoch, own):
+    """lookback_excl by one wave over `words` (uint64, updated in place; tile t's state is words[t * stride + stride - 1]):
+    (status, excl)"""
+    assert words.dtype == np.uint64 and words.flags.c_contiguous
+    excl = C.c_uint32(0)
+    rc = _lib().cn_selftest_walk(acc.h, _p(words), words.size, stride, tile, epoch, own, C.byref(excl))
+    return rc, int(excl.value)
+
+
+def scan_u32(acc, rec, n, stride, first, m, totals=True):
+    """exclusive_u32_multi over counters first .. first + m - 1 of the n records of `stride` words in rec: (outs [m, n], totals [m] or None)"""
+    rec = np.ascontiguousarray(rec, dtype=np.uint32)
+    assert rec.size == n * stride
+    outs = np.empty((m, n), dtype=np.uint32)
+    tot = np.zeros(m, dtype=np.uint64) if totals else None
+    acc._chk(_lib().cn_selftest_scan_u32(acc.h, _p(rec), n, stride, first, m, _p(outs), _p(tot) if totals else None))
+    return outs, tot
+
+
+def scan_set_epoch(acc, epoch):
+    acc._chk(_lib().cn_selftest_scan_set_epoch(acc.h, epoch))
+
+
+def st_set_epoch(acc, epoch):
+    acc._chk(_lib().cn_selftest_st_set_epoch(acc.h, epoch))
+
+
+def merge_fused(acc, ivls, dist=0, n_cap=None):
+    """cnivl::merge_fused over ivls (IVL_DT, ordered by contig and start)"""
+    ivls = np.ascontiguousarray(ivls, dtype=cornetto_amd.IVL_DT)
+    out = np.empty(ivls.size, dtype=cornetto_amd.IVL_DT)
+    n = C.c_int64(0)
+    acc._chk(_lib().cn_selftest_merge_fused(acc.h, _p(ivls), ivls.size, ivls.size if n_cap is None else n_cap, dist, _p(out), C.byref(n)))
+    return out[:n.value]
+
+
+def scan_u64(acc, v):
+    """the 64-bit scan of bgrun.hip: (exclusive prefixes, total)"""
+    io = np.array(v, dtype=np.uint64)
+    tot = C.c_uint64(0)
+    acc._chk(_lib().cn_selftest_scan_u64(acc.h, _p(io), io.size, C.byref(tot)))
+    return io, int(tot.value)

@@ -50,6 +50,12 @@ def test_the_product_build_has_no_development_switches():
         assert n.encode() in dev, n
     d = cornetto_amd.lib(dev=True)
     assert sorted(d._declared) == declared_symbols()
+    # the self-test entry points of the scan primitives (csrc/selftest.hip, cn_selftest_*: tests/selftest_bind.py) are in the development build
+    # only, under a prefix of their own: not in the header, not in the binding's table, not a byte of them in the product build
+    assert b"cn_selftest_" in dev and b"cn_selftest_" not in prod
+    assert hasattr(d, "cn_selftest_walk") and not hasattr(cornetto_amd.lib(), "cn_selftest_walk")
+    hdr = open(os.path.join(ROOT, "include", "cornetto_accel.h")).read()
+    assert "selftest" not in hdr and "selftest" not in open(os.path.join(ROOT, "cornetto_amd", "__init__.py")).read()
 
 
 def test_no_device_is_a_status_not_a_fallback(lib):

@@ -662,6 +662,46 @@ def test_telofind_lookalike_bytes_vs_oracle(acc):
         assert [tuple(map(int, h)) for h in hits] == exp, motif
 
 
+SCAN_TILE = 4096      # counters per tile of the look-back scan (csrc/scan.hpp): beyond it a launch has np >= 2 tiles
+TF_TILE = 16256       # positions per telofind tile (csrc/telo.hip); a tile never spans two contigs
+
+
+@pytest.mark.parametrize("motif", [b"TTAGGG", b"AAAA"])
+@pytest.mark.parametrize("n_ctg", [4097, 8200])
+def test_telofind_more_tiles_than_one_scan_tile_vs_oracle(acc, n_ctg, motif):
+    """tf_order scans one record of four counters per telofind tile (m = 4, stride 4) and a scan tile holds 4096 of them: 4097 and 8200
+    contigs of 6 to 40 bases are 4097 and 8200 telofind tiles, 2 and 3 scan tiles, so the tickets q np + t, the states from q np and the
+    four offset arrays are used with np >= 2.  The unbordered motif goes through the rows and tf_gather, the bordered one through the
+    second pass at the scanned offsets; telo_scan is the queued launch of the same scan."""
+    rng = np.random.default_rng(n_ctg)
+    units = (motif[::-1].translate(bytes.maketrans(b"ACGT", b"TGCA")), motif)
+    seqs = []
+    for i in range(n_ctg):
+        n = int(rng.integers(6, 41))
+        s = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=n)].copy()
+        if i % 3 != 1:                                            # two of three hold the motif or its reverse complement, once or in a row
+            p = int(rng.integers(0, n - len(motif) + 1))
+            rep = np.frombuffer(units[i % 2] * int(rng.integers(1, 5)), dtype=np.uint8)[: n - p]
+            s[p:p + len(rep)] = rep
+        seqs.append(s)
+    n_tiles = sum((len(s) + TF_TILE - 1) // TF_TILE for s in seqs)           # the tiling rule of telofind_impl
+    assert n_tiles > SCAN_TILE * (n_ctg // SCAN_TILE) >= SCAN_TILE
+    thr = acc.telowin_threshold(0.4, 99.9)
+    exp_h, exp_w = [], []
+    for ci, s in enumerate(seqs):
+        oh = ob.telofind(s, motif)
+        exp_h += [(ci, int(h["strand"]), int(h["start"]), int(h["end"])) for h in oh]
+        exp_w += [(ci, int(w["start"]), int(w["end"]), int(w["car"])) for w in ob.telowin(oh, len(s), thr)]
+    assert len(exp_h) > n_ctg // 2 and exp_h[-1][0] > n_ctg - 10 and {h[1] for h in exp_h} == {0, 1}
+    asm = acc.asm_upload(seqs)
+    hits = acc.telofind(asm, motif)
+    assert [tuple(map(int, h)) for h in hits] == exp_h
+    hits, wins = acc.telo_scan(asm, motif, thr)
+    asm.close()
+    assert [tuple(map(int, h)) for h in hits] == exp_h
+    assert [tuple(map(int, w)) for w in wins] == exp_w
+
+
 # ---------------------------------------------------------------------------------------------------
 # coverage windows
 # ---------------------------------------------------------------------------------------------------
@@ -830,6 +870,66 @@ def test_cov_select_windows_whose_int_sums_wrap(w, inc):
     assert ei.value.status == -5
     cov.close()
     a.close()
+
+
+def test_cov_regs_more_block_tiles_than_one_scan_tile_vs_oracle(acc):
+    """cov_tilescan scans the {depth, mq} sums of the block tiles (m = 2, stride 2) and a scan tile holds 4096 of them.  With -w 64 -i 1 a
+    block tile is 256 positions, so 72 contigs of 16 to 45 kb are more than 8192 block tiles, 3 scan tiles.  Every contig has many block
+    tiles and every window that crosses a seam between two of them takes the offsets of both, mod 2^32: the sums of all depths pass 2^32
+    many times over.  All windows of all contigs against the oracle."""
+    w, inc = 64, 1
+    rng = np.random.default_rng(6)
+    lens = [int(n) for n in rng.integers(16_000, 45_001, size=72)]
+    n_tiles = sum((ob.n_reg(n, w, inc) + w // inc + 1 + 255) // 256 for n in lens)   # the tiling rule of cn_cov_prepare_impl (CB_THREADS = 256)
+    assert n_tiles > 2 * SCAN_TILE
+    depths = [rng.integers(0, 65536, size=n).astype(np.uint16) for n in lens]
+    mqs = [rng.integers(0, 65536, size=n).astype(np.uint16) for n in lens]
+    assert sum(int(d.astype(np.int64).sum()) for d in depths) > 10 << 32
+    cov = acc.cov_upload(depths, mqs)
+    sd, sq, n = acc.cov_prepare(cov, w, inc)
+    assert (sd, sq, n) == (sum(int(d.astype(np.int64).sum()) for d in depths), sum(int(q.astype(np.int64).sum()) for q in mqs), sum(lens))
+    for ci in range(len(lens)):
+        got = acc.cov_regs(cov, ci)
+        exp = ob.get_regs(depths[ci], mqs[ci], w, inc)
+        assert np.array_equal(got, exp.astype(got.dtype)), (ci, lens[ci])
+    cov.close()
+
+
+def test_cov_select_more_window_tiles_than_one_scan_tile_vs_oracle(acc):
+    """cov_order scans the number of selected windows of every window tile, the second word of a record of two (stride 2 from in + 1), and
+    a scan tile holds 4096 of them.  A contig has one window tile per 256 windows and at least one: 9400 contigs of 1 to 4 windows, a tenth of them too short to be taken, and
+    three of 300 to 700 are more than 8192 window tiles, 3 scan tiles.  Both selections, and the packed form, in (contig, window) order
+    against the oracle's windows under the reference's predicate (src/boringbits_main.c:439,467,473-474)."""
+    w, inc = 50, 50
+    rng = np.random.default_rng(7)
+    lens = [int(n) for n in rng.integers(1, 201, size=9400)]
+    for at, n in ((100, 300 * inc + 7), (4500, 700 * inc), (9399, 513 * inc + 1)):
+        lens[at] = n
+    level = lambda n: np.repeat(rng.integers(0, 100, size=n // inc + 1), inc)[:n]      # one level per window: means on both sides of the thresholds
+    depths = [(level(n) + rng.integers(0, 3, size=n)).astype(np.uint16) for n in lens]
+    mqs = [np.minimum(d, level(d.size)).astype(np.uint16) for d in depths]
+    lo, hi, Q, edge, min_len = 30, 70, 0.4, 0, 20
+    cov = acc.cov_upload(depths, mqs)
+    acc.cov_prepare(cov, w, inc)
+    for boring in (False, True):
+        taken = [(n > min_len) if boring else (n >= min_len) for n in lens]
+        n_tiles = sum((ob.n_reg(n, w, inc) + 255) // 256 for n, t in zip(lens, taken) if t)   # the tiling rule of cov_run_windows
+        assert n_tiles > 2 * SCAN_TILE
+        exp = []
+        for ci, (d, q) in enumerate(zip(depths, mqs)):
+            if taken[ci]:
+                for r in ob.get_regs(d, q, w, inc):
+                    st, end, dep, mq = int(r["st"]), int(r["end"]), int(r["depth"]), int(r["mq_depth"])
+                    fun = bool(ob.is_fun(dep, mq, lo, hi, Q))
+                    if (st > edge and end < d.size - edge and not fun) if boring else fun:
+                        exp.append((ci, st, end, dep, mq))
+        assert len(exp) > 2000 and exp[-1][0] > 9390
+        recs = acc.cov_select(cov, lo, hi, Q, edge, min_len, boring)
+        assert [tuple(int(x) for x in r) for r in recs] == exp, boring
+        pk, cf = acc.cov_select_packed(cov, lo, hi, Q, edge, min_len, boring)
+        un = acc.unpack_regs(pk, cf, lens, w)
+        assert [tuple(int(x) for x in r) for r in un] == exp, boring
+    cov.close()
 
 
 def test_sdust_repeatable_with_many_small_chunks(dacc, golden_dir, monkeypatch):

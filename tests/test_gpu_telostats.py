@@ -259,6 +259,28 @@ def test_two_merge_distances_on_one_handle(acc):
     asm.close()
 
 
+def test_more_window_words_than_one_scan_tile(acc):
+    """te_order scans the heads and the tails of every word of 64 windows (m = 2, stride 2), four words per window tile, and a tile of the
+    scan holds 4096 of them.  A record has one window tile per 256 visited windows and at least one: 2100 records of 0.3 to 2.5 kb and three
+    of 2 or 3 window tiles are more than 8192 words, 3 tiles of the scan.  Regions lie in records all along the list, so the places of
+    the heads and tails behind the first tile of the scan decide the rows."""
+    rng = np.random.default_rng(57)
+    records = []
+    for i in range(2100):
+        L = int(rng.integers(300, 2501))
+        n = int(rng.integers(250, 700))
+        blocks = [[], [(0, min(L, n))], [(max(0, L - n), L)], [(0, min(L, n)), (max(0, L - n), L)]][i % 4 if i % 5 else 0]
+        records.append((b"r%d" % i, tc.planted(rng, L, blocks, b"TTAGGG" if i % 2 else b"CCCTAA")))
+    for at, L in ((50, 60000), (1100, 110000), (2099, 52300)):
+        records[at] = (b"long%d" % at, tc.planted(rng, L, [(0, 1500), (51000, 51600), (L - 1200, L)]))
+    n_words = 4 * sum((tc.visited(len(s)) - 1) // 256 + 1 for _, s in records)      # the tiling rule of ensure_tw_layout, 4 words of 64 windows per tile
+    assert n_words > 2 * 4096
+    E = 400
+    exp = tc.expected(records, E=E)
+    assert exp["total"] > 1000 and exp["two"] > 100 and exp["rows"][-1][0] == 2099 and exp["c"][1100] >= 2
+    assert device_rows(acc, records, E=E) == exp["rows"]
+
+
 def test_region_list_sized_too_small(dacc, monkeypatch):
     """the development build takes the size of the region list from CORNETTO_TE_CAP_FORCE: with room for 3 regions the counted total does not
     fit, the placement is rerun with the true size and all rows come back; so they do from the next call, forced small again or not"""

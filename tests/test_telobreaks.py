@@ -116,6 +116,21 @@ def test_telobreaks_rejects_coordinates_outside_the_contig(acc):
 
 
 @pytest.mark.gpu
+def test_telobreaks_refuses_more_intervals_than_its_32_bit_counts_hold(acc):
+    """tb_scan counts run starts with 32-bit sums: 2^32 intervals are refused (CORNETTO_E_UNSUPPORTED = -5) before the
+    first of them is read, so one row stands for them here; 2^32 - 1 would be read, which is why only the refusal is tested"""
+    import ctypes as C
+    lens = np.array([1000], np.int32)
+    sd = np.array([(0, 0, 500)], cornetto_amd.IVL_DT)
+    tel = np.array([(0, 100, 200, 100)], cornetto_amd.TELROW_DT)
+    p, n = C.c_void_p(), C.c_int64(-1)
+    rc = acc.L.cornetto_telobreaks(acc.h, lens.ctypes.data, 1, sd.ctypes.data, 1 << 32, tel.ctypes.data, 1, C.byref(p), C.byref(n))
+    assert rc == -5 and not p.value and n.value == 0
+    assert b"2^32-1" in acc.L.cornetto_accel_last_error(acc.h)
+    assert len(acc.telobreaks(lens, sd, tel)) == 1             # the handle is still good
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("lens_f,sd_f,tel_f,exp", TELOBREAKS_CASES)
 def test_telobreaks_cli_golden(golden_dir, lens_f, sd_f, tel_f, exp):
     p = subprocess.run([cornetto_amd.CLI_PATH, "telobreaks"] + [os.path.join(golden_dir, f) for f in (lens_f, sd_f, tel_f)],
