@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-__all__ = ["lib", "Accel", "AccelError", "HIT_DT", "WIN_DT", "IVL_DT", "TELROW_DT", "khash_str_order", "panel_boring", "REG_DT", "REGREC_DT", "build",
+__all__ = ["lib", "Accel", "AccelError", "HIT_DT", "WIN_DT", "IVL_DT", "TELROW_DT", "HAP_ROW_DT", "khash_str_order", "panel_boring", "REG_DT", "REGREC_DT", "build",
            "LIB_PATH", "CLI_PATH"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -23,6 +23,7 @@ HIT_DT = np.dtype([("ctg", "<i4"), ("strand", "<i4"), ("start", "<i4"), ("end", 
 WIN_DT = np.dtype([("ctg", "<i4"), ("start", "<i4"), ("end", "<i4"), ("car", "<i4")])
 IVL_DT = np.dtype([("ctg", "<i4"), ("start", "<i4"), ("finish", "<i4")])
 TELROW_DT = np.dtype([("ctg", "<i4"), ("start", "<i4"), ("end", "<i4"), ("matched", "<i4")])
+HAP_ROW_DT = np.dtype([("query", "<i4"), ("ctg", "<i4"), ("start", "<i4"), ("finish", "<i4")])
 FQREC_DT = np.dtype([("head", "<i8"), ("seq", "<i8"), ("qual", "<i8"), ("len", "<i4"), ("name_len", "<i4"),
                      ("comment_len", "<i4"), ("keep", "<i4")])
 EMITREC_DT = np.dtype([("ctg", "<i4"), ("rc", "<i4"), ("head", "<i8"), ("head_len", "<i8")])
@@ -48,6 +49,11 @@ class StepOpt(C.Structure):
     """cornetto_step_opt_t (include/cornetto_accel.h)"""
     _fields_ = [("motif", C.c_char_p), ("thr_adj", C.c_double), ("window_size", C.c_int32), ("window_inc", C.c_int32), ("low_cov", C.c_float),
                 ("high_cov", C.c_float), ("low_mq", C.c_float), ("edge_len", C.c_int32), ("min_ctg_len", C.c_int32), ("boring", C.c_int32)]
+
+
+class HapOpt(C.Structure):
+    """cornetto_hap_opt_t (include/cornetto_accel.h)"""
+    _fields_ = [("merge_dist", C.c_int32), ("flank", C.c_int32)]
 
 
 SUMS_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_uint64), C.c_void_p)
@@ -111,6 +117,8 @@ def lib(dev=False):
         "cornetto_panel_defaults": (None, [vp]),
         "cornetto_panel_defaults_recreate": (None, [vp]),
         "cornetto_panel_boring": (C.c_int, [vp, C.c_int32, vp, C.c_int64, vp, C.c_int64, vp, C.POINTER(vp), C.POINTER(C.c_int64)]),
+        "cornetto_hap_defaults": (None, [vp]),
+        "cornetto_hap_fun": (C.c_int, [vp, vp, i32, vp, vp, i32, vp, pp, C.POINTER(i64)]),
         "cornetto_telobreaks": (C.c_int, [vp, vp, C.c_int32, vp, C.c_int64, vp, C.c_int64, C.POINTER(vp), C.POINTER(C.c_int64)]),
         "cornetto_khash_str_order": (C.c_int32, [C.POINTER(C.c_char_p), C.c_int32, vp, vp]),
         "cornetto_fastq_split": (C.c_int, [vp, vp, i64, C.c_int, i32, pp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), pp]),
@@ -487,6 +495,24 @@ class Accel:
         ivls = np.ascontiguousarray(ivls, dtype=IVL_DT)
         p, n = C.c_void_p(), C.c_int64()
         self._chk(self.L.cornetto_ivl_merge(self.h, ivls.ctypes.data, len(ivls), dist, C.byref(p), C.byref(n)))
+        return _take(self.L, p, n.value, IVL_DT)
+
+    def hap_fun(self, lens, rows_per_hap, merge_dist=None, flank=None):
+        """cornetto_hap_fun(): the merged haplotype funbits of scripts/create-hapnetto.sh:40-67.  lens: int32 per contig of the assembly;
+        rows_per_hap: one HAP_ROW_DT array per haplotype (query id, contig index, start, finish), rows in any order -> IVL_DT rows"""
+        lens = np.ascontiguousarray(lens, dtype=np.int32)
+        parts = [np.ascontiguousarray(r, dtype=HAP_ROW_DT).reshape(-1) for r in rows_per_hap]
+        rows = np.concatenate(parts) if parts else np.zeros(0, HAP_ROW_DT)
+        n_rows = np.array([len(r) for r in parts], dtype=np.int64)
+        opt = HapOpt()
+        self.L.cornetto_hap_defaults(C.byref(opt))
+        if merge_dist is not None:
+            opt.merge_dist = merge_dist
+        if flank is not None:
+            opt.flank = flank
+        p, n = C.c_void_p(), C.c_int64()
+        self._chk(self.L.cornetto_hap_fun(self.h, lens.ctypes.data, len(lens), rows.ctypes.data, n_rows.ctypes.data, len(parts), C.byref(opt),
+                                          C.byref(p), C.byref(n)))
         return _take(self.L, p, n.value, IVL_DT)
 
     # ---- telobreaks ------------------------------------------------------------------------------

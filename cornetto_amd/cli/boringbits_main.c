@@ -13,7 +13,13 @@
  * Extension (not in the reference, off by default): `--runs` reads both files as RUN-LENGTH bedgraphs (`name start end value`, one record per
  * run of equal depth: mosdepth per-base output, `bedtools genomecov -bga`) and prints what the same command without it prints on their per-base
  * expansion — a record `name s e v` stands for the lines `name p p+1 v`, p = s .. e-1.  The runs are expanded on the device (cornetto_bgrun_*);
- * everything behind the ingest is the same code.  Without the option such a file is refused as in the reference (end=start+1). */
+ * everything behind the ingest is the same code.  Without the option such a file is refused as in the reference (end=start+1).
+ *
+ * Extension (not in the reference, off by default): `noboringbits --panel ... --hap hap1.paf [--hap hap2.paf ...]` prints the DIPLOID boring bits,
+ * the boringbits.bed of scripts/create-hapnetto.sh:84: the merged haplotype funbits (:40-67; cornetto_hap_fun() on the device, cli_host_hap_fun()
+ * under --accel=no) join the merged windows and the lowQ rows before step 5 (:71).  `--dip FILE` keeps the primary panel on stdout and writes the
+ * diploid one to FILE (one pass over the coverage for both), `--hap-fun FILE` writes hap1_hap2_funbits.bed (:67), `--hap-params D,F` sets the
+ * script's two constants (:50, :58). */
 #include <getopt.h>
 #include <math.h>
 #include <stdlib.h>
@@ -32,6 +38,11 @@ typedef struct {
     int min_ctg_len, edge_len;
 } optp_t;
 
+/* ---- --hap: the haplotype stage of scripts/create-hapnetto.sh:40-67 in front of step 5 of the panel ---- */
+#define HP_MAX 8
+static const char *hp_paf[HP_MAX + 1], *hp_dip = NULL, *hp_fun_out = NULL;
+static int hp_n = 0, hp_par[2] = {1000000, 500};   /* create-hapnetto.sh:50,58 */
+
 static void print_help(FILE *fp, const optp_t *o)
 {
     fprintf(fp, "Usage: cornetto boringbits cov-total.bg -q cov-mq20.bg\n");
@@ -49,6 +60,11 @@ static void print_help(FILE *fp, const optp_t *o)
     fprintf(fp, "   --accel=yes|no             Running on accelerator [yes]\n");
     fprintf(fp, "   --runs                     (extension) the depth files are run-length bedgraphs: name start end value,\n");
     fprintf(fp, "                              one record per run (mosdepth, bedtools genomecov -bga); contigs start at 0, no gaps\n");
+    fprintf(fp, "   --hap FILE                 (extension, with --panel) PAF of a haplotype assembly against the primary one, 1 to %d times:\n", HP_MAX);
+    fprintf(fp, "                              print the diploid boring bits (scripts/create-hapnetto.sh)\n");
+    fprintf(fp, "   --dip FILE                 (extension, with --hap) the diploid boring bits go to FILE, stdout stays the primary panel\n");
+    fprintf(fp, "   --hap-fun FILE             (extension, with --hap) write the merged haplotype funbits to FILE\n");
+    fprintf(fp, "   --hap-params D,F           (extension, with --hap) merge distance and corner flank [%d,%d]\n", hp_par[0], hp_par[1]);
 }
 
 /* ---- --panel: steps 4-9 of scripts/create-cornetto.sh on the merged fun windows ---------------------------------- */
@@ -67,7 +83,61 @@ static int32_t pn_find(const pn_asm_t *a, const int32_t *slots, uint32_t n_slots
     return -1;
 }
 
-static void panel_print(const char *asm_bed, const char *lowq_bed, char **cov_names, int32_t n_cov, const cornetto_ivl_t *fun, int64_t n_fun)
+typedef struct {
+    const pn_asm_t *a;
+    const int32_t *slots;
+    uint32_t n_slots;
+} pn_lookup_t;
+
+static int32_t pn_lookup(const char *name, void *arg)
+{
+    const pn_lookup_t *l = (const pn_lookup_t *)arg;
+    return pn_find(l->a, l->slots, l->n_slots, name);
+}
+
+static void panel_write(FILE *fp, const pn_asm_t *a, const cornetto_ivl_t *v, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) fprintf(fp, "%s\t%d\t%d\n", a->name[v[i].ctg], v[i].start, v[i].finish);
+}
+
+static FILE *panel_fopen_w(const char *path)
+{
+    FILE *fp = fopen(path, "w");
+    if (!fp) {
+        CLI_ERROR("Failed to open %s for writing", path);
+        exit(EXIT_FAILURE);
+    }
+    return fp;
+}
+
+/* the merged haplotype funbits of the --hap files (create-hapnetto.sh:40-67), by assembly index: on the device h, or on the host when h is NULL */
+static void panel_hap_fun(cornetto_accel_t *h, const pn_asm_t *a, const int32_t *slots, uint32_t n_slots, cornetto_ivl_t **fun, int64_t *n_fun)
+{
+    pn_lookup_t look = {a, slots, n_slots};
+    cornetto_hap_row_t *rows = NULL;
+    int64_t n = 0, cap = 0, n_rows[HP_MAX];
+    for (int k = 0; k < hp_n; ++k) {
+        int64_t dropped = 0;
+        n_rows[k] = cli_hap_paf_load(hp_paf[k], pn_lookup, &look, &rows, &n, &cap, &dropped);
+        if (dropped) CLI_WARNING("%s: %lld rows on targets the assembly BED does not have were dropped", hp_paf[k], (long long)dropped);
+        if (n_rows[k] == 0) { /* (the script dies here too: it never creates ${HAP}_tmp.bed, create-hapnetto.sh:47-55) */
+            CLI_ERROR("%s: no row on a contig of the assembly", hp_paf[k]);
+            exit(EXIT_FAILURE);
+        }
+    }
+    if (h) {
+        cornetto_hap_opt_t ho;
+        cornetto_hap_defaults(&ho);
+        ho.merge_dist = hp_par[0];
+        ho.flank = hp_par[1];
+        cli_accel_check(h, cornetto_hap_fun(h, a->len, a->n, rows, n_rows, hp_n, &ho, fun, n_fun), "haplotype stage");
+    } else {
+        cli_host_hap_fun(a->len, a->n, rows, n_rows, hp_n, hp_par[0], hp_par[1], fun, n_fun);
+    }
+    free(rows);
+}
+
+static void panel_print(cornetto_accel_t *h, const char *asm_bed, const char *lowq_bed, char **cov_names, int32_t n_cov, const cornetto_ivl_t *fun, int64_t n_fun)
 {
     char *line = NULL;
     size_t cap = 0;
@@ -144,7 +214,35 @@ static void panel_print(const char *asm_bed, const char *lowq_bed, char **cov_na
     po.extend_gate = pn_par[8] >= 0 ? pn_par[8] : pn_par[3];
     cornetto_ivl_t *out = NULL;
     int64_t n_out = 0;
-    if (cornetto_panel_boring(a.len, a.n, fv, nf, lq, nl, &po, &out, &n_out) != CORNETTO_OK) {
+    if (hp_n > 0) {
+        /* create-hapnetto.sh:71: the haplotype funbits join the merged windows and the lowQ rows in front of step 5 */
+        cornetto_ivl_t *hf = NULL;
+        int64_t n_hf = 0;
+        panel_hap_fun(h, &a, slots, n_slots, &hf, &n_hf);
+        if (hp_fun_out) {
+            FILE *fo = panel_fopen_w(hp_fun_out);
+            panel_write(fo, &a, hf, n_hf);
+            fclose(fo);
+        }
+        cornetto_ivl_t *dv = (cornetto_ivl_t *)cli_xmalloc(((size_t)nf + (size_t)n_hf + 1) * sizeof(*dv));
+        memcpy(dv, fv, (size_t)nf * sizeof(*dv));
+        memcpy(dv + nf, hf, (size_t)n_hf * sizeof(*dv));
+        if (h) cornetto_free(hf);
+        else free(hf);
+        if (cornetto_panel_boring(a.len, a.n, dv, nf + n_hf, lq, nl, &po, &out, &n_out) != CORNETTO_OK) {
+            CLI_ERROR("%s", "panel interval stage failed");
+            exit(EXIT_FAILURE);
+        }
+        free(dv);
+        if (hp_dip) { /* the diploid panel to the file, the primary one below */
+            FILE *fo = panel_fopen_w(hp_dip);
+            panel_write(fo, &a, out, n_out);
+            fclose(fo);
+            cornetto_free(out);
+            out = NULL;
+        }
+    }
+    if (!out && cornetto_panel_boring(a.len, a.n, fv, nf, lq, nl, &po, &out, &n_out) != CORNETTO_OK) {
         CLI_ERROR("%s", "panel interval stage failed");
         exit(EXIT_FAILURE);
     }
@@ -887,7 +985,7 @@ static int host_bits(FILE *ft, FILE *fq, const optp_t *opt, int8_t boring, const
         cornetto_ivl_t *fun = NULL;
         int64_t n_fun = 0;
         cli_host_merge_windows(recs, n_recs, pn_par[0], pn_par[1], &fun, &n_fun);       /* create-cornetto.sh:41-47 */
-        panel_print(panel_bed, lowq_bed, cov.names, cov.n_ctg, fun, n_fun);
+        panel_print(NULL, panel_bed, lowq_bed, cov.names, cov.n_ctg, fun, n_fun);
         free(fun);
     } else {
         t0 = cli_realtime();
@@ -913,6 +1011,8 @@ int boringbits_main(int argc, char *argv[], int8_t boring)
         {"min-ctg-len", required_argument, 0, 'm'}, {"edge-len", required_argument, 0, 'e'},
         {"panel", required_argument, 0, 0},       {"lowq", required_argument, 0, 0},
         {"panel-params", required_argument, 0, 0}, {"runs", no_argument, 0, 0},
+        {"hap", required_argument, 0, 0},         {"dip", required_argument, 0, 0},
+        {"hap-fun", required_argument, 0, 0},     {"hap-params", required_argument, 0, 0},
         {0, 0, 0, 0}};
     optp_t opt = {2500, 50, 0.4f, 2.5f, 0.4f, 1000000, 100000}; /* :540-556 */
     const char *covmq = NULL, *panel_bed = NULL, *lowq_bed = NULL;
@@ -966,6 +1066,22 @@ int boringbits_main(int argc, char *argv[], int8_t boring)
             }
         } else if (c == 0 && li == 21) {
             runs = 1;
+        } else if (c == 0 && li == 22) {
+            if (hp_n == HP_MAX) {
+                CLI_ERROR("--hap: at most %d haplotype PAFs", HP_MAX);
+                exit(EXIT_FAILURE);
+            }
+            hp_paf[hp_n++] = optarg;
+        } else if (c == 0 && li == 23) {
+            hp_dip = optarg;
+        } else if (c == 0 && li == 24) {
+            hp_fun_out = optarg;
+        } else if (c == 0 && li == 25) { /* create-hapnetto.sh:50,58 */
+            char tail;
+            if (sscanf(optarg, "%d,%d%c", &hp_par[0], &hp_par[1], &tail) != 2 || hp_par[0] < 0 || hp_par[1] < 1) {
+                CLI_ERROR("%s", "--hap-params wants two integers: merge-d (>= 0),flank (>= 1)");
+                exit(EXIT_FAILURE);
+            }
         } else if (c == 0 && li == 9) { /* --accel: the seam the reference left (src/boringbits_main.c:627-632) */
             if (strcmp(optarg, "no") == 0 || strcmp(optarg, "n") == 0) {
                 cli_host_set(1);       /* the host path of cli/host_backend.c: sequential parse, window sums, selection */
@@ -987,6 +1103,10 @@ int boringbits_main(int argc, char *argv[], int8_t boring)
     }
     if ((panel_bed || lowq_bed) && (boring || !panel_bed)) {
         CLI_ERROR("%s", "--panel / --lowq: only with noboringbits, and --lowq needs --panel");
+        exit(EXIT_FAILURE);
+    }
+    if ((hp_n > 0 || hp_dip || hp_fun_out) && (boring || !panel_bed || hp_n == 0)) {
+        CLI_ERROR("%s", "--hap / --dip / --hap-fun: only with noboringbits; --hap needs --panel, --dip and --hap-fun need --hap");
         exit(EXIT_FAILURE);
     }
 
@@ -1163,7 +1283,7 @@ int boringbits_main(int argc, char *argv[], int8_t boring)
     print_params(n_ctg, mean_depth, mean_mq, &opt);
 
     if (panel_bed) {
-        panel_print(panel_bed, lowq_bed, names, n_ctg, fun, n_fun);
+        panel_print(h, panel_bed, lowq_bed, names, n_ctg, fun, n_fun);
         cornetto_free(fun);
         for (int32_t i = 0; i < n_ctg; ++i) free(names[i]);
         free(names);

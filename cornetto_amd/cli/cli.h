@@ -191,6 +191,12 @@ typedef struct {
     char tp;
 } cli_paf_t;
 void cli_paf_parse(char *line, cli_paf_t *r);
+/* the rows of one haplotype-to-primary PAF as scripts/create-hapnetto.sh:44,50 uses them (columns 1, 6, 8, 9), appended to a growing array
+ * (n, cap in rows): column 6 goes through find_ctg (name -> index of the assembly BED, -1: not there — the row is dropped and counted),
+ * column 1 becomes an id of this file's own.  Fewer than 9 tab-separated columns, a coordinate that is not a number of 0 .. 2^31-1 or
+ * end <= start: one CLI_ERROR line and exit(EXIT_FAILURE).  -> the rows appended */
+typedef int32_t (*cli_name_find_fn)(const char *name, void *arg);
+int64_t cli_hap_paf_load(const char *path, cli_name_find_fn find_ctg, void *arg, cornetto_hap_row_t **rows, int64_t *n, int64_t *cap, int64_t *n_dropped);
 /* a telomere BED (load_telobed of src/telocontigs.c:59-108 and src/asmstats.c:230-290): sscanf("%s\t%ld\t%ld") per line; fewer than three
  * fields, a negative coordinate or start >= end is exit(EXIT_FAILURE).  on_row(contig name, arg) once per row, in file order. */
 void cli_telobed_load(const char *path, void (*on_row)(const char *ctg, void *arg), void *arg);
@@ -230,6 +236,9 @@ void cli_host_cov_free(cli_host_cov_t *c);
 void cli_host_cov_select(const cli_host_cov_t *c, int w, int inc, int32_t lo, int32_t hi, float low_mq, int32_t edge_len, int32_t min_ctg_len, int boring,
                          cornetto_regrec_t **recs, int64_t *n_recs);
 void cli_host_merge_windows(const cornetto_regrec_t *recs, int64_t n_recs, int32_t dist, int32_t min_len, cornetto_ivl_t **ivls, int64_t *n_ivls);
+/* same contract as cornetto_hap_fun() (rows already checked by cli_hap_paf_load); the result is malloc memory */
+void cli_host_hap_fun(const int32_t *ctg_len, int32_t n_ctg, const cornetto_hap_row_t *rows, const int64_t *n_rows, int32_t n_hap, int32_t merge_dist, int32_t flank,
+                      cornetto_ivl_t **fun, int64_t *n_fun);
 /* same contract as cornetto_telobreaks(); -1: a coordinate outside its contig */
 int cli_host_telobreaks(const int32_t *ctg_len, int32_t n_ctg, const cornetto_ivl_t *sd, int64_t n_sd, const cornetto_telrow_t *tel, int64_t n_tel,
                         cornetto_ivl_t **out, int64_t *n_out);

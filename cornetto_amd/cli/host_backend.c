@@ -741,6 +741,118 @@ void cli_host_merge_windows(const cornetto_regrec_t *recs, int64_t n_recs, int32
     *n_ivls = n;
 }
 
+/* ------------------------------------------------------------------------------------------------ the haplotype stage
+ * scripts/create-hapnetto.sh:40-67 step by step, sequential: per haplotype a loop over its queries (:48-51: the rows of one query sorted by
+ * target and start, merge -d merge_dist), the gaps of every contig (:55), the corners of every block (:58), sort + merge (:61); then the
+ * haplotypes together (:67).  No library call. */
+static int hap_by_query(const void *a_, const void *b_)
+{
+    const cornetto_hap_row_t *a = (const cornetto_hap_row_t *)a_, *b = (const cornetto_hap_row_t *)b_;
+    if (a->query != b->query) return a->query < b->query ? -1 : 1;
+    if (a->ctg != b->ctg) return a->ctg < b->ctg ? -1 : 1;
+    return a->start < b->start ? -1 : a->start > b->start;
+}
+
+static int hap_by_pos(const void *a_, const void *b_)
+{
+    const cornetto_ivl_t *a = (const cornetto_ivl_t *)a_, *b = (const cornetto_ivl_t *)b_;
+    if (a->ctg != b->ctg) return a->ctg < b->ctg ? -1 : 1;
+    return a->start < b->start ? -1 : a->start > b->start;
+}
+
+/* bedtools sort | bedtools merge -d dist, in place -> the number of rows left */
+static int64_t hap_sort_merge(cornetto_ivl_t *v, int64_t n, int32_t dist)
+{
+    qsort(v, (size_t)n, sizeof(*v), hap_by_pos);
+    int64_t m = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (m > 0 && v[m - 1].ctg == v[i].ctg && (int64_t)v[i].start <= (int64_t)v[m - 1].finish + dist) {
+            if (v[i].finish > v[m - 1].finish) v[m - 1].finish = v[i].finish;
+        } else {
+            v[m++] = v[i];
+        }
+    }
+    return m;
+}
+
+typedef struct {
+    cornetto_ivl_t *v;
+    int64_t n, cap;
+} hap_list_t;
+
+static void hap_push(hap_list_t *l, int32_t ctg, int64_t start, int64_t finish)
+{
+    if (l->n == l->cap) {
+        l->cap = l->cap ? l->cap * 2 : 1024;
+        l->v = (cornetto_ivl_t *)cli_xrealloc(l->v, (size_t)l->cap * sizeof(*l->v));
+    }
+    l->v[l->n].ctg = ctg;
+    l->v[l->n].start = (int32_t)start;
+    l->v[l->n].finish = (int32_t)(finish < INT32_MAX ? finish : INT32_MAX);
+    ++l->n;
+}
+
+void cli_host_hap_fun(const int32_t *ctg_len, int32_t n_ctg, const cornetto_hap_row_t *rows, const int64_t *n_rows, int32_t n_hap, int32_t merge_dist, int32_t flank,
+                      cornetto_ivl_t **fun, int64_t *n_fun)
+{
+    hap_list_t all = {NULL, 0, 0};
+    int64_t at = 0;
+    for (int32_t k = 0; k < n_hap; at += n_rows[k], ++k) {
+        const int64_t n = n_rows[k];
+        cornetto_hap_row_t *r = (cornetto_hap_row_t *)cli_xmalloc(((size_t)n + 1) * sizeof(*r));
+        memcpy(r, rows + at, (size_t)n * sizeof(*r));
+        qsort(r, (size_t)n, sizeof(*r), hap_by_query);
+        /* :48-51 every query on its own: its rows as BED intervals on their targets, sort, merge -d */
+        hap_list_t blocks = {NULL, 0, 0};
+        for (int64_t i = 0; i < n;) {
+            int64_t e = i;
+            while (e < n && r[e].query == r[i].query) ++e;
+            cornetto_ivl_t *q = (cornetto_ivl_t *)cli_xmalloc((size_t)(e - i) * sizeof(*q));
+            for (int64_t j = i; j < e; ++j) {
+                q[j - i].ctg = r[j].ctg;
+                q[j - i].start = r[j].start;
+                q[j - i].finish = r[j].finish;
+            }
+            const int64_t m = hap_sort_merge(q, e - i, merge_dist);
+            for (int64_t j = 0; j < m; ++j) hap_push(&blocks, q[j].ctg, q[j].start, q[j].finish);
+            free(q);
+            i = e;
+        }
+        free(r);
+        /* :55 the gaps: every contig minus the blocks on it */
+        hap_list_t tmp2 = {NULL, 0, 0};
+        cornetto_ivl_t *b = (cornetto_ivl_t *)cli_xmalloc(((size_t)blocks.n + 1) * sizeof(*b));
+        memcpy(b, blocks.v, (size_t)blocks.n * sizeof(*b));
+        qsort(b, (size_t)blocks.n, sizeof(*b), hap_by_pos);
+        int64_t j = 0;
+        for (int32_t c = 0; c < n_ctg; ++c) {
+            int64_t pos = 0;
+            const int64_t len = ctg_len[c];
+            for (; j < blocks.n && b[j].ctg == c; ++j) {
+                const int64_t s = b[j].start < len ? b[j].start : len, e = b[j].finish < len ? b[j].finish : len;
+                if (s > pos) hap_push(&tmp2, c, pos, s);
+                if (e > pos) pos = e;
+            }
+            if (pos < len) hap_push(&tmp2, c, pos, len);
+        }
+        free(b);
+        /* :58 the corners of every block, as the awk prints them (the right one is not clamped to the contig) */
+        for (int64_t i = 0; i < blocks.n; ++i) {
+            if (blocks.v[i].start >= flank) hap_push(&tmp2, blocks.v[i].ctg, (int64_t)blocks.v[i].start - flank, (int64_t)blocks.v[i].start + flank);
+            if (blocks.v[i].finish >= flank) hap_push(&tmp2, blocks.v[i].ctg, (int64_t)blocks.v[i].finish - flank, (int64_t)blocks.v[i].finish + flank);
+        }
+        free(blocks.v);
+        /* :61 */
+        const int64_t m = hap_sort_merge(tmp2.v, tmp2.n, 0);
+        for (int64_t i = 0; i < m; ++i) hap_push(&all, tmp2.v[i].ctg, tmp2.v[i].start, tmp2.v[i].finish);
+        free(tmp2.v);
+    }
+    /* :67 */
+    if (!all.v) all.v = (cornetto_ivl_t *)cli_xmalloc(sizeof(*all.v));
+    *n_fun = hap_sort_merge(all.v, all.n, 0);
+    *fun = all.v;
+}
+
 /* ------------------------------------------------------------------------------------------------ telobreaks
  * src/telomere_breaks.c:79-148: one bit per base for the low-complexity intervals, a second bit set for the runs of it
  * that hold a telomere row with its 100-base flanks; the runs of the second set are the output. */

@@ -1,5 +1,5 @@
 /* tables.c — the small text tables the assembly sub-commands share: a string -> index map, the PAF line of src/pafrec.c:43-98 (fixasm,
- * asmstats), the telomere BED of src/telocontigs.c:59-108 / src/asmstats.c:230-290 (telocontigs, asmstats) and the natural name order of
+ * asmstats), the four PAF columns of scripts/create-hapnetto.sh:44,50 (noboringbits --hap), the telomere BED of src/telocontigs.c:59-108 / src/asmstats.c:230-290 (telocontigs, asmstats) and the natural name order of
  * src/misc.c:139-171 (asmstats). */
 #include <errno.h>
 #include <stdlib.h>
@@ -117,6 +117,95 @@ void cli_paf_parse(char *line, cli_paf_t *r)
         if (!strcmp(p, "tp:A:P")) r->tp = 'P';
         else if (!strcmp(p, "tp:A:S")) r->tp = 'S';
     }
+}
+
+/* ---------------------------------------------------------------- the PAF columns of the haplotype stage (scripts/create-hapnetto.sh:44,50)
+ * The script cuts fields 1-10 and uses 1, 6, 8 and 9: the first nine tab-separated fields must be there, the rest of the line (cg:Z: tags of
+ * megabytes) is not looked at.  getline() takes lines of any length. */
+static int32_t hap_coord(const char *s, const char *e, const char *path, long long line_no, int col)
+{
+    long long v = 0;
+    const char *p = s;
+    const int neg = p < e && *p == '-';
+    if (neg) ++p;
+    if (p == e) v = -1;
+    for (; p < e && v >= 0; ++p) {
+        if (*p < '0' || *p > '9') v = -1;
+        else if ((v = v * 10 + (*p - '0')) > 0x7fffffffLL) v = -2;
+    }
+    if (v == -1) {
+        CLI_ERROR("%s: line %lld: column %d is not a number", path, line_no, col);
+        exit(EXIT_FAILURE);
+    }
+    if (v == -2 || neg) {
+        CLI_ERROR("%s: line %lld: column %d is negative or beyond 2^31-1", path, line_no, col);
+        exit(EXIT_FAILURE);
+    }
+    return (int32_t)v;
+}
+
+int64_t cli_hap_paf_load(const char *path, cli_name_find_fn find_ctg, void *arg, cornetto_hap_row_t **rows, int64_t *n, int64_t *cap, int64_t *n_dropped)
+{
+    FILE *fp = fopen(path, "r");
+    if (!fp) {
+        CLI_ERROR("Failed to open %s : No such file or directory.", path);
+        exit(EXIT_FAILURE);
+    }
+    cli_map_t queries;
+    memset(&queries, 0, sizeof(queries));
+    char *line = NULL;
+    size_t lcap = 0;
+    ssize_t got;
+    long long line_no = 0;
+    int64_t n_used = 0;
+    *n_dropped = 0;
+    while ((got = getline(&line, &lcap, fp)) != -1) {
+        ++line_no;
+        while (got > 0 && (line[got - 1] == '\n' || line[got - 1] == '\r')) --got;
+        if (got == 0) continue; /* (an empty line: neither cut nor awk makes a row of it) */
+        const char *fs[9], *fe[9];
+        int nf = 0;
+        const char *p = line, *end = line + got;
+        while (nf < 9) {
+            const char *t = (const char *)memchr(p, '\t', (size_t)(end - p));
+            fs[nf] = p;
+            fe[nf] = t ? t : end;
+            ++nf;
+            if (!t) break;
+            p = t + 1;
+        }
+        if (nf < 9) {
+            CLI_ERROR("%s: line %lld: a PAF line has at least 9 tab-separated columns. Had %d.", path, line_no, nf);
+            exit(EXIT_FAILURE);
+        }
+        const int32_t start = hap_coord(fs[7], fe[7], path, line_no, 8), finish = hap_coord(fs[8], fe[8], path, line_no, 9);
+        if (finish <= start) {
+            CLI_ERROR("%s: line %lld: target end %d is not behind target start %d", path, line_no, finish, start);
+            exit(EXIT_FAILURE);
+        }
+        line[fe[5] - line] = 0;
+        const int32_t ctg = find_ctg(fs[5], arg);
+        if (ctg < 0) { /* a target the assembly BED does not have: `bedtools subtract -a assembly` never sees it */
+            ++*n_dropped;
+            continue;
+        }
+        int added;
+        const int32_t q = cli_map_put(&queries, fs[0], (size_t)(fe[0] - fs[0]), &added);
+        if (*n == *cap) {
+            *cap = *cap ? *cap * 2 : 1024;
+            *rows = (cornetto_hap_row_t *)cli_xrealloc(*rows, (size_t)*cap * sizeof(**rows));
+        }
+        cornetto_hap_row_t *r = &(*rows)[(*n)++];
+        r->query = q;
+        r->ctg = ctg;
+        r->start = start;
+        r->finish = finish;
+        ++n_used;
+    }
+    free(line);
+    fclose(fp);
+    cli_map_free(&queries);
+    return n_used;
 }
 
 /* ---------------------------------------------------------------- the telomere BED */

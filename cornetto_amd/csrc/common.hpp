@@ -155,6 +155,7 @@ enum {   // device workspace slots
     WS_FQ_TEXT, WS_FQ_CNT, WS_FQ_NL, WS_FQ_RECS, WS_FQ_ENDS, WS_FQ_SRC,
     WS_SCAN, WS_STITCH,
     WS_TE_WORDS, WS_TE_REG, WS_TE_ROWS, WS_TE_CNT,
+    WS_SORT, WS_HAP_ROWS, WS_HAP_BLOCKS, WS_HAP_FUN,
     WS_COUNT
 };
 static_assert(WS_COUNT <= 64, "cornetto_accel::dev has 64 slots");

@@ -1,4 +1,4 @@
-// selftest.hip — the scan primitives of wave.hpp / scan.hpp / ivlmerge.hpp behind plain C entry points, DEVELOPMENT BUILD ONLY (-DCN_DEV:
+// selftest.hip — the scan primitives of wave.hpp / scan.hpp / ivlmerge.hpp and the radix sort of sort.hpp behind plain C entry points, DEVELOPMENT BUILD ONLY (-DCN_DEV:
 // the product object of this file is empty, tests/test_abi.py looks for the prefix in both libraries).  tests/test_gpu_scan.py
 // (tests/selftest_bind.py) compares them with numpy on inputs the product entry points cannot produce: prepared tile states for the
 // look-back, full-range values, strides and counter sets at more than one tile, epochs next to the wrap.  Not part of the C ABI: no
@@ -7,6 +7,7 @@
 #include "common.hpp"
 #include "ivlmerge.hpp"
 #include "scan.hpp"
+#include "sort.hpp"
 #include "wave.hpp"
 
 namespace {
@@ -198,6 +199,32 @@ int cn_selftest_merge_fused(cornetto_accel_t *h, const cornetto_ivl_t *in, int64
     CN_HIP(h, hipMemcpyAsync(out, d_out.p, (size_t)small[1] * sizeof(cornetto_ivl_t), hipMemcpyDeviceToHost, h->stream));
     CN_HIP(h, hipStreamSynchronize(h->stream));
     *n_out = (int64_t)small[1];
+    return CORNETTO_OK;
+}
+
+// cnsort::pairs_u64 itself, on the handle's own WS_SORT (and WS_SCAN, through the table's scan): the n pairs (keys[i], vals[i]) -> the same
+// pairs in ascending key order, equal keys in input order; key_bits: the digits that are looked at (the keys are 0 above)
+int cn_selftest_sort_pairs(cornetto_accel_t *h, const unsigned long long *keys, const uint32_t *vals, int64_t n, int key_bits, unsigned long long *out_keys,
+                           uint32_t *out_vals)
+{
+    if (!h || n < 0 || n > ((int64_t)1 << 28) || (n > 0 && (!keys || !vals || !out_keys || !out_vals)) || key_bits < 1 || key_bits > 64)
+        return cn_fail(h, CORNETTO_E_ARG, "selftest_sort_pairs: bad argument");
+    if (n == 0) return CORNETTO_OK;
+    CN_HIP(h, hipSetDevice(h->device));
+    cn_timing_begin(h);
+    DevBuf d_k, d_v;
+    if (d_k.alloc((size_t)n * 8) != hipSuccess || d_v.alloc((size_t)n * 4) != hipSuccess) return cn_fail(h, CORNETTO_E_NOMEM, "selftest: device allocation failed");
+    uint8_t *ws = (uint8_t *)cn_ws(h, WS_SORT, cnsort::ws_bytes(n));
+    if (!ws) return cn_fail(h, CORNETTO_E_NOMEM, "selftest: workspace allocation failed");
+    CN_HIP(h, hipMemcpyAsync(d_k.p, keys, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+    CN_HIP(h, hipMemcpyAsync(d_v.p, vals, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+    u64 *r_k = nullptr;
+    uint32_t *r_v = nullptr;
+    CN_TRY(cnsort::pairs_u64(h, "selftest_sort", d_k.as<u64>(), d_v.as<uint32_t>(), n, ws, key_bits, &r_k, &r_v));
+    CN_HIP(h, hipMemcpyAsync(out_keys, r_k, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream));
+    CN_HIP(h, hipMemcpyAsync(out_vals, r_v, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+    CN_HIP(h, hipStreamSynchronize(h->stream));
+    cn_timing_end(h);
     return CORNETTO_OK;
 }
 

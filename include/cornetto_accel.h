@@ -579,6 +579,37 @@ int cornetto_panel_boring(const int32_t *ctg_len, int32_t n_ctg, const cornetto_
                           int64_t n_lowq, const cornetto_panel_opt_t *opt, cornetto_ivl_t **boring, int64_t *n_boring);
 
 /* ---------------------------------------------------------------------------------------------------
+ * haplotype stage of the diploid panel — scripts/create-hapnetto.sh:40-67 without cut / sort / awk / bedtools, on the
+ * device (parity with bedtools itself is unpinned: see cornetto_amd/csrc/hap.hip)
+ * ------------------------------------------------------------------------------------------------- */
+
+/* one line of a haplotype-to-primary PAF as the script reads it (scripts/create-hapnetto.sh:44,50): column 1 as an id that
+ * is only compared for equality within its haplotype, column 6 as an index into the assembly BED, columns 8 and 9 */
+typedef struct {
+    int32_t query, ctg, start, finish;
+} cornetto_hap_row_t;
+
+typedef struct {
+    int32_t merge_dist; /* bedtools merge -d within one (query, target) pair (1000000, scripts/create-hapnetto.sh:50) */
+    int32_t flank;      /* half width of a corner (500, scripts/create-hapnetto.sh:58) */
+} cornetto_hap_opt_t;
+void cornetto_hap_defaults(cornetto_hap_opt_t *opt);
+
+/* The merged haplotype funbits (hap1_hap2_funbits.bed, scripts/create-hapnetto.sh:67) of n_hap haplotypes.  rows: the rows of
+ * haplotype 0, then of haplotype 1, ... in any order, n_rows[k] of haplotype k.  Per haplotype: blocks = merge -d merge_dist of
+ * the rows of every (query, target) pair on its own (scripts/create-hapnetto.sh:48-51; a gap of exactly merge_dist merges);
+ * gaps = every contig [0, len) minus the union of the blocks on it (scripts/create-hapnetto.sh:55; a contig without blocks is
+ * one gap, a contig of length 0 none); corners = [start - flank, start + flank) of every block with start >= flank and
+ * [finish - flank, finish + flank) of every block with finish >= flank, not clamped to the contig, capped at INT32_MAX
+ * (scripts/create-hapnetto.sh:58); funbits = merge of gaps and corners, overlapping and book-ended rows merge
+ * (scripts/create-hapnetto.sh:61).  Result: the merge of the funbits of all haplotypes (scripts/create-hapnetto.sh:67),
+ * by (ctg, start); it joins the `fun` rows of cornetto_panel_boring() (scripts/create-hapnetto.sh:71).  A haplotype without
+ * rows yields every contig as a gap.  CORNETTO_E_ARG: ctg outside [0, n_ctg), finish <= start, start < 0, a negative count or
+ * length.  Release fun with cornetto_free(). */
+int cornetto_hap_fun(cornetto_accel_t *h, const int32_t *ctg_len, int32_t n_ctg, const cornetto_hap_row_t *rows, const int64_t *n_rows,
+                     int32_t n_hap, const cornetto_hap_opt_t *opt, cornetto_ivl_t **fun, int64_t *n_fun);
+
+/* ---------------------------------------------------------------------------------------------------
  * telobreaks — src/telomere_breaks.c:47-172 (the consumer of the sdust BED and the telofind TSV)
  * ------------------------------------------------------------------------------------------------- */
 
