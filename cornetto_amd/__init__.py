@@ -120,6 +120,8 @@ def lib(dev=False):
         "cornetto_hap_defaults": (None, [vp]),
         "cornetto_hap_fun": (C.c_int, [vp, vp, i32, vp, vp, i32, vp, pp, C.POINTER(i64)]),
         "cornetto_telobreaks": (C.c_int, [vp, vp, C.c_int32, vp, C.c_int64, vp, C.c_int64, C.POINTER(vp), C.POINTER(C.c_int64)]),
+        "cornetto_telo_breaks": (C.c_int, [vp, vp, cp, i32, i32, pp, C.POINTER(i64)]),
+        "cornetto_telobreaks_ivl": (C.c_int, [vp, vp, C.c_int32, vp, C.c_int64, vp, C.c_int64, C.POINTER(vp), C.POINTER(C.c_int64)]),
         "cornetto_khash_str_order": (C.c_int32, [C.POINTER(C.c_char_p), C.c_int32, vp, vp]),
         "cornetto_fastq_split": (C.c_int, [vp, vp, i64, C.c_int, i32, pp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), pp]),
         "cornetto_fasta_split": (C.c_int, [vp, vp, i64, C.c_int, pp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), pp]),
@@ -525,6 +527,24 @@ class Accel:
         p, n = C.c_void_p(), C.c_int64()
         self._chk(self.L.cornetto_telobreaks(self.h, ctg_len.ctypes.data, len(ctg_len), sd.ctypes.data, len(sd), tel.ctypes.data, len(tel),
                                              C.byref(p), C.byref(n)))
+        return _take(self.L, p, n.value, IVL_DT)
+
+    def telobreaks_ivl(self, ctg_len, sd, tel):
+        """cornetto_telobreaks_ivl(): the same records by the interval rule, for an sd list sorted by (ctg, start) whose starts lie beyond
+        the previous finish (what sdust prints); AccelError -3 for a list that is not"""
+        ctg_len = np.ascontiguousarray(ctg_len, dtype=np.int32)
+        sd = np.ascontiguousarray(sd, dtype=IVL_DT)
+        tel = np.ascontiguousarray(tel, dtype=TELROW_DT)
+        p, n = C.c_void_p(), C.c_int64()
+        self._chk(self.L.cornetto_telobreaks_ivl(self.h, ctg_len.ctypes.data, len(ctg_len), sd.ctypes.data, len(sd), tel.ctypes.data, len(tel),
+                                                 C.byref(p), C.byref(n)))
+        return _take(self.L, p, n.value, IVL_DT)
+
+    def telo_breaks(self, asm, motif=b"TTAGGG", T=20, W=64):
+        """cornetto_telo_breaks(): sdust(T, W), telofind(motif) and the interval rule on a resident assembly -> IVL_DT rows, the records of
+        telobreaks() on the two lists; neither list leaves the device"""
+        p, n = C.c_void_p(), C.c_int64()
+        self._chk(self.L.cornetto_telo_breaks(self.h, asm.ptr, motif, T, W, C.byref(p), C.byref(n)))
         return _take(self.L, p, n.value, IVL_DT)
 
     # ---- coverage --------------------------------------------------------------------------------

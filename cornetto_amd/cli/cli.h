@@ -215,6 +215,9 @@ void cli_host_telowin(const cornetto_hit_t *hits, int64_t n_hits, const int32_t 
  * sequential bedtools merge -d and the intersection with the record's end intervals (scripts/telostats.sh:35-47) */
 void cli_host_telo_ends(const uint8_t *seq, int64_t len, const char *motif, double thr_adj, int32_t merge_dist, int32_t ends, int32_t ctg,
                         cornetto_ivl_t **rows, int64_t *n_rows, int64_t *cap_rows);
+/* the rows of cornetto_telo_breaks() for ONE record (their ctg = `ctg`), appended to a growing array (n, cap in rows): the host sdust, the
+ * host telofind and the interval rule (test/realtest.sh:65-69 on one record); -1: -w / -t out of range */
+int cli_host_telo_breaks(const uint8_t *seq, int64_t len, const char *motif, int T, int W, int32_t ctg, cornetto_ivl_t **rows, int64_t *n_rows, int64_t *cap_rows);
 /* get_depths(): what the two bedgraphs hold; exits with the reference's messages on malformed input */
 typedef struct {
     int32_t n_ctg;

@@ -853,6 +853,52 @@ void cli_host_hap_fun(const int32_t *ctg_len, int32_t n_ctg, const cornetto_hap_
     *fun = all.v;
 }
 
+/* ------------------------------------------------------------------------------------------------ telostats --breaks
+ * test/realtest.sh:65-69 on one record: sdust, telofind, then src/telomere_breaks.c:95-148 as the rule on intervals of
+ * csrc/telobreaks_ivl.hip — what sdust prints is sorted with every start beyond the previous finish (src/sdust/sdust.c:88-102), so the
+ * intervals are the runs of the reference's bitset.  Sequential: one binary search per run of at least 24 bases. */
+int cli_host_telo_breaks(const uint8_t *seq, int64_t len, const char *motif, int T, int W, int32_t ctg, cornetto_ivl_t **rows, int64_t *n_rows, int64_t *cap_rows)
+{
+    cornetto_ivl_t *sd = NULL;
+    cornetto_hit_t *hits = NULL;
+    int64_t n_sd = 0, cap_sd = 0, n_hits = 0, cap_hits = 0;
+    if (cli_host_sdust(seq, len, T, W, 0, &sd, &n_sd, &cap_sd) != 0) return -1;
+    cli_host_telofind(seq, len, motif, 0, &hits, &n_hits, &cap_hits);
+    uint8_t *mark = (uint8_t *)cli_xmalloc((size_t)n_sd + 1);
+    memset(mark, 0, (size_t)n_sd + 1);
+    for (int64_t i = 1; i < n_sd; ++i)
+        if (sd[i].start <= sd[i - 1].finish) {
+            CLI_ERROR("sdust intervals %d-%d and %d-%d of one record touch or are out of order", sd[i - 1].start, sd[i - 1].finish, sd[i].start, sd[i].finish);
+            exit(EXIT_FAILURE);
+        }
+    for (int64_t i = 0; i < n_hits; ++i) {
+        if (hits[i].end - hits[i].start < 24) continue;                               /* MIN_TEL, :10,:98 */
+        const int64_t a = hits[i].start - 100 < 0 ? 0 : hits[i].start - 100, b = (int64_t)hits[i].end + 100 > len ? len : hits[i].end + 100;   /* :102-103 */
+        int64_t lo = 0, hi = n_sd;                                                    /* lo = intervals that start at or before a */
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) / 2;
+            if (sd[mid].start <= a) lo = mid + 1;
+            else hi = mid;
+        }
+        if (lo > 0 && (sd[lo - 1].finish > len ? len : sd[lo - 1].finish) >= b) mark[lo - 1] = 1;
+    }
+    for (int64_t i = 0; i < n_sd; ++i) {
+        if (!mark[i]) continue;
+        if (*n_rows == *cap_rows) {
+            *cap_rows = *cap_rows ? *cap_rows * 2 : 64;
+            *rows = (cornetto_ivl_t *)cli_xrealloc(*rows, (size_t)*cap_rows * sizeof(**rows));
+        }
+        (*rows)[*n_rows].ctg = ctg;
+        (*rows)[*n_rows].start = sd[i].start - 1 < 0 ? 0 : sd[i].start - 1;           /* :139-142 */
+        (*rows)[*n_rows].finish = (int32_t)((sd[i].finish > len ? len : sd[i].finish) - 1);
+        ++*n_rows;
+    }
+    free(mark);
+    free(sd);
+    free(hits);
+    return 0;
+}
+
 /* ------------------------------------------------------------------------------------------------ telobreaks
  * src/telomere_breaks.c:79-148: one bit per base for the low-complexity intervals, a second bit set for the runs of it
  * that hold a telomere row with its 100-base flanks; the runs of the second set are the output. */

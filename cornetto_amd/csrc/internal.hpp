@@ -48,3 +48,16 @@ int cn_telo_scan_impl(cornetto_accel_t *h, const cornetto_asm_t *a, const char *
 // window layout of the assembly (cornetto_asm::d_tw_boff, d_tw_tiles, tw_n_tiles): written by tf_scan beside its matches for a motif without
 // a border, built from the runs otherwise.  Synchronises.  telostats.hip turns it into the merged regions at the contig ends.
 int cn_telo_marks_impl(cornetto_accel_t *h, const cornetto_asm_t *a, const char *motif, const unsigned long long **d_marks);
+
+// The two lists cornetto_telo_breaks (telobreaks_ivl.hip) reads, left on the device: neither is copied to the host, only its count is.  Both
+// take the plain synchronous route of their public entry points (no one-go form, no estimate of the last call) without the timing
+// bracket, and both synchronise.  A list stays valid until the next sdust / telofind call on the handle.
+//   cn_sdust_list_impl   cornetto_sdust_asm(): the stitched intervals, by contig, then by start (sdust.hip's workspace); nullptr when n is 0
+//   cn_telo_hits_impl    cornetto_telofind(): the runs of both strands (telo.hip's workspace).  A motif with a border (AAAA, ACACA) or of
+//                        more than 32 bytes keeps its present route — the greedy runs are collected on the host — and the finished list is
+//                        uploaded again: such motifs are not what a telomere search runs with.
+// A cornetto_sdust_asm_begin() nobody finished is finished and dropped first; that runs a timing bracket of its own, so a caller with a
+// bracket calls cn_sdust_drop_pending() BEFORE it opens it (cn_sdust_list_impl() drops too: a no-op then).
+void cn_sdust_drop_pending(cornetto_accel_t *h);
+int cn_sdust_list_impl(cornetto_accel_t *h, const cornetto_asm_t *a, int32_t T, int32_t W, const cornetto_ivl_t **d_ivls, int64_t *n_ivls);
+int cn_telo_hits_impl(cornetto_accel_t *h, const cornetto_asm_t *a, const char *motif, const cornetto_hit_t **d_hits, int64_t *n_hits);

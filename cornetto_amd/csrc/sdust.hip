@@ -34,6 +34,7 @@
 #include "scan.hpp"
 #include "tiles.hpp"
 #include "ivlmerge.hpp"
+#include "internal.hpp"
 
 namespace {
 
@@ -1639,8 +1640,11 @@ int sd_one_go_finish(cornetto_accel_t *h, cornetto_asm_t *a, cornetto_ivl_t *of,
 
 // phase 0: the whole call.  phase 1 (cornetto_sdust_asm_begin): queue it in one go if the last call for this table left its counts behind and
 // return without waiting (h->sd_pend.state = 1); nothing queued if not (state 0); or, where the one-go form could not be set up after the main
-// kernel was launched, the whole call (state 2, the result kept in h->sd_pend)
-int sdust_asm_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, int32_t T, int32_t W, cornetto_ivl_t **ivls, int64_t *n_ivls, const int phase)
+// kernel was launched, the whole call (state 2, the result kept in h->sd_pend).
+// d_keep (cn_sdust_list_impl, phase 0 only): the stitched list stays on the device — *d_keep points at it, *n_ivls is its count, ivls is not
+// used, nothing but the count is copied —, the call takes the plain route (no one-go form) and leaves the timing bracket to its caller
+int sdust_asm_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, int32_t T, int32_t W, cornetto_ivl_t **ivls, int64_t *n_ivls, const int phase,
+                   const cornetto_ivl_t **d_keep = nullptr)
 {
     // CORNETTO_SDUST_TRACE=1: host-side time stamps of the call's phases on stderr (development aid)
     static const bool trace = CN_DEV_INT("CORNETTO_SDUST_TRACE", 0) != 0;
@@ -1652,16 +1656,17 @@ int sdust_asm_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, int32_t T, i
         clock_gettime(CLOCK_MONOTONIC, &t);
         fprintf(stderr, "[sdust trace] %-22s %8.3f ms\n", what, (t.tv_sec - ts0.tv_sec) * 1e3 + (t.tv_nsec - ts0.tv_nsec) * 1e-6);
     };
-    if (!h || !a_in || !ivls || !n_ivls) return cn_fail(h, CORNETTO_E_ARG, "sdust: bad argument");
+    if (!h || !a_in || (!ivls && !d_keep) || !n_ivls) return cn_fail(h, CORNETTO_E_ARG, "sdust: bad argument");
     cornetto_asm_t *a = const_cast<cornetto_asm_t *>(a_in);   // only the cached chunk table is touched
-    *ivls = nullptr;
+    if (d_keep) *d_keep = nullptr;
+    else *ivls = nullptr;
     *n_ivls = 0;
     // (W - 2 words in the window.  Up to 64: sdust_w64; up to 255: the older kernel with byte counters in LDS; up to 1024: the
     // same with its state in global memory.  Beyond, the reference's own 32-bit products r * l (:115,:118) overflow.)
     if (W < 3 || W > 1026) return cn_fail(h, CORNETTO_E_UNSUPPORTED, "sdust: -w %d outside 3..1026 (the reference crashes below 3)", W);
     if (T < 0 || T > (1 << 20)) return cn_fail(h, CORNETTO_E_UNSUPPORTED, "sdust: -t %d outside 0..2^20", T);
     CN_HIP(h, hipSetDevice(h->device));
-    cn_timing_begin(h);
+    if (!d_keep) cn_timing_begin(h);
 
     // waves the chip holds at once (LDS-bound: 19 per CU), once per handle
     const int variant0 = CN_DEV_INT("CORNETTO_SDUST_VARIANT", 0);
@@ -1881,7 +1886,7 @@ int sdust_asm_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, int32_t T, i
         // the rest of the call in one go (below) needs the counts the last call for this table left behind: ONE predicate for the early-out of
         // cornetto_sdust_asm_begin() here and for the one-go form itself
         const int64_t est_key = key * 131 + T * 1031 + W;
-        const bool one_go = w64_path && sift_on && !want_stats && a->sd_est_key == est_key && a->sd_est_rows >= 0 && CN_DEV_INT("CORNETTO_SDUST_FUSED", 1);
+        const bool one_go = w64_path && sift_on && !want_stats && a->sd_est_key == est_key && a->sd_est_rows >= 0 && !d_keep && CN_DEV_INT("CORNETTO_SDUST_FUSED", 1);
         if (phase == 1 && !one_go)
             return CORNETTO_OK;                        // (nothing to size the rest of the call by: cornetto_sdust_asm_end runs it)
         for (int attempt = 0; attempt < 4; ++attempt) {
@@ -2230,8 +2235,10 @@ int sdust_asm_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, int32_t T, i
             cap = ovf;   // rerun with room for the densest chunk: results are never truncated
         }
         if (tot > 0x7fffffffull) return cn_fail(h, CORNETTO_E_UNSUPPORTED, "sdust: %llu intervals", tot);
-        o = (cornetto_ivl_t *)cn_result_alloc((tot ? tot : 1) * sizeof(cornetto_ivl_t));
-        if (!o) return cn_fail(h, CORNETTO_E_NOMEM, "sdust: host allocation failed");
+        if (!d_keep) {
+            o = (cornetto_ivl_t *)cn_result_alloc((tot ? tot : 1) * sizeof(cornetto_ivl_t));
+            if (!o) return cn_fail(h, CORNETTO_E_NOMEM, "sdust: host allocation failed");
+        }
         stamp("result buffer");
         if (tot > 0) {
             // dense list + stitched list + the merge's scratch.  The chunk lists are merged with the reference's own rule
@@ -2245,13 +2252,14 @@ int sdust_asm_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, int32_t T, i
             CN_TRY(cnivl::merge(h, "sdust_stitch", d_dst, (int64_t)n, 0, ws, d_st, d_tot + 9));
             stamp("gather+stitch queued");
             if (trace) { (void)hipStreamSynchronize(h->stream); stamp("gather+stitch done (trace only)"); }
-            if (hipMemcpyAsync(o, d_st, n * sizeof(cornetto_ivl_t), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+            if ((!d_keep && hipMemcpyAsync(o, d_st, n * sizeof(cornetto_ivl_t), hipMemcpyDeviceToHost, h->stream) != hipSuccess) ||
                 hipMemcpyAsync(p_tot, d_tot + 9, 8, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
                 hipStreamSynchronize(h->stream) != hipSuccess) {
                 cornetto_free(o);
                 return cn_fail(h, CORNETTO_E_HIP, "sdust: stitch / copy back failed");
             }
             n_out = (int64_t)p_tot[0];                 // only the first n_out entries of o are meaningful
+            if (d_keep) *d_keep = d_st;
             stamp("results on the host");
         }
         if (sift_on) {                                 // what the next call for this table may count on
@@ -2259,6 +2267,10 @@ int sdust_asm_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, int32_t T, i
             a->sd_est_rows = (int64_t)tot;
             a->sd_est_out = n_out;
         }
+    }
+    if (d_keep) {
+        *n_ivls = n_out;
+        return CORNETTO_OK;
     }
     cn_timing_end(h);
     if (!o) {
@@ -2273,17 +2285,32 @@ int sdust_asm_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, int32_t T, i
     *n_ivls = n_out;
     return CORNETTO_OK;
 }
+
+// a _begin nobody finished: its result is dropped
+void sd_drop_pending(cornetto_accel_t *h)
+{
+    if (!h || h->sd_pend.state == 0) return;
+    cornetto_ivl_t *dv = nullptr;
+    int64_t dn = 0;
+    if (cornetto_sdust_asm_end(h, reinterpret_cast<const cornetto_asm_t *>(h->sd_pend.a), h->sd_pend.T, h->sd_pend.W, &dv, &dn) == CORNETTO_OK) cornetto_free(dv);
+}
 }  // namespace
+
+// ---- the stitched list left on the device (internal.hpp): what cornetto_telo_breaks reads ----
+void cn_sdust_drop_pending(cornetto_accel_t *h) { sd_drop_pending(h); }
+
+int cn_sdust_list_impl(cornetto_accel_t *h, const cornetto_asm_t *a, int32_t T, int32_t W, const cornetto_ivl_t **d_ivls, int64_t *n_ivls)
+{
+    if (!d_ivls) return cn_fail(h, CORNETTO_E_ARG, "sdust: bad argument");
+    sd_drop_pending(h);
+    return sdust_asm_impl(h, a, T, W, nullptr, n_ivls, 0, d_ivls);
+}
 
 extern "C" {
 
 int cornetto_sdust_asm(cornetto_accel_t *h, const cornetto_asm_t *a_in, int32_t T, int32_t W, cornetto_ivl_t **ivls, int64_t *n_ivls)
 {
-    if (h && h->sd_pend.state != 0) {                  // a _begin nobody finished: its result is dropped
-        cornetto_ivl_t *dv = nullptr;
-        int64_t dn = 0;
-        if (cornetto_sdust_asm_end(h, reinterpret_cast<const cornetto_asm_t *>(h->sd_pend.a), h->sd_pend.T, h->sd_pend.W, &dv, &dn) == CORNETTO_OK) cornetto_free(dv);
-    }
+    sd_drop_pending(h);
     return sdust_asm_impl(h, a_in, T, W, ivls, n_ivls, 0);
 }
 

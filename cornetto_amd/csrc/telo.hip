@@ -685,10 +685,13 @@ int ensure_tw_layout(cornetto_accel_t *h, cornetto_asm_t *am)
     return CORNETTO_OK;
 }
 
+// d_keep (cn_telo_hits_impl; hits is nullptr then): the runs stay on the device — *d_keep points at them, *n_hits is their count, the list is
+// not copied to the host
 int telofind_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, const char *motif_c, cornetto_hit_t **hits,
-                  int64_t *n_hits, bool want_bitmap_req, unsigned long long **bitmap_out, bool *bitmap_valid)
+                  int64_t *n_hits, bool want_bitmap_req, unsigned long long **bitmap_out, bool *bitmap_valid, const cornetto_hit_t **d_keep = nullptr)
 {
-    if (!h || !a_in || !motif_c) return cn_fail(h, CORNETTO_E_ARG, "telofind: bad argument");
+    if (!h || !a_in || !motif_c || (d_keep && (hits || !n_hits))) return cn_fail(h, CORNETTO_E_ARG, "telofind: bad argument");
+    const bool want_hits = hits || d_keep;
     cornetto_asm_t *a = const_cast<cornetto_asm_t *>(a_in);   // only the cached tile table is touched
     const std::string motif(motif_c);
     const int k = (int)motif.size();
@@ -696,7 +699,9 @@ int telofind_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, const char *m
     if (k > (1 << 20)) return cn_fail(h, CORNETTO_E_UNSUPPORTED, "telofind: motif of %d bytes; at most %d are supported", k, 1 << 20);
     const bool long_motif = k > MAX_MOTIF;   // beyond the 32-bit automaton: compared byte by byte (tf_scan<-1>), runs by the sequential rule
     CN_HIP(h, hipSetDevice(h->device));
-    if (hits) { *hits = nullptr; *n_hits = 0; }
+    if (hits) *hits = nullptr;
+    if (d_keep) *d_keep = nullptr;
+    if (want_hits) *n_hits = 0;
     if (bitmap_valid) *bitmap_valid = false;
     a->tf_est_cnt[0] = a->tf_est_cnt[1] = a->tf_est_cnt[2] = a->tf_est_cnt[3] = -1;
 
@@ -796,7 +801,7 @@ int telofind_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, const char *m
         A.bases = a->d_bases; A.ctg_off = a->d_off; A.ctg_len = a->d_len; A.tiles = a->d_tf_tiles; A.lut = d_lut; A.k = k; A.mot = d_mot;
         A.bordered = bordered ? 1 : 0; A.bitmap = want_bitmap ? d_bitmap : nullptr; A.bm_off = a->d_tw_boff; A.tile_cnt = d_tc; A.ovf = d_ovf; A.n_tiles = (int64_t)nt;
         // pass 1: single pass into fixed rows (unbordered motif, hits wanted), or counts only
-        const bool rows_mode = hits && !bordered;
+        const bool rows_mode = want_hits && !bordered;
         int32_t *d_rows[4] = {nullptr, nullptr, nullptr, nullptr};
         if (rows_mode) {
             for (int q = 0; q < 4; ++q) {
@@ -812,7 +817,7 @@ int telofind_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, const char *m
         CN_TRY(launch(A));
         CN_TRACE("telofind: tf_scan queued");
         if (bitmap_valid) *bitmap_valid = want_bitmap;
-        if (hits) {
+        if (want_hits) {
             if (!tf_lists_fit_u32(a, k, bordered))
                 return cn_fail(h, CORNETTO_E_UNSUPPORTED, "telofind: %lld bases can hold more than 2^32-1 list entries of this motif", (long long)a->total);
             // place of every tile in the dense, contig-ordered lists + list totals
@@ -856,8 +861,10 @@ int telofind_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, const char *m
                 uint32_t *d_coff = (uint32_t *)cn_ws(h, WS_TF_ROFF, 4 * ((size_t)a->n + 1) * 4);
                 cornetto_hit_t *d_hits = (cornetto_hit_t *)cn_ws(h, WS_TF_HITS, tot * sizeof(cornetto_hit_t));
                 if (!d_coff || !d_hits) return cn_fail(h, CORNETTO_E_NOMEM, "telofind: workspace allocation failed");
-                out = (cornetto_hit_t *)cn_result_alloc((tot ? tot : 1) * sizeof(cornetto_hit_t));
-                if (!out) return cn_fail(h, CORNETTO_E_NOMEM, "telofind: host allocation failed");
+                if (!d_keep) {
+                    out = (cornetto_hit_t *)cn_result_alloc((tot ? tot : 1) * sizeof(cornetto_hit_t));
+                    if (!out) return cn_fail(h, CORNETTO_E_NOMEM, "telofind: host allocation failed");
+                }
                 hipEvent_t ea = cn_event(h), eb = cn_event(h);
                 (void)hipEventRecord(ea, h->stream);
                 tf_ctgoff<<<dim3((unsigned)((a->n + 256) / 256)), dim3(256), 0, h->stream>>>(a->d_tf_ct0, a->n, (int64_t)nt, d_offq[0], d_offq[1], d_offq[2],
@@ -869,7 +876,7 @@ int telofind_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, const char *m
                 h->recs.push_back(cornetto_accel::Rec{"tf_pair", ea, eb});
                 bool ok = hipGetLastError() == hipSuccess;
                 ok = ok && hipMemcpyAsync(p_cnt, d_cnt, 64, hipMemcpyDeviceToHost, h->stream) == hipSuccess;
-                if (tot) ok = ok && cn_result_d2h(h, out, d_hits, tot * sizeof(cornetto_hit_t)) == hipSuccess;
+                if (tot && !d_keep) ok = ok && cn_result_d2h(h, out, d_hits, tot * sizeof(cornetto_hit_t)) == hipSuccess;
                 ok = ok && hipStreamSynchronize(h->stream) == hipSuccess;
                 if (!ok || (p_cnt[4] >> 32) != 0) {
                     cn_result_quiesce(h);
@@ -877,6 +884,7 @@ int telofind_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, const char *m
                     return cn_fail(h, CORNETTO_E_HIP, "telofind: pairing run heads with tails failed%s", ok ? " (a contig has unequal heads and tails)" : "");
                 }
                 n_out = (int64_t)tot;
+                if (d_keep && tot) *d_keep = d_hits;
                 for (int q = 0; q < 4; ++q) a->tf_est_cnt[q] = (int64_t)cnt[q];
             } else {
                 // sequential greedy rule on the device over the dense match lists
@@ -914,6 +922,14 @@ int telofind_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, const char *m
                             const int2 r = runs[run_off[2 * c + strand] + i];
                             out[n_out++] = cornetto_hit_t{c, strand, r.x, r.y};
                         }
+                if (d_keep) {                          // (internal.hpp: a motif with a border keeps this route, the finished list goes up again)
+                    cornetto_hit_t *d_hits = n_out ? (cornetto_hit_t *)cn_ws(h, WS_TF_HITS, (size_t)n_out * sizeof(cornetto_hit_t)) : nullptr;
+                    const hipError_t e = !n_out ? hipSuccess : !d_hits ? hipErrorOutOfMemory : hipMemcpy(d_hits, out, (size_t)n_out * sizeof(cornetto_hit_t), hipMemcpyHostToDevice);
+                    free(out);
+                    out = nullptr;
+                    if (e != hipSuccess) return cn_fail(h, CORNETTO_E_HIP, "telofind: uploading the runs -> %s", hipGetErrorString(e));
+                    *d_keep = d_hits;
+                }
             }
         } else {
             CN_HIP(h, hipStreamSynchronize(h->stream));   // `lut` is a local
@@ -927,6 +943,7 @@ int telofind_impl(cornetto_accel_t *h, const cornetto_asm_t *a_in, const char *m
         *hits = out;
         *n_hits = n_out;
     }
+    if (d_keep) *n_hits = n_out;
     return CORNETTO_OK;
 }
 
@@ -1030,6 +1047,13 @@ int cn_telo_scan_impl(cornetto_accel_t *h, const cornetto_asm_t *a, const char *
         *n_hits = nh;
     }
     return rc;
+}
+
+// ---- the runs left on the device (internal.hpp): what cornetto_telo_breaks reads ----
+int cn_telo_hits_impl(cornetto_accel_t *h, const cornetto_asm_t *a, const char *motif, const cornetto_hit_t **d_hits, int64_t *n_hits)
+{
+    if (!d_hits || !n_hits) return cn_fail(h, CORNETTO_E_ARG, "telofind: bad argument");
+    return telofind_impl(h, a, motif, nullptr, n_hits, false, nullptr, nullptr, d_hits);
 }
 
 // ---- the marks alone (internal.hpp): what cornetto_telo_ends builds its regions from ----------------------------------------------------

@@ -632,6 +632,28 @@ typedef struct {
 int cornetto_telobreaks(cornetto_accel_t *h, const int32_t *ctg_len, int32_t n_ctg, const cornetto_ivl_t *sd, int64_t n_sd,
                         const cornetto_telrow_t *tel, int64_t n_tel, cornetto_ivl_t **out, int64_t *n_out);
 
+/* The telomere breaks of a resident assembly: sdust(T, W) and telofind(motif) on the device, then the interval rule below; equal to
+ * cornetto_sdust_asm() + cornetto_telofind() + cornetto_telobreaks() on their results (rows {ctg, start, end, end - start}), i.e. to
+ * the chain of test/realtest.sh:65-69 (`cornetto sdust` and `cornetto telofind` each write a file, `cornetto telobreaks` reads both and
+ * the table of lengths) with src/telomere_breaks.c:79-148 behind it.
+ * Neither list leaves the device.  T, W: the limits of cornetto_sdust_asm(); motif: those of cornetto_telofind().  rows by contig, then
+ * by start; release them with cornetto_free(). */
+int cornetto_telo_breaks(cornetto_accel_t *h, const cornetto_asm_t *a, const char *motif, int32_t T, int32_t W,
+                         cornetto_ivl_t **rows, int64_t *n_rows);
+
+/* The same kernels on explicit lists: src/telomere_breaks.c:95-148 as a rule on intervals instead of two bitsets.  sd must be sorted by
+ * (ctg, start), with every start greater than the previous finish in the same contig (what sdust prints: src/sdust/sdust.c:88-102 merges
+ * an interval that starts at or before the previous finish); a list that is not, or that names a contig outside [0, n_ctg):
+ * CORNETTO_E_ARG, checked on the device.  finish may exceed the contig length (it is cut there, as cornetto_telobreaks() cuts it).  Then a
+ * row of tel with matched >= 24 marks the one interval that contains [max(0, start - 100), min(L, end + 100)), and every marked interval
+ * comes out once as {ctg, max(start - 1, 0), min(finish, L) - 1}: the records of cornetto_telobreaks() in the same order.  Rows of a
+ * contig outside [0, n_ctg) are dropped; a row outside its contig or with start >= end, or an interval with a negative start:
+ * CORNETTO_E_FORMAT, as there.  As there, too: with an empty sd or an empty tel nothing can be marked, and the rows are not looked at
+ * (an empty sd: no kernel runs; an empty tel: sd is still checked); an interval that starts at or beyond its contig's end is empty after
+ * the cut and marks nothing, without an error.  At most 2^31 - 1 intervals.  Release out with cornetto_free(). */
+int cornetto_telobreaks_ivl(cornetto_accel_t *h, const int32_t *ctg_len, int32_t n_ctg, const cornetto_ivl_t *sd, int64_t n_sd,
+                            const cornetto_telrow_t *tel, int64_t n_tel, cornetto_ivl_t **out, int64_t *n_out);
+
 /* Host helper: the iteration order of the reference's khash string map (klib khash 0.2.8, src/khash.h) after
  * kh_put() of names[0..n) in that order — the order in which telobreaks prints its contigs (:133).  slot[i] = dense
  * id of the distinct key of names[i] (ids in order of first appearance); order[k] = id in the k-th occupied bucket.
