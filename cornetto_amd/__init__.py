@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-__all__ = ["lib", "Accel", "AccelError", "HIT_DT", "WIN_DT", "IVL_DT", "TELROW_DT", "HAP_ROW_DT", "khash_str_order", "panel_boring", "REG_DT", "REGREC_DT", "build",
+__all__ = ["lib", "Accel", "bgzf_scan", "BGZF_DT", "AccelError", "HIT_DT", "WIN_DT", "IVL_DT", "TELROW_DT", "HAP_ROW_DT", "khash_str_order", "panel_boring", "REG_DT", "REGREC_DT", "build",
            "LIB_PATH", "CLI_PATH"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -28,6 +28,7 @@ FQREC_DT = np.dtype([("head", "<i8"), ("seq", "<i8"), ("qual", "<i8"), ("len", "
                      ("comment_len", "<i4"), ("keep", "<i4")])
 EMITREC_DT = np.dtype([("ctg", "<i4"), ("rc", "<i4"), ("head", "<i8"), ("head_len", "<i8")])
 FAREC_DT = np.dtype([("head", "<i8"), ("len", "<i8"), ("name_len", "<i4"), ("pad", "<i4")])
+BGZF_DT = np.dtype([("src", "<i8"), ("dst", "<i8"), ("n_src", "<i4"), ("n_dst", "<i4"), ("crc", "<u4"), ("pad", "<i4")])
 REG_DT = np.dtype([("st", "<i4"), ("end", "<i4"), ("depth", "<i4"), ("mq_depth", "<i4")])
 REGREC_DT = np.dtype([("ctg", "<i4"), ("st", "<i4"), ("end", "<i4"), ("depth", "<i4"), ("mq_depth", "<i4")])
 REGPK_DT = np.dtype([("st", "<i4"), ("depth", "<u2"), ("mq_depth", "<u2")])
@@ -130,6 +131,9 @@ def lib(dev=False):
         "cornetto_text_put": (C.c_int, [vp, vp, vp, i64, i64, C.c_int]),
         "cornetto_text_wait": (C.c_int, [vp, vp, C.c_int]),
         "cornetto_fasta_split_text": (C.c_int, [vp, vp, i64, C.c_int, pp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32), pp]),
+        "cornetto_bgzf_scan": (C.c_int, [vp, i64, i64, C.POINTER(i64), vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]),
+        "cornetto_text_inflate": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(i64)]),
+        "cornetto_text_gather": (C.c_int, [vp, vp, vp, vp, i64, vp]),
         "cornetto_emit_open": (C.c_int, [vp, vp, vp, i64, vp, i64, pp, C.POINTER(i64)]),
         "cornetto_emit_get": (C.c_int, [vp, vp, vp, i64, i64, C.c_int]),
         "cornetto_emit_wait": (C.c_int, [vp, vp, C.c_int]),
@@ -191,6 +195,20 @@ def lib(dev=False):
     L._declared = sorted(sig)
     _libs[path] = L
     return L
+
+
+def bgzf_scan(data, file_off=0, dst=0):
+    """cornetto_bgzf_scan() over `data`, the bytes at file_off of a BGZF file -> (blocks BGZF_DT: the members that lie wholly inside `data`, with
+    dst counting on from `dst`; file offset to resume at; True if what begins there is not a BGZF member).  Host only."""
+    L = lib()
+    keep = np.frombuffer(bytes(data), dtype=np.uint8)
+    blocks = np.zeros(keep.size // 26 + 1, dtype=BGZF_DT)
+    d, nb, resume, broken = C.c_int64(dst), C.c_int64(), C.c_int64(), C.c_int32()
+    rc = L.cornetto_bgzf_scan(keep.ctypes.data if keep.size else None, keep.size, file_off, C.byref(d), blocks.ctypes.data, blocks.size, C.byref(nb),
+                              C.byref(resume), C.byref(broken))
+    if rc != 0:
+        raise AccelError(rc, L.cornetto_accel_strerror(rc).decode())
+    return blocks[:nb.value].copy(), resume.value, bool(broken.value)
 
 
 class _Owner:
@@ -410,6 +428,90 @@ class Accel:
         recs = _take(self.L, p, cnt.value, FAREC_DT)
         res = _Resident(self, seqs, self.L.cornetto_asm_free, recs["len"]) if want_seqs else None
         return recs, used.value, bool(plain.value), res
+
+    def _text_from(self, data, cap=None):
+        """`data` as a device text (cornetto_text_open + one cornetto_text_put from a pinned slab)"""
+        keep = np.frombuffer(bytes(data), dtype=np.uint8)
+        t = C.c_void_p()
+        self._chk(self.L.cornetto_text_open(self.h, max(1, keep.size, cap or 0), C.byref(t)))
+        if keep.size:
+            pin = self.L.cornetto_pinned_alloc(keep.size)
+            try:
+                C.memmove(pin, keep.ctypes.data, keep.size)
+                self._chk(self.L.cornetto_text_put(self.h, t, pin, keep.size, 0, 0))
+                self._chk(self.L.cornetto_text_wait(self.h, t, 0))
+            except Exception:
+                self.L.cornetto_text_free(self.h, t)
+                raise
+            finally:
+                self.L.cornetto_pinned_free(pin)
+        return t
+
+    def _text_bytes(self, t, n):
+        """the first n bytes of a device text (cornetto_text_gather of one range)"""
+        out = C.create_string_buffer(max(1, n))
+        at, ln = np.array([0], dtype=np.int64), np.array([n], dtype=np.int32)
+        self._chk(self.L.cornetto_text_gather(self.h, t, at.ctypes.data, ln.ctypes.data, 1, out))
+        return out.raw[:n]
+
+    def bgzf_inflate(self, data, blocks=None, fill=None):
+        """the BGZF file `data` inflated on the device (cornetto_text_inflate) -> (bytes of the inflated text, first_bad: -1 or the index of the
+        first block that is not what its footer says).  blocks: BGZF_DT, by default what bgzf_scan(data) gives (ValueError unless the chain
+        ends with the data); fill: the inflated text and 256 bytes behind it are filled with this byte value beforehand and returned.  The status of the call is kept in
+        self.last_status (0, or CORNETTO_E_FORMAT = -6 when first_bad >= 0), its kernel times in self.inflate_timing; every other status raises."""
+        if blocks is None:
+            blocks, resume, broken = bgzf_scan(data)
+            if broken or resume != len(data):
+                raise ValueError("not a BGZF chain: it ends at byte %d of %d" % (resume, len(data)))
+        blocks = np.ascontiguousarray(blocks, dtype=BGZF_DT)
+        total = (int((blocks["dst"] + blocks["n_dst"]).max()) if blocks.size else 0) + (256 if fill is not None else 0)
+        comp = self._text_from(data)
+        out = None
+        try:
+            out = self._text_from(bytes([fill]) * total if fill is not None else b"", cap=total)
+            bad = C.c_int64(-1)
+            rc = self.L.cornetto_text_inflate(self.h, comp, out, blocks.ctypes.data, blocks.size, C.byref(bad))
+            self.last_status, self.inflate_timing = rc, self.last_timing()      # (the copy below is a compute call of its own)
+            if rc != 0 and not (rc == -6 and bad.value >= 0):
+                self._chk(rc)
+            return self._text_bytes(out, total), bad.value
+        finally:
+            self.L.cornetto_text_free(self.h, comp)
+            if out is not None:
+                self.L.cornetto_text_free(self.h, out)
+
+    def fasta_split_bgzf(self, data, final=True, want_seqs=False, want_names=False):
+        """fasta_split_slabs() of the text the BGZF file `data` holds: inflated on the device (cornetto_text_inflate), framed there
+        (cornetto_fasta_split_text) -> (records, consumed, plain, resident sequences or None); want_names: a fifth item, the records' names
+        fetched with cornetto_text_gather.  A block that is not what its footer says raises AccelError (status -6)."""
+        blocks, resume, broken = bgzf_scan(data)
+        if broken or resume != len(data):
+            raise ValueError("not a BGZF chain: it ends at byte %d of %d" % (resume, len(data)))
+        total = int(blocks["n_dst"].sum())
+        comp = self._text_from(data)
+        out = None
+        try:
+            out = self._text_from(b"", cap=total)
+            bad = C.c_int64(-1)
+            self._chk(self.L.cornetto_text_inflate(self.h, comp, out, blocks.ctypes.data, blocks.size, C.byref(bad)))
+            p, cnt, used, plain, seqs = C.c_void_p(), C.c_int64(), C.c_int64(), C.c_int32(), C.c_void_p()
+            self._chk(self.L.cornetto_fasta_split_text(self.h, out, total, 1 if final else 0, C.byref(p), C.byref(cnt), C.byref(used), C.byref(plain),
+                                                       C.byref(seqs) if want_seqs else None))
+            recs = _take(self.L, p, cnt.value, FAREC_DT)
+            res = _Resident(self, seqs, self.L.cornetto_asm_free, recs["len"]) if want_seqs else None
+            names = None
+            if want_names:
+                at = np.ascontiguousarray(recs["head"] + 1, dtype=np.int64)
+                ln = np.ascontiguousarray(recs["name_len"], dtype=np.int32)
+                buf = C.create_string_buffer(max(1, int(ln.sum())))
+                self._chk(self.L.cornetto_text_gather(self.h, out, at.ctypes.data, ln.ctypes.data, len(recs), buf))
+                ends = np.cumsum(ln)
+                names = [buf.raw[int(e - k):int(e)] for e, k in zip(ends, ln)]
+        finally:
+            self.L.cornetto_text_free(self.h, comp)
+            if out is not None:
+                self.L.cornetto_text_free(self.h, out)
+        return (recs, used.value, bool(plain.value), res) + ((names,) if want_names else ())
 
     # ---- telofind / telowin ----------------------------------------------------------------------
     def telofind(self, asm, motif=b"TTAGGG"):

@@ -3,8 +3,9 @@
  * cornetto_fastq_split) and handed to the caller's scan in input order.  Anything else — wrapped FASTQ, stray lines, a FASTQ record inside a FASTA
  * file, the reference's error cases — is read by the sequential reader (cli/fastx.c) from the first byte the device was not sure about: the
  * output is kseq's either way (src/kseq.h:184-224 as called at src/find_telomere.c:101, src/sdust/sdust.c:196).
- * stream_run() looks at the input once and picks one of three sources:
+ * stream_run() looks at the input once and picks one of four sources:
  *   stream_whole_fasta()  an uncompressed regular FASTA file as ONE text on the device;
+ *   stream_bgzf_fasta()   a BGZF-compressed (bgzip) regular FASTA file: uploaded as it is, inflated on the device into ONE text;
  *   stream_pieces()       gzip, stdin, FASTQ, CORNETTO_CLI_WHOLE=0 or CORNETTO_FASTQ_PIECE (bytes per piece): pinned pieces, framed one by one;
  *   stream_sequential()   what those two leave, or everything (CORNETTO_FASTQ_SPLIT=host, text that begins with neither '>' nor '@'). */
 #include <errno.h>
@@ -12,6 +13,7 @@
 #include <pthread.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
 #include <zlib.h>
@@ -121,6 +123,7 @@ static int64_t piece_fill(stream_t *s, char *dst, int64_t want)
     }
     if (got < 0) {
         CLI_ERROR("reading %s failed", s->path);
+        if (!s->h) cli_accel_open_cancel();    /* (exit() beside a device that is still being opened on the helper thread ends with SIGSEGV) */
         exit(EXIT_FAILURE);
     }
     return got;
@@ -230,6 +233,8 @@ typedef struct {
     int64_t next;
     pthread_mutex_t mu;
     pthread_cond_t cv;
+    pthread_t pin_th;
+    int pin_started;
 } whole_ring_t;
 
 static void *whole_reader(void *p)
@@ -273,6 +278,35 @@ static void *whole_pinner(void *p)
         if (!m) return NULL;
     }
     return NULL;
+}
+
+/* the ring for a text of `cap` bytes read from fd -> the number of reader threads.  `w` must stay where it is until whole_ring_close() */
+static int whole_ring_open(whole_ring_t *w, int fd, int64_t cap)
+{
+    memset(w, 0, sizeof(*w));
+    pthread_mutex_init(&w->mu, NULL);
+    pthread_cond_init(&w->cv, NULL);
+    w->fd = fd;
+    /* sixteen slabs of 8 MiB: a reader thread per slab in flight copies from the page cache at 4-6 GB/s, the copy queues take ~45 GB/s */
+    w->slab = 8LL << 20;
+    if (cap < w->slab * WHOLE_SLOTS) w->slab = ((cap + WHOLE_SLOTS - 1) / WHOLE_SLOTS + 65535) & ~65535LL;   /* (a small file: a small ring) */
+    w->n_slots = (int)((cap + w->slab - 1) / w->slab);
+    if (w->n_slots > WHOLE_SLOTS) w->n_slots = WHOLE_SLOTS;
+    if (w->n_slots < 1) w->n_slots = 1;
+    w->pin_started = pthread_create(&w->pin_th, NULL, whole_pinner, w) == 0;
+    if (!w->pin_started) whole_pinner(w);
+    int n_thr = getenv("CORNETTO_READ_THREADS") ? read_threads() : 16;
+    if (n_thr > w->n_slots) n_thr = w->n_slots;
+    return n_thr;
+}
+
+/* the slabs go to the stream (stream_release()) */
+static void whole_ring_close(stream_t *s, whole_ring_t *w)
+{
+    if (w->pin_started) pthread_join(w->pin_th, NULL);   /* (it uses `w`) */
+    for (int sl = 0; sl < w->n_slots; ++sl) s->pinned[s->n_pinned++] = w->ring[sl];
+    pthread_mutex_destroy(&w->mu);
+    pthread_cond_destroy(&w->cv);
 }
 
 /* bytes [off, off + n) of the file through the ring into the device text */
@@ -348,21 +382,7 @@ static int64_t stream_whole_fasta(stream_t *s)
     cli_accel_check(s->h, cornetto_text_open(s->h, cap, &s->text), "allocating the text on the GPU");
     TRACE("device text allocated");
     whole_ring_t w;
-    memset(&w, 0, sizeof(w));
-    pthread_mutex_init(&w.mu, NULL);
-    pthread_cond_init(&w.cv, NULL);
-    w.fd = s->raw_fd;
-    /* sixteen slabs of 8 MiB: a reader thread per slab in flight copies from the page cache at 4-6 GB/s, the copy queues take ~45 GB/s */
-    w.slab = 8LL << 20;
-    if (cap < w.slab * WHOLE_SLOTS) w.slab = ((cap + WHOLE_SLOTS - 1) / WHOLE_SLOTS + 65535) & ~65535LL;   /* (a small file: a small ring) */
-    w.n_slots = (int)((cap + w.slab - 1) / w.slab);
-    if (w.n_slots > WHOLE_SLOTS) w.n_slots = WHOLE_SLOTS;
-    if (w.n_slots < 1) w.n_slots = 1;
-    pthread_t pin_th;
-    const int pin_started = pthread_create(&pin_th, NULL, whole_pinner, &w) == 0;
-    if (!pin_started) whole_pinner(&w);
-    int n_thr = getenv("CORNETTO_READ_THREADS") ? read_threads() : 16;
-    if (n_thr > w.n_slots) n_thr = w.n_slots;
+    const int n_thr = whole_ring_open(&w, s->raw_fd, cap);
     int64_t off = 0;
     int plain_all = 1;
     while (off < size && plain_all) {
@@ -391,11 +411,176 @@ static int64_t stream_whole_fasta(stream_t *s)
         else if (used == 0 && !final) plain_all = 0; /* one record longer than a text (2^32 bytes): the sequential reader reports it as the reference's reader would */
         else if (final) off = size;
     }
-    if (pin_started) pthread_join(pin_th, NULL);   /* (it uses `w`, which lives on this stack) */
-    for (int sl = 0; sl < w.n_slots; ++sl) s->pinned[s->n_pinned++] = w.ring[sl];
-    pthread_mutex_destroy(&w.mu);
-    pthread_cond_destroy(&w.cv);
+    whole_ring_close(s, &w);
     return off;
+}
+
+/* ---------------------------------------------------------------- a BGZF-compressed FASTA FILE, inflated on the device
+ * gzread() inflates on one host thread (the reference's reader: src/find_telomere.c:96, src/kseq.h:234) while the device waits.  bgzip output is
+ * a chain of independent gzip members of at most 64 KiB with their sizes in the headers: the file goes to the device as it is, through the same
+ * slab ring; a host thread walks the chain beside the upload (cornetto_bgzf_scan over the mapped file: no system call per block); the device
+ * inflates a block per wave and checks every CRC-32 (cornetto_text_inflate); the text is framed and scanned ONCE as an uncompressed file's is,
+ * and the record names come back packed (cornetto_text_gather).  Nothing is printed before the whole text has inflated cleanly: whatever is
+ * not a sound BGZF chain of a text that fits goes through the piece loop from its first byte, as it always did. */
+typedef struct {
+    int fd;
+    int64_t size;
+    cornetto_bgzf_block_t *blocks;
+    int64_t n, total;
+    const char *why;          /* NULL: the chain ends with the file */
+} bgzf_walk_t;
+
+static void *bgzf_walker(void *p)
+{
+    bgzf_walk_t *k = (bgzf_walk_t *)p;
+    void *m = mmap(NULL, (size_t)k->size, PROT_READ, MAP_PRIVATE, k->fd, 0);
+    if (m == MAP_FAILED) { k->why = "the file cannot be mapped"; return NULL; }
+    int64_t cap = k->size / 16384 + 64, at = 0;
+    k->blocks = (cornetto_bgzf_block_t *)cli_xmalloc((size_t)cap * sizeof(*k->blocks));
+    while (at < k->size) {
+        if (k->n == cap) {
+            cap *= 2;
+            cornetto_bgzf_block_t *nb = (cornetto_bgzf_block_t *)cli_xmalloc((size_t)cap * sizeof(*nb));
+            memcpy(nb, k->blocks, (size_t)k->n * sizeof(*nb));
+            free(k->blocks);
+            k->blocks = nb;
+        }
+        int64_t got = 0, resume = at;
+        int32_t broken = 0;
+        if (cornetto_bgzf_scan((const uint8_t *)m + at, k->size - at, at, &k->total, k->blocks + k->n, cap - k->n, &got, &resume, &broken) != CORNETTO_OK) broken = 1;
+        k->n += got;
+        at = resume;
+        if (broken) { k->why = "the chain breaks"; break; }
+        if (got == 0) { k->why = "bytes behind the last block"; break; }
+    }
+    munmap(m, (size_t)k->size);
+    return NULL;
+}
+
+static void bgzf_fallback(stream_t *s, const char *why)
+{
+    if (s->trace) fprintf(stderr, "[cli trace] bgzf: fallback (%s)\n", why);
+}
+
+/* is what begins the file a BGZF member? */
+static int bgzf_first_member(int fd)
+{
+    uint8_t *head = (uint8_t *)cli_xmalloc(65536);
+    const int64_t have = cli_read_at(fd, (char *)head, 65536, 0, NULL);
+    cornetto_bgzf_block_t b;
+    int64_t dst = 0, n = 0, resume = 0;
+    int32_t broken = 0;
+    const int ok = have > 0 && cornetto_bgzf_scan(head, have, 0, &dst, &b, 1, &n, &resume, &broken) == CORNETTO_OK && n == 1;
+    free(head);
+    return ok;
+}
+
+/* the names of the text's records, packed on the device and copied once -> r[0 .. nrec), its names in *names_out */
+static cli_recname_t *bgzf_names(stream_t *s, const cornetto_farec_t *recs, int64_t nrec, char **names_out)
+{
+    cli_recname_t *r = (cli_recname_t *)cli_xmalloc(((size_t)nrec + 1) * sizeof(*r));
+    int64_t *at = (int64_t *)cli_xmalloc(((size_t)nrec + 1) * sizeof(*at)), name_bytes = 0;
+    int32_t *len = (int32_t *)cli_xmalloc(((size_t)nrec + 1) * sizeof(*len));
+    for (int64_t i = 0; i < nrec; ++i) {
+        at[i] = recs[i].head + 1;
+        len[i] = recs[i].name_len;
+        name_bytes += recs[i].name_len;
+    }
+    char *names = (char *)cli_xmalloc((size_t)name_bytes + 1), *q = names;
+    cli_accel_check(s->h, cornetto_text_gather(s->h, s->text, at, len, nrec, names), "fetching the record names");
+    for (int64_t i = 0; i < nrec; ++i) {
+        r[i].name = q;
+        r[i].name_len = recs[i].name_len;
+        r[i].len = recs[i].len;
+        q += recs[i].name_len;
+    }
+    free(at);
+    free(len);
+    *names_out = names;
+    return r;
+}
+
+/* -> 0: not taken, nothing has been printed and s->fp is where it was: the piece loop goes on from the first byte.  1: the records up to the
+ * offset *resume of the INFLATED text were handled; *total is that text's size (less: the sequential reader goes on at *resume) */
+static int stream_bgzf_fasta(stream_t *s, int64_t csize, int64_t *resume, int64_t *total)
+{
+    const int64_t LIMIT = 0xFFFFFF00LL - 4096;
+    const int n_pinned0 = s->n_pinned;
+    bgzf_walk_t k;
+    memset(&k, 0, sizeof(k));
+    k.fd = open(s->path, O_RDONLY);
+    if (k.fd < 0) { bgzf_fallback(s, "the file cannot be opened again"); return 0; }
+    k.size = csize;
+    const char *why = NULL;
+    cornetto_text_t *comp = NULL;
+    if (csize > LIMIT) why = "the file is larger than a device text";
+    pthread_t walk_th;
+    const int walk_started = !why && pthread_create(&walk_th, NULL, bgzf_walker, &k) == 0;
+    if (!why) {
+        if (!s->h) s->h = cli_accel_open_end();
+        TRACE("device open");
+        const int rc = cornetto_text_open(s->h, csize, &comp);
+        if (rc == CORNETTO_E_NOMEM) why = "no device memory for the compressed text";
+        else cli_accel_check(s->h, rc, "allocating the text on the GPU");
+    }
+    if (!why) {
+        whole_ring_t w;
+        const int n_thr = whole_ring_open(&w, k.fd, csize);
+        s->text = comp;
+        whole_put(s, &w, n_thr, 0, csize);
+        s->text = NULL;
+        whole_ring_close(s, &w);
+        TRACE("compressed text on the device");
+    }
+    if (walk_started) pthread_join(walk_th, NULL);
+    else if (!why) bgzf_walker(&k);
+    close(k.fd);
+    if (!why) {
+        TRACE("block chain walked");
+        why = k.why;
+    }
+    if (!why && k.total > LIMIT) why = "the text is larger than a device text";
+    if (!why) {
+        const int rc = cornetto_text_open(s->h, k.total > 0 ? k.total : 1, &s->text);
+        if (rc == CORNETTO_E_NOMEM) why = "no device memory for the text";
+        else cli_accel_check(s->h, rc, "allocating the text on the GPU");
+    }
+    if (!why) {
+        int64_t first_bad = -1;
+        const int rc = cornetto_text_inflate(s->h, comp, s->text, k.blocks, k.n, &first_bad);
+        if (rc == CORNETTO_E_FORMAT && first_bad >= 0) why = "a block is not what its footer says";
+        else if (rc == CORNETTO_E_NOMEM) why = "no device memory for the block table";
+        else cli_accel_check(s->h, rc, "inflating the text on the GPU");
+    }
+    if (comp) cornetto_text_free(s->h, comp);
+    free(k.blocks);
+    if (why) {
+        if (s->text) cornetto_text_free(s->h, s->text);
+        s->text = NULL;
+        while (s->n_pinned > n_pinned0) cornetto_pinned_free(s->pinned[--s->n_pinned]);   /* the ring's slabs: the piece loop pins its own */
+        bgzf_fallback(s, why);
+        return 0;
+    }
+    TRACE("text inflated on the device");
+    cornetto_farec_t *recs = NULL;
+    cornetto_asm_t *a = NULL;
+    int64_t nrec = 0, used = 0;
+    int32_t plain = 1;
+    cli_accel_check(s->h, cornetto_fasta_split_text(s->h, s->text, k.total, 1, &recs, &nrec, &used, &plain, s->names_only ? NULL : &a), "framing the FASTA records");
+    TRACE("records framed");
+    if (nrec) {
+        char *names = NULL;
+        cli_recname_t *r = bgzf_names(s, recs, nrec, &names);
+        s->scan(s->h, r, nrec, a, s->arg);
+        TRACE("scanned and printed");
+        free(names);
+        free(r);
+    }
+    cornetto_free(recs);
+    cornetto_asm_free(s->h, a);
+    *resume = plain ? k.total : used;     /* not plain: what follows at `used` is for the sequential reader */
+    *total = k.total;
+    return 1;
 }
 
 /* ---------------------------------------------------------------- one call */
@@ -433,7 +618,25 @@ static void stream_run(stream_t *s, int must_open)
         if (!s->h) cli_accel_open_begin();
         /* CORNETTO_CLI_WHOLE=0 and an explicit piece size keep the piece loop */
         const char *we = getenv("CORNETTO_CLI_WHOLE");
-        if (fasta && s->raw_fd >= 0 && s->size > 0 && !(we && !atoi(we)) && !getenv("CORNETTO_FASTQ_PIECE")) {
+        const int whole = !(we && !atoi(we)) && !getenv("CORNETTO_FASTQ_PIECE");
+        /* a compressed regular file: bgzip's output is inflated on the device (CORNETTO_BGZF=0: never) */
+        const char *be = getenv("CORNETTO_BGZF");
+        int64_t bz_resume = 0, bz_total = 0;
+        int bz = 0;
+        if (whole && s->raw_fd < 0 && strcmp(s->path, "-") && !gzdirect(s->fp) && !(be && !atoi(be)) && stat(s->path, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0) {
+            const int fd = open(s->path, O_RDONLY);
+            const int is_bgzf = fd >= 0 && bgzf_first_member(fd);
+            if (fd >= 0) close(fd);
+            if (!is_bgzf) bgzf_fallback(s, "not BGZF");
+            else if (!fasta) bgzf_fallback(s, "not FASTA");
+            else bz = stream_bgzf_fasta(s, (int64_t)st.st_size, &bz_resume, &bz_total);
+        }
+        if (bz) {
+            n_rest = 0;
+            more = bz_resume < bz_total;
+            if (more) bgzf_fallback(s, "the text is not plain FASTA to its end: the sequential reader goes on");
+            if (more) gzseek(s->fp, (z_off_t)bz_resume, SEEK_SET);
+        } else if (fasta && s->raw_fd >= 0 && s->size > 0 && whole) {
             const int64_t resume = stream_whole_fasta(s);
             close(s->raw_fd);
             n_rest = 0;

@@ -50,7 +50,7 @@ struct cornetto_accel {
         void *p = nullptr;
         size_t bytes = 0;
     };
-    Ws dev[64];
+    Ws dev[72];
     Ws pin[32];
     int sd_slots = 0;   // sdust: waves the device holds at once (occupancy query, cached)
     int sd_cus = 0;
@@ -156,9 +156,10 @@ enum {   // device workspace slots
     WS_SCAN, WS_STITCH,
     WS_TE_WORDS, WS_TE_REG, WS_TE_ROWS, WS_TE_CNT,
     WS_SORT, WS_HAP_ROWS, WS_HAP_BLOCKS, WS_HAP_FUN,
+    WS_BZ_BLOCKS, WS_BZ_STATUS, WS_BZ_PACK,
     WS_COUNT
 };
-static_assert(WS_COUNT <= 64, "cornetto_accel::dev has 64 slots");
+static_assert(WS_COUNT <= 72, "cornetto_accel::dev has 72 slots");
 enum {   // pinned host slots
     PIN_A, PIN_B, PIN_C, PIN_D, PIN_E, PIN_F, PIN_SMALL, PIN_TW, PIN_CW, PIN_STEP, PIN_TE
 };
@@ -395,6 +396,14 @@ struct cornetto_cov {
     // and checks afterwards (cornetto_panel_step: no round trip for the count); -1: none yet
     int64_t cw_est_key = -1, cw_est_cnt = -1;
     CnPrefix cb_pref, cw_pref;           // tiles.hpp: as in cornetto_asm
+};
+
+// a text put on the device slab by slab (fastq.hip: cornetto_text_*), or inflated there (inflate.hip)
+struct cornetto_text {
+    uint8_t *d = nullptr;
+    int64_t cap = 0;
+    hipStream_t q[4] = {nullptr, nullptr, nullptr, nullptr};     // copy queues: one copy in flight moves ~28 GB/s over PCIe, several ~45
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // the last copy of slot s (the caller's slab ring has up to four slabs)
 };
 
 // Development switches (chunk sizes, kernel-family selection, forced estimates, ablations): read from the environment ONLY in the development

@@ -480,13 +480,7 @@ extern "C" int cornetto_fasta_split(cornetto_accel_t *h, const char *text, int64
 }
 
 // ---- a text put on the device slab by slab (include/cornetto_accel.h: cornetto_text_*) ------------------------------------------------
-struct cornetto_text {
-    uint8_t *d = nullptr;
-    int64_t cap = 0;
-    hipStream_t q[4] = {nullptr, nullptr, nullptr, nullptr};     // copy queues: one copy in flight moves ~28 GB/s over PCIe, several ~45
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // the last copy of slot s (the caller's slab ring has up to four slabs)
-};
-
+// (struct cornetto_text: common.hpp — inflate.hip reads and fills texts too)
 extern "C" int cornetto_text_open(cornetto_accel_t *h, int64_t capacity, cornetto_text_t **out)
 {
     if (!h || !out || capacity < 1 || capacity > 0xFFFFFF00LL) return cn_fail(h, CORNETTO_E_ARG, "text_open: bad argument");

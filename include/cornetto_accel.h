@@ -518,6 +518,42 @@ int cornetto_fasta_split_text(cornetto_accel_t *h, cornetto_text_t *t, int64_t n
                               int64_t *consumed, int32_t *plain, cornetto_asm_t **seqs);
 
 /* ---------------------------------------------------------------------------------------------------
+ * BGZF: a bgzip-compressed text inflated on the device (`samtools faidx`-able assembly.fasta.gz in front of telofind / sdust:
+ * the reference reads it with gzread() on one thread, src/find_telomere.c:96, src/kseq.h:234)
+ * ------------------------------------------------------------------------------------------------- */
+
+/* one BGZF block (a gzip member of at most 64 KiB with its size in the header) */
+typedef struct cornetto_bgzf_block {
+    int64_t src;   /* offset of its raw deflate stream in the compressed text */
+    int64_t dst;   /* offset of its bytes in the inflated text: the sum of n_dst of the blocks before it */
+    int32_t n_src; /* bytes of the deflate stream (BSIZE + 1 - header - 8) */
+    int32_t n_dst; /* ISIZE of the footer, at most 65536 */
+    uint32_t crc;  /* CRC-32 of the footer */
+    int32_t pad;
+} cornetto_bgzf_block_t;
+
+/* Walk the chain of BGZF members in buf[0 .. n), which are the bytes at offset file_off of the file.  Host only, no device.
+ *   dst        in: the inflated offset of the first member; out: that of the member behind the last one returned
+ *   blocks     room for `cap` blocks; *n_blocks of them are filled: the members that lie wholly inside the buffer (src counts from the
+ *              beginning of the FILE)
+ *   resume     file offset of the first member not returned: hand the bytes from there on over next
+ *   broken     1: what begins at `resume` is not a BGZF member (another gzip flavour, no `BC` extra subfield, ISIZE above 65536, other
+ *              bytes); 0: the buffer or `blocks` ended there */
+int cornetto_bgzf_scan(const uint8_t *buf, int64_t n, int64_t file_off, int64_t *dst, cornetto_bgzf_block_t *blocks, int64_t cap,
+                       int64_t *n_blocks, int64_t *resume, int32_t *broken);
+
+/* Inflate the blocks from the device text `comp` into the device text `out` (a wave per block: bgzf_inflate) and check every block's
+ * CRC-32 (bgzf_crc32).  Waits for the puts of `comp`.  Every block must lie inside its text (CORNETTO_E_ARG otherwise; nothing runs).
+ * first_bad: -1, or the lowest index of a block that did not decode to exactly n_dst bytes with the footer's CRC — the status is
+ * CORNETTO_E_FORMAT then, the good blocks have their bytes, and a bad block wrote inside its own [dst, dst + n_dst) at most. */
+int cornetto_text_inflate(cornetto_accel_t *h, cornetto_text_t *comp, cornetto_text_t *out, const cornetto_bgzf_block_t *blocks,
+                          int64_t n_blocks, int64_t *first_bad);
+
+/* The bytes [at[i], at[i] + len[i]) of a device text, i = 0 .. n - 1, packed back to back on the device (one kernel) and copied to dst
+ * (one copy; host memory of sum(len) bytes): how the record names of an inflated text reach the host. */
+int cornetto_text_gather(cornetto_accel_t *h, cornetto_text_t *t, const int64_t *at, const int32_t *len, int64_t n, char *dst);
+
+/* ---------------------------------------------------------------------------------------------------
  * fixasm output text: the records of a resident assembly, renamed and reoriented
  * ------------------------------------------------------------------------------------------------- */
 
