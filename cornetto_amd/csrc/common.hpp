@@ -161,8 +161,10 @@ enum {   // device workspace slots
 };
 static_assert(WS_COUNT <= 72, "cornetto_accel::dev has 72 slots");
 enum {   // pinned host slots
-    PIN_A, PIN_B, PIN_C, PIN_D, PIN_E, PIN_F, PIN_SMALL, PIN_TW, PIN_CW, PIN_STEP, PIN_TE
+    PIN_A, PIN_B, PIN_C, PIN_D, PIN_E, PIN_F, PIN_SMALL, PIN_TW, PIN_CW, PIN_STEP, PIN_TE,
+    PIN_COUNT
 };
+static_assert(PIN_COUNT <= 32, "cornetto_accel::pin has 32 slots");
 
 static inline int cn_fail(cornetto_accel_t *h, int status, const char *fmt, ...)
 {

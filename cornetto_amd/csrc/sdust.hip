@@ -2425,4 +2425,9 @@ uint64_t *cornetto_sdust(void *km, const uint8_t *seq, int l_seq, int T, int W, 
     return ret;
 }
 
+#ifdef CN_DEV
+// the process-wide handle of the drop-ins above (null before their first call), for cn_selftest_ws_fill (selftest.hip): development build only
+cornetto_accel_t *cn_selftest_sdust_core_handle(void) { return g_handle; }
+#endif
+
 }  // extern "C"

@@ -1,7 +1,8 @@
 // selftest.hip — the scan primitives of wave.hpp / scan.hpp / ivlmerge.hpp and the radix sort of sort.hpp behind plain C entry points, DEVELOPMENT BUILD ONLY (-DCN_DEV:
 // the product object of this file is empty, tests/test_abi.py looks for the prefix in both libraries).  tests/test_gpu_scan.py
 // (tests/selftest_bind.py) compares them with numpy on inputs the product entry points cannot produce: prepared tile states for the
-// look-back, full-range values, strides and counter sets at more than one tile, epochs next to the wrap.  Not part of the C ABI: no
+// look-back, full-range values, strides and counter sets at more than one tile, epochs next to the wrap.  cn_selftest_ws_fill sets the
+// contents of the handle's workspaces between two calls (tests/test_gpu_ws_fill.py: no stage depends on what they held).  Not part of the C ABI: no
 // declaration in include/cornetto_accel.h.  Every entry takes host pointers, allocates, copies and synchronises by itself.
 #ifdef CN_DEV
 #include "common.hpp"
@@ -83,9 +84,118 @@ int run_block_excl(cornetto_accel_t *h, const void *in, void *pre_out, void *tot
     return CORNETTO_OK;
 }
 
+// ---- what a workspace slot holds between two complete calls (DESIGN.md section 3 has the same table, with the owning stages) -----------------
+//   scratch   nothing: every word a call reads it has written itself (cn_ws: "contents undefined")
+//   vouched   contents a later call may use again, but only while the named host fields of the handle say so
+//   polled    words that kernels wait on (the epoch-tagged tile states of the single-pass scans); valid by epoch, never by content
+enum WsClass { WSC_SCRATCH, WSC_VOUCHED, WSC_POLLED };
+struct WsRow {
+    int slot;
+    const char *name;
+    WsClass cls;
+    const char *voucher;           // vouched: the host fields; polled: what makes a word count
+};
+#define WS_ROW(s, c, v) {s, #s, c, v}
+#define WS_SCR(s) {s, #s, WSC_SCRATCH, ""}
+constexpr WsRow ws_table[] = {
+    WS_ROW(WS_TF_LUT, WSC_VOUCHED, "tf_lut_key, tf_lut_ptr"),
+    WS_SCR(WS_TF_CNT), WS_SCR(WS_TF_TB), WS_SCR(WS_TF_TC), WS_SCR(WS_TF_L0), WS_SCR(WS_TF_L1), WS_SCR(WS_TF_L2), WS_SCR(WS_TF_L3),
+    WS_ROW(WS_TF_BITMAP, WSC_VOUCHED, "tf_bm_uid, tf_bm_ptr, tf_bm_words"),
+    WS_SCR(WS_TF_ROFF), WS_SCR(WS_TF_RUNS), WS_SCR(WS_TF_NRUNS),
+    WS_SCR(WS_TW_BOFF), WS_SCR(WS_TW_TILES), WS_SCR(WS_TW_OUT), WS_SCR(WS_TW_CNT), WS_SCR(WS_TW_HITS), WS_SCR(WS_TW_LEN), WS_SCR(WS_TW_BITMAP),
+    WS_SCR(WS_SD_OUT), WS_SCR(WS_SD_CNT), WS_SCR(WS_SD_OFF), WS_SCR(WS_SD_DST), WS_SCR(WS_SD_STATS), WS_SCR(WS_SD_PERM),
+    WS_SCR(WS_CB_T32), WS_SCR(WS_CB_T64), WS_SCR(WS_CB_GRAND),
+    WS_SCR(WS_CW_REGS), WS_SCR(WS_CW_SEL), WS_SCR(WS_CW_CNT), WS_SCR(WS_CW_TRES), WS_SCR(WS_CW_CF),
+    WS_SCR(WS_TF_HITS),
+    WS_SCR(WS_BG_TEXT_A), WS_SCR(WS_BG_TEXT_B), WS_SCR(WS_BG_TOK_A), WS_SCR(WS_BG_TOK_B), WS_SCR(WS_BG_CNT_A), WS_SCR(WS_BG_CNT_B), WS_SCR(WS_BG_SMALL), WS_SCR(WS_BG_BRK),
+    WS_SCR(WS_TB), WS_SCR(WS_TB_SMALL), WS_SCR(WS_TB_OUT), WS_SCR(WS_CW_MERGE), WS_SCR(WS_IVL_MERGE),
+    WS_SCR(WS_FQ_TEXT), WS_SCR(WS_FQ_CNT), WS_SCR(WS_FQ_NL), WS_SCR(WS_FQ_RECS), WS_SCR(WS_FQ_ENDS), WS_SCR(WS_FQ_SRC),
+    WS_ROW(WS_SCAN, WSC_POLLED, "scan_epoch, scan_tickets"),
+    WS_ROW(WS_STITCH, WSC_POLLED, "st_epoch, st_tickets"),
+    WS_SCR(WS_TE_WORDS), WS_SCR(WS_TE_REG), WS_SCR(WS_TE_ROWS), WS_SCR(WS_TE_CNT),
+    WS_SCR(WS_SORT), WS_SCR(WS_HAP_ROWS), WS_SCR(WS_HAP_BLOCKS), WS_SCR(WS_HAP_FUN),
+    WS_SCR(WS_BZ_BLOCKS), WS_SCR(WS_BZ_STATUS), WS_SCR(WS_BZ_PACK),
+};
+#undef WS_ROW
+#undef WS_SCR
+static_assert(sizeof(ws_table) / sizeof(ws_table[0]) == WS_COUNT, "every device workspace slot has a class: a new slot gets a row here and in DESIGN.md section 3");
+constexpr bool ws_table_in_order()
+{
+    for (int i = 0; i < WS_COUNT; ++i)
+        if (ws_table[i].slot != i) return false;
+    return true;
+}
+static_assert(ws_table_in_order(), "the rows of ws_table stand in the order of the enum");
+
+// the pinned slots: all scratch (the host reads of a call what the call's own copies wrote)
+constexpr const char *pin_names[] = {"PIN_A", "PIN_B", "PIN_C", "PIN_D", "PIN_E", "PIN_F", "PIN_SMALL", "PIN_TW", "PIN_CW", "PIN_STEP", "PIN_TE"};
+static_assert(sizeof(pin_names) / sizeof(pin_names[0]) == PIN_COUNT, "every pinned slot has a name");
+
 }  // namespace
 
 extern "C" {
+
+// the name of device slot `slot` / of pinned slot `slot` as the enums of common.hpp spell it; null outside the enum
+const char *cn_selftest_ws_name(int slot) { return slot >= 0 && slot < WS_COUNT ? ws_table[slot].name : nullptr; }
+const char *cn_selftest_pin_name(int slot) { return slot >= 0 && slot < PIN_COUNT ? pin_names[slot] : nullptr; }
+// 0 scratch, 1 vouched, 2 polled (-1 outside the enum); *voucher: the host fields that vouch ("" for scratch)
+int cn_selftest_ws_class(int slot, const char **voucher)
+{
+    if (slot < 0 || slot >= WS_COUNT) return -1;
+    if (voucher) *voucher = ws_table[slot].voucher;
+    return (int)ws_table[slot].cls;
+}
+
+// Every byte of every allocated workspace of the handle set to `byte`, over the slot's whole capacity: what the next call finds where cn_ws says
+// "contents undefined".  Scratch slots and the pinned slots are filled; vouched slots are filled and their voucher is dropped exactly as a fresh
+// handle has it (the next call uploads / clears again); polled slots (WS_SCAN, WS_STITCH) are NOT touched — their words are waited on by kernels, a
+// filled word with the epoch of a later call would be waited on for ever; tests/test_gpu_scan.py owns them.  No word any kernel spins on is written.
+// filled[s] / skipped[s] (n_dev >= WS_COUNT entries each), pin_filled[s] (n_pin >= PIN_COUNT): bytes per slot.
+// BETWEEN COMPLETE OPERATIONS ONLY: CORNETTO_E_ARG, and nothing touched, while cornetto_sdust_asm_begin() waits for its _end or a lazy handle's copies
+// are out.  What the handle cannot tell is the caller's to keep: no fill while a streaming session (cornetto_bgin_*, cornetto_bgrun_*) has a feed or a
+// prefetch on its way or a text object's slabs are in flight on its own queues (only the handle's three streams are waited for here); the tests fill
+// between complete sessions.
+int cn_selftest_ws_fill(cornetto_accel_t *h, int byte, int64_t *filled, int64_t *skipped, int n_dev, int64_t *pin_filled, int n_pin)
+{
+    if (!h || byte < 0 || byte > 255 || !filled || !skipped || n_dev < WS_COUNT || !pin_filled || n_pin < PIN_COUNT) return cn_fail(h, CORNETTO_E_ARG, "selftest_ws_fill: bad argument");
+    if (h->sd_pend.state != 0 || h->copies_pending) return cn_fail(h, CORNETTO_E_ARG, "selftest_ws_fill: an operation is in flight on the handle");
+    CN_HIP(h, hipSetDevice(h->device));
+    auto sync_all = [&]() -> int {
+        CN_HIP(h, hipStreamSynchronize(h->stream));
+        if (h->stream2) CN_HIP(h, hipStreamSynchronize(h->stream2));
+        if (h->copy_stream) CN_HIP(h, hipStreamSynchronize(h->copy_stream));
+        return CORNETTO_OK;
+    };
+    CN_TRY(sync_all());
+    for (int s = 0; s < WS_COUNT; ++s) {
+        const cornetto_accel::Ws &w = h->dev[s];
+        filled[s] = skipped[s] = 0;
+        if (!w.p || !w.bytes) continue;
+        if (ws_table[s].cls == WSC_POLLED) {
+            skipped[s] = (int64_t)w.bytes;
+            continue;
+        }
+        CN_HIP(h, hipMemsetAsync(w.p, byte, w.bytes, h->stream));
+        filled[s] = (int64_t)w.bytes;
+        if (s == WS_TF_LUT) {                         // (telo.hip: the tables of a motif are uploaded unless these say they are there)
+            h->tf_lut_key.clear();
+            h->tf_lut_ptr = nullptr;
+        }
+        if (s == WS_TF_BITMAP) {                      // (telo.hip: the padding words are cleared unless these say they are zero)
+            h->tf_bm_uid = 0;
+            h->tf_bm_ptr = nullptr;
+            h->tf_bm_words = 0;
+        }
+    }
+    for (int s = 0; s < PIN_COUNT; ++s) {
+        const cornetto_accel::Ws &w = h->pin[s];
+        pin_filled[s] = 0;
+        if (!w.p || !w.bytes) continue;
+        memset(w.p, byte, w.bytes);
+        pin_filled[s] = (int64_t)w.bytes;
+    }
+    return sync_all();
+}
 
 // out[i] = the primitive `which` over the wave of in[i]: 0 wave_incl<uint32_t>, 1 wave_incl<unsigned long long> (in and out 64-bit),
 // 2 wave_incl_dpp, 3 wave_sum.  n: a multiple of 64.

@@ -1012,9 +1012,10 @@ int cn_telo_scan_impl(cornetto_accel_t *h, const cornetto_asm_t *a, const char *
     bool valid = false;
     cornetto_hit_t *hh = nullptr;
     int64_t nh = 0;
-    // a bordered motif needs the runs themselves to build the marks, so the hits are always fetched then
+    // a bordered motif needs the runs themselves to build the marks, so the hits are always fetched then — and so does a motif beyond the
+    // automaton's 32 bytes, with or without a border: telofind_impl scans it by the sequential rule and writes no marks
     const std::string m(motif ? motif : "");
-    const bool need_hits = hits || has_border(m) || has_border(revcomp(m));
+    const bool need_hits = hits || (int)m.size() > MAX_MOTIF || has_border(m) || has_border(revcomp(m));
     CN_TRACE("telo_scan: enter");
     int rc = telofind_impl(h, a, motif, need_hits ? &hh : nullptr, need_hits ? &nh : nullptr, true, &d_bitmap, &valid);
     CN_TRACE("telo_scan: telofind done");

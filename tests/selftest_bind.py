@@ -1,5 +1,6 @@
 """ctypes binding of the cn_selftest_* entry points (cornetto_amd/csrc/selftest.hip, bgrun.hip): the scan primitives of wave.hpp /
-scan.hpp / ivlmerge.hpp on their own, in the DEVELOPMENT build of the library only.  Not part of the C ABI; used by test_gpu_scan.py.
+scan.hpp / ivlmerge.hpp on their own, and the hook that sets the contents of a handle's workspaces (cn_selftest_ws_fill), in the DEVELOPMENT
+build of the library only.  Not part of the C ABI; used by test_gpu_scan.py, test_gpu_ws_fill.py and test_ws_table.py.
 Every function takes an `Accel(0, dev=True)` (the `dacc` fixture) and numpy arrays."""
 import ctypes as C
 
@@ -28,10 +29,18 @@ def _lib():
         "cn_selftest_merge_fused": [vp, vp, i64, i64, i32, vp, C.POINTER(i64)],
         "cn_selftest_scan_u64": [vp, vp, i64, C.POINTER(C.c_uint64)],
     }
+    sig["cn_selftest_ws_fill"] = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int]
+    sig["cn_selftest_ws_class"] = [C.c_int, C.POINTER(C.c_char_p)]
     for name, args in sig.items():
         fn = getattr(L, name)
         fn.restype = C.c_int
         fn.argtypes = args
+    for name in ("cn_selftest_ws_name", "cn_selftest_pin_name"):
+        fn = getattr(L, name)
+        fn.restype = C.c_char_p
+        fn.argtypes = [C.c_int]
+    L.cn_selftest_sdust_core_handle.restype = vp
+    L.cn_selftest_sdust_core_handle.argtypes = []
     _bound[id(L)] = True
     return L
 
@@ -93,6 +102,71 @@ def merge_fused(acc, ivls, dist=0, n_cap=None):
     n = C.c_int64(0)
     acc._chk(_lib().cn_selftest_merge_fused(acc.h, _p(ivls), ivls.size, ivls.size if n_cap is None else n_cap, dist, _p(out), C.byref(n)))
     return out[:n.value]
+
+
+WS_CLASSES = ("scratch", "vouched", "polled")
+
+
+def _names(fn):
+    out = []
+    while fn(len(out)) is not None:
+        out.append(fn(len(out)).decode())
+    return out
+
+
+def ws_names():
+    """the device workspace slots by their enum names, in enum order (cn_selftest_ws_name)"""
+    return _names(_lib().cn_selftest_ws_name)
+
+
+def pin_names():
+    return _names(_lib().cn_selftest_pin_name)
+
+
+def ws_classes():
+    """{slot name: (class of WS_CLASSES, the host fields that vouch for its contents or "")}: the hook's table (cn_selftest_ws_class)"""
+    out = {}
+    for i, name in enumerate(ws_names()):
+        v = C.c_char_p()
+        out[name] = (WS_CLASSES[_lib().cn_selftest_ws_class(i, C.byref(v))], v.value.decode())
+    return out
+
+
+def ws_fill_rc(acc, byte):
+    """cn_selftest_ws_fill: every allocated workspace of the handle set to `byte` over its whole capacity, the vouchers of the vouched slots
+    dropped, the polled slots (WS_SCAN, WS_STITCH) left alone -> (status, {name: bytes filled}, {name: bytes skipped}, {pinned name: bytes
+    filled}), slots with 0 bytes left out.  BETWEEN COMPLETE OPERATIONS ONLY: E_ARG, nothing touched, while sdust_begin() waits for its
+    sdust_end() or a lazy handle's copies are out; never while a bgin / bgrun session has a feed or a prefetch on its way or a text object's
+    slabs are in flight (they use queues of their own: the handle cannot tell, and the hook waits for the handle's own streams only)."""
+    dn, pn = ws_names(), pin_names()
+    f, s, p = np.zeros(len(dn), np.int64), np.zeros(len(dn), np.int64), np.zeros(len(pn), np.int64)
+    rc = _lib().cn_selftest_ws_fill(acc.h, byte, _p(f), _p(s), len(dn), _p(p), len(pn))
+    if rc != 0:
+        return rc, {}, {}, {}
+    return (rc, {n: int(v) for n, v in zip(dn, f) if v}, {n: int(v) for n, v in zip(dn, s) if v}, {n: int(v) for n, v in zip(pn, p) if v})
+
+
+class _Handle:
+    """a handle the library owns, with what ws_fill() needs of an Accel"""
+
+    def __init__(self, h):
+        self.h = C.c_void_p(h)
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise cornetto_amd.AccelError(rc, _lib().cornetto_accel_last_error(self.h).decode())
+
+
+def sdust_core_handle():
+    """the process-wide handle of cornetto_sdust() / cornetto_sdust_core() in the development build; None before their first call"""
+    h = _lib().cn_selftest_sdust_core_handle()
+    return _Handle(h) if h else None
+
+
+def ws_fill(acc, byte):
+    rc, filled, skipped, pinned = ws_fill_rc(acc, byte)
+    acc._chk(rc)
+    return filled, skipped, pinned
 
 
 def scan_u64(acc, v):

@@ -222,11 +222,34 @@ def acc():
     a.close()
 
 
+MERGE_TILE = 1024                  # cnivl::ST_TILE: intervals per tile of the merge
+ROUND = 1024 * MERGE_TILE          # intervals whose tile maxima st_tiles scans in one round
+SWALLOW_END = 2_000_000_000        # beyond every start below
+
+
+def _one_contig_swallowed_from(seed, n, at):
+    """n intervals of ONE contig in start order (short ones: they merge into many), interval `at` with a finish beyond every later start"""
+    rng = np.random.default_rng(seed)
+    iv = np.zeros(n, cornetto_amd.IVL_DT)
+    iv["start"] = np.sort(rng.integers(0, 1_500_000_000, size=n)).astype(np.int32)
+    iv["finish"] = iv["start"] + rng.integers(0, 300, size=n).astype(np.int32)
+    iv["finish"][at] = SWALLOW_END
+    return iv
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("seed,n,dist", [(1, 1, 0), (2, 50, 0), (3, 5000, 10), (4, 200_000, 1000), (5, 1_000_000, 0), (6, 70_000, 200_000),
                                          # the tile seams of the max-scan (1024 intervals) and of the add-scan of the heads (4096)
-                                         (7, 1023, 0), (8, 1024, 0), (9, 1025, 0), (10, 4095, 0), (11, 4096, 0), (12, 4097, 0)])
+                                         (7, 1023, 0), (8, 1024, 0), (9, 1025, 0), (10, 4095, 0), (11, 4096, 0), (12, 4097, 0),
+                                         # st_tiles scans the tile maxima 1024 at a time and carries the maximum on: one tile beyond a round, and beyond two
+                                         (13, ROUND + 1, 0), (14, 2 * ROUND + 3, 0)])
 def test_ivl_merge_vs_oracle(acc, seed, n, dist):
+    if n > ROUND:
+        iv = _one_contig_swallowed_from(seed, n, 5)                       # an interval of the FIRST tile reaches beyond every later start
+        exp = ob.ivl_merge(_p2o(iv), dist)
+        assert 1 <= len(exp) <= 6 and int(exp["end"][-1]) == SWALLOW_END  # nothing after it opens a new interval, in any round
+        assert np.array_equal(_p2o(acc.ivl_merge(iv, dist)), exp)
+        return
     rng = np.random.default_rng(seed)
     ctg = np.sort(rng.integers(0, max(1, n // 1000 + 3), size=n)).astype(np.int32)
     start = rng.integers(0, 5_000_000, size=n).astype(np.int32)
@@ -238,6 +261,18 @@ def test_ivl_merge_vs_oracle(acc, seed, n, dist):
         iv["finish"][n // 2] = iv["start"][n // 2] + 4_000_000            # one interval that swallows many
     got = acc.ivl_merge(iv, dist)
     assert np.array_equal(_p2o(got), ob.ivl_merge(_p2o(iv), dist))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seed,n", [(15, ROUND + 1), (16, 2 * ROUND + 3)])
+def test_ivl_merge_swallowing_interval_in_the_last_tile_of_round_one(acc, seed, n):
+    """the sibling of the two largest sets above: the swallowing interval lies in tile 1023, the last one of st_tiles' first round, so the
+    maximum reaches the later tiles through the carry alone; the tiles before it merge as random intervals do"""
+    at = 1023 * MERGE_TILE + 7
+    iv = _one_contig_swallowed_from(seed, n, at)
+    exp = ob.ivl_merge(_p2o(iv), 0)
+    assert len(exp) > 1000 and int(exp["end"][-1]) == SWALLOW_END and int(exp["start"][-1]) <= int(iv["start"][at])
+    assert np.array_equal(_p2o(acc.ivl_merge(iv, 0)), exp)
 
 
 @pytest.mark.gpu
