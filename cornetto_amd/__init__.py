@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-__all__ = ["lib", "Accel", "bgzf_scan", "BGZF_DT", "AccelError", "HIT_DT", "WIN_DT", "IVL_DT", "TELROW_DT", "HAP_ROW_DT", "khash_str_order", "panel_boring", "REG_DT", "REGREC_DT", "build",
+__all__ = ["lib", "Accel", "bgzf_scan", "bam_header", "BGZF_DT", "BAMREC_DT", "BAM_SCAN_TILE", "BamFormatError", "AccelError", "HIT_DT", "WIN_DT", "IVL_DT", "TELROW_DT", "HAP_ROW_DT", "khash_str_order", "panel_boring", "REG_DT", "REGREC_DT", "build",
            "LIB_PATH", "CLI_PATH"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -43,6 +43,19 @@ class BgRunErr(C.Structure):
     _fields_ = [("kind", C.c_int32), ("file", C.c_int32), ("record", C.c_int64), ("a", C.c_int32), ("b", C.c_int32)]
 
 
+class BamErr(C.Structure):
+    """cornetto_bamerr_t (include/cornetto_accel.h)"""
+    _fields_ = [("kind", C.c_int32), ("a", C.c_int32), ("b", C.c_int32), ("pad", C.c_int32), ("record", C.c_int64)]
+
+
+class BamDepthOpt(C.Structure):
+    """cornetto_bamdepth_opt_t (include/cornetto_accel.h)"""
+    _fields_ = [("min_mapq", C.c_int32), ("skip_flags", C.c_uint32), ("window", C.c_int64), ("records", C.c_int32), ("pad", C.c_int32)]
+
+
+BAMREC_DT = np.dtype([("offset", "<i8"), ("ref_id", "<i4"), ("pos", "<i4"), ("mapq", "<i4"), ("flag", "<i4"), ("counted", "<i4"), ("n_ops", "<i4"), ("span", "<i8"),
+                      ("bases", "<i8")])
+BAM_SCAN_TILE = 4096  # CORNETTO_BAM_SCAN_TILE: positions per workgroup of the depth scan (checked against the library when it is loaded)
 BGRUN_TILE = 4096     # CORNETTO_BGRUN_TILE: positions per workgroup of the run expansion (checked against the library when it is loaded)
 
 
@@ -67,6 +80,14 @@ class BedgraphFormatError(ValueError):
     def __init__(self, kind, record, a, b, file=None):
         super().__init__("bedgraph check %d failed at record %d (%d, %d)%s" % (kind, record, a, b, "" if file is None else " of file %d" % file))
         self.kind, self.record, self.a, self.b, self.file = kind, record, a, b, file
+
+
+class BamFormatError(ValueError):
+    """a check of the BAM reader failed (kind / record / numbers as in cornetto_bamerr_t; kind 7: the file has no BAM header)"""
+
+    def __init__(self, kind, record, a, b):
+        super().__init__("BAM check %d failed at record %d (%d, %d)" % (kind, record, a, b))
+        self.kind, self.record, self.a, self.b = kind, record, a, b
 
 
 class AccelError(RuntimeError):
@@ -186,15 +207,50 @@ def lib(dev=False):
         "cornetto_bgrun_error": (C.POINTER(BgRunErr), [vp]),
         "cornetto_bgrun_finish": (C.c_int, [vp, vp, pp, C.POINTER(i32), C.POINTER(C.POINTER(cp)), C.POINTER(i64)]),
         "cornetto_cov_download": (C.c_int, [vp, vp, i32, vp, vp]),
+        "cornetto_bam_header": (C.c_int, [vp, i64, C.POINTER(i32), C.POINTER(C.POINTER(cp)), C.POINTER(C.POINTER(i32)), C.POINTER(i64)]),
+        "cornetto_bamdepth_defaults": (None, [C.POINTER(BamDepthOpt)]),
+        "cornetto_bam_scan_tile": (i32, []),
+        "cornetto_bamdepth_open": (C.c_int, [vp, C.POINTER(BamDepthOpt), vp, i32, pp]),
+        "cornetto_bamdepth_close": (None, [vp, vp]),
+        "cornetto_bamdepth_feed": (C.c_int, [vp, vp, vp, vp, i64, i64]),
+        "cornetto_bamdepth_error": (C.POINTER(BamErr), [vp]),
+        "cornetto_bamdepth_finish": (C.c_int, [vp, vp, pp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
+        "cornetto_bam_records": (C.c_int, [vp, vp, pp, C.POINTER(i64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
     assert L.cornetto_bgrun_tile() == BGRUN_TILE
+    assert L.cornetto_bam_scan_tile() == BAM_SCAN_TILE
     L._declared = sorted(sig)
     _libs[path] = L
     return L
+
+
+def bam_header(data):
+    """cornetto_bam_header() over `data`, the first inflated bytes of a BAM -> (names, lens, header bytes), or None when the header goes on
+    behind them; ValueError when they are no BAM header.  Host only."""
+    L = lib()
+    keep = np.frombuffer(bytes(data), dtype=np.uint8)
+    n_ref, names, lens, hb = C.c_int32(), C.POINTER(C.c_char_p)(), C.POINTER(C.c_int32)(), C.c_int64()
+    rc = L.cornetto_bam_header(keep.ctypes.data if keep.size else None, keep.size, C.byref(n_ref), C.byref(names), C.byref(lens), C.byref(hb))
+    if rc == 1:
+        return None
+    if rc == -6:
+        raise ValueError("not a BAM header")
+    if rc != 0:
+        raise AccelError(rc, L.cornetto_accel_strerror(rc).decode())
+    nm = [names[i].decode() for i in range(n_ref.value)]
+    ln = [lens[i] for i in range(n_ref.value)]
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    arr = C.cast(names, C.POINTER(C.c_void_p))
+    for i in range(n_ref.value):
+        libc.free(arr[i])
+    libc.free(C.cast(names, C.c_void_p))
+    libc.free(C.cast(lens, C.c_void_p))
+    return nm, ln, hb.value
 
 
 def bgzf_scan(data, file_off=0, dst=0):
@@ -768,6 +824,80 @@ class Accel:
             libc.free(arr[i])
         libc.free(C.cast(names, C.c_void_p))
         return _Resident(self, cov, L.cornetto_cov_free, lens), nm, ncl.value
+
+    # ---- BAM ---------------------------------------------------------------------------------------
+    def _bam_run(self, blob, window, min_mapq, records, feeds=1):
+        """the BAM file `blob` through cornetto_bamdepth_*: the header from the leading blocks (zlib + cornetto_bam_header), the compressed
+        bytes as one device text, its blocks in `feeds` feeds -> (names, coverage or None, record table or None, n_records, n_counted,
+        n_clamped).  Raises BamFormatError; a record larger than the window raises AccelError (status -4).  The kernel times of all
+        feeds and of the finish are kept in self.bam_timing."""
+        import zlib
+        L = self.L
+        blocks, resume, broken = bgzf_scan(blob)
+        if broken or resume != len(blob):
+            raise BamFormatError(7 if not len(blocks) else 6, 0, 0, 0)
+        head, hdr = b"", None
+        for b in blocks:
+            try:
+                head += zlib.decompress(bytes(blob[int(b["src"]):int(b["src"]) + int(b["n_src"])]), -15)
+            except zlib.error:
+                raise BamFormatError(6, 0, 0, 0)
+            try:
+                hdr = bam_header(head)
+            except ValueError:
+                raise BamFormatError(7, -1, 0, 0)
+            if hdr is not None:
+                break
+        if hdr is None:
+            raise BamFormatError(2, -1, 0, -1)
+        names, lens, skip = hdr
+        opt = BamDepthOpt()
+        L.cornetto_bamdepth_defaults(C.byref(opt))
+        opt.min_mapq, opt.records = min_mapq, records
+        if window is not None:
+            opt.window = window
+        lens_a = np.array(lens, dtype=np.int32)
+        comp = self._text_from(blob)
+        bd = C.c_void_p()
+        self.bam_timing = []
+        try:
+            self._chk(L.cornetto_bamdepth_open(self.h, C.byref(opt), lens_a.ctypes.data, len(lens), C.byref(bd)))
+
+            def check(rc):
+                self.bam_timing += self.last_timing()
+                if rc == -6:
+                    e = L.cornetto_bamdepth_error(bd).contents
+                    if e.kind:
+                        raise BamFormatError(e.kind, e.record, e.a, e.b)
+                self._chk(rc)
+            cuts = [len(blocks) * i // feeds for i in range(feeds + 1)]
+            for i in range(feeds):
+                part = np.ascontiguousarray(blocks[cuts[i]:cuts[i + 1]])
+                check(L.cornetto_bamdepth_feed(self.h, bd, comp, part.ctypes.data, part.size, skip if i == 0 else 0))
+            cov, nr, nc, ncl = C.c_void_p(), C.c_int64(), C.c_int64(), C.c_int64()
+            check(L.cornetto_bamdepth_finish(self.h, bd, C.byref(cov), C.byref(nr), C.byref(nc), C.byref(ncl)))
+            res = _Resident(self, cov, L.cornetto_cov_free, lens) if cov.value else None
+            recs = None
+            if records:
+                p, n = C.c_void_p(), C.c_int64()
+                self._chk(L.cornetto_bam_records(self.h, bd, C.byref(p), C.byref(n)))
+                recs = _take(L, p, n.value, BAMREC_DT)
+            return names, res, recs, nr.value, nc.value, ncl.value
+        finally:
+            if bd.value:
+                L.cornetto_bamdepth_close(self.h, bd)
+            L.cornetto_text_free(self.h, comp)
+
+    def bam_depth(self, blob, window=None, min_mapq=20, feeds=1):
+        """both coverage tracks of the BAM file `blob` (bytes) -> (resident coverage, [contig names], n_records, n_counted, n_clamped): what
+        `samtools depth -aa` and `samtools depth -Q min_mapq -aa` count (include/cornetto_accel.h states the rules).  window: bytes of
+        inflated BAM on the device at once (never changes a result); feeds: the blocks are handed over in that many calls."""
+        names, cov, _, nr, nc, ncl = self._bam_run(blob, window, min_mapq, 0, feeds)
+        return cov, names, nr, nc, ncl
+
+    def bam_records(self, blob, window=None):
+        """the records of the BAM file `blob` as the depth kernel reads them (BAMREC_DT); no depth array is allocated"""
+        return self._bam_run(blob, window, 20, 2)[2]
 
     def bedgraph_runs_ingest(self, tot_pieces, mq_pieces, alternate=True):
         """stream two RUN-LENGTH bedgraphs (iterables of bytes pieces, any split points) through cornetto_bgrun_*; returns what

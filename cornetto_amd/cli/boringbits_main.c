@@ -58,6 +58,9 @@ static void print_help(FILE *fp, const optp_t *o)
     fprintf(fp, "   -h                         help\n");
     fprintf(fp, "   --verbose INT              verbosity level [%d]\n", cli_log_level);
     fprintf(fp, "   --accel=yes|no             Running on accelerator [yes]\n");
+    fprintf(fp, "   --bam FILE                 (extension) both depth tracks from this BAM instead of the two depth files and -q:\n");
+    fprintf(fp, "                              what samtools depth -aa and samtools depth -Q 20 -aa count\n");
+    fprintf(fp, "   --bam-mapq INT             (extension) mapping quality of the second track of --bam [20]\n");
     fprintf(fp, "   --runs                     (extension) the depth files are run-length bedgraphs: name start end value,\n");
     fprintf(fp, "                              one record per run (mosdepth, bedtools genomecov -bga); contigs start at 0, no gaps\n");
     fprintf(fp, "   --hap FILE                 (extension, with --panel) PAF of a haplotype assembly against the primary one, 1 to %d times:\n", HP_MAX);
@@ -953,14 +956,16 @@ static void print_bits(char **names, const int32_t *lens, int32_t n_ctg, const c
 }
 
 /* --accel=no / CORNETTO_ACCEL=no: the whole sub-command on the host (cli/host_backend.c), the_boring_bits() :483-536 */
-static int host_bits(FILE *ft, FILE *fq, const optp_t *opt, int8_t boring, const char *panel_bed, const char *lowq_bed, const char *const *runs_paths)
+static int host_bits(FILE *ft, FILE *fq, const optp_t *opt, int8_t boring, const char *panel_bed, const char *lowq_bed, const char *const *runs_paths,
+                     const char *bam_path, int bam_mapq)
 {
     double t0 = cli_realtime();
     cli_host_cov_t cov;
-    if (runs_paths) cli_host_get_depths_runs(ft, fq, runs_paths[0], runs_paths[1], &cov);
+    if (bam_path) cli_host_get_depths_bam(bam_path, bam_mapq, &cov);
+    else if (runs_paths) cli_host_get_depths_runs(ft, fq, runs_paths[0], runs_paths[1], &cov);
     else cli_host_get_depths(ft, fq, &cov);
-    fclose(ft);
-    fclose(fq);
+    if (ft) fclose(ft);
+    if (fq) fclose(fq);
     if (cov.n_clamped) CLI_WARNING("%lld depth values were truncated to 65535", (long long)cov.n_clamped);
     CLI_VERBOSE("Loaded depth files in %.2f seconds", cli_realtime() - t0);
     int32_t mean_depth = (int32_t)0x80000000, mean_mq = (int32_t)0x80000000;   /* (no record at all: the reference rounds 0 / 0) */
@@ -1013,11 +1018,12 @@ int boringbits_main(int argc, char *argv[], int8_t boring)
         {"panel-params", required_argument, 0, 0}, {"runs", no_argument, 0, 0},
         {"hap", required_argument, 0, 0},         {"dip", required_argument, 0, 0},
         {"hap-fun", required_argument, 0, 0},     {"hap-params", required_argument, 0, 0},
+        {"bam", required_argument, 0, 0},         {"bam-mapq", required_argument, 0, 0},
         {0, 0, 0, 0}};
     optp_t opt = {2500, 50, 0.4f, 2.5f, 0.4f, 1000000, 100000}; /* :540-556 */
-    const char *covmq = NULL, *panel_bed = NULL, *lowq_bed = NULL;
+    const char *covmq = NULL, *panel_bed = NULL, *lowq_bed = NULL, *bam = NULL;
     FILE *fp_help = stderr;
-    int c, li = 0, runs = 0;
+    int c, li = 0, runs = 0, bam_mapq = 20;
     optind = 1;
     while ((c = getopt_long(argc, argv, "t:B:K:v:o:q:Q:H:L:w:i:e:m:hV", lo, &li)) >= 0) {
         if (c == 'K') {
@@ -1082,6 +1088,16 @@ int boringbits_main(int argc, char *argv[], int8_t boring)
                 CLI_ERROR("%s", "--hap-params wants two integers: merge-d (>= 0),flank (>= 1)");
                 exit(EXIT_FAILURE);
             }
+        } else if (c == 0 && li == 26) {
+            bam = optarg;
+        } else if (c == 0 && li == 27) {
+            char *end = NULL;
+            const long q = strtol(optarg, &end, 10);
+            if (end == optarg || *end || q < 0 || q > 255) {
+                CLI_ERROR("--bam-mapq wants an integer from 0 to 255. You entered %s", optarg);
+                exit(EXIT_FAILURE);
+            }
+            bam_mapq = (int)q;
         } else if (c == 0 && li == 9) { /* --accel: the seam the reference left (src/boringbits_main.c:627-632) */
             if (strcmp(optarg, "no") == 0 || strcmp(optarg, "n") == 0) {
                 cli_host_set(1);       /* the host path of cli/host_backend.c: sequential parse, window sums, selection */
@@ -1092,12 +1108,16 @@ int boringbits_main(int argc, char *argv[], int8_t boring)
             }
         }
     }
-    if (argc - optind != 1 || fp_help == stdout) { /* :638-644 */
+    if (bam && fp_help != stdout && (argc - optind != 0 || covmq || runs)) {
+        CLI_ERROR("%s", "--bam takes the place of the two depth files: no positional file, no -q and no --runs with it");
+        exit(EXIT_FAILURE);
+    }
+    if ((!bam && argc - optind != 1) || fp_help == stdout) { /* :638-644 */
         print_help(fp_help, &opt);
         exit(fp_help == stdout ? EXIT_SUCCESS : EXIT_FAILURE);
     }
-    const char *covtotal = argv[optind];
-    if (!covmq) {
+    const char *covtotal = bam ? NULL : argv[optind];
+    if (!covmq && !bam) {
         print_help(fp_help, &opt);
         exit(EXIT_FAILURE);
     }
@@ -1112,18 +1132,18 @@ int boringbits_main(int argc, char *argv[], int8_t boring)
 
     /* ---------------- get_depths (:180-301): text -> uint16 arrays, on the device ---------------- */
     double t0 = cli_realtime();
-    FILE *ft = fopen(covtotal, "r");
+    FILE *ft = fopen(bam ? bam : covtotal, bam ? "rb" : "r");
     if (!ft) {
-        CLI_ERROR("Failed to open %s : No such file or directory.", covtotal);
+        CLI_ERROR("Failed to open %s : No such file or directory.", bam ? bam : covtotal);
         exit(EXIT_FAILURE);
     }
-    FILE *fq = fopen(covmq, "r");
-    if (!fq) {
+    FILE *fq = bam ? NULL : fopen(covmq, "r");   /* (--bam: one file; cli/bam.c and the host reader open their own, ft only says that it is there) */
+    if (!bam && !fq) {
         CLI_ERROR("Failed to open %s : No such file or directory.", covmq);
         exit(EXIT_FAILURE);
     }
     const char *const run_paths[2] = {covtotal, covmq};
-    if (cli_host_mode()) return host_bits(ft, fq, &opt, boring, panel_bed, lowq_bed, runs ? run_paths : NULL);
+    if (cli_host_mode()) return host_bits(ft, fq, &opt, boring, panel_bed, lowq_bed, runs ? run_paths : NULL, bam, bam_mapq);
     int devs[CLI_MAX_DEV];
     const int n_dev = cli_device_list(devs);
     if (n_dev >= 1) { /* the text is parsed on the first listed device */
@@ -1139,7 +1159,7 @@ int boringbits_main(int argc, char *argv[], int8_t boring)
     struct stat st_t, st_q;
     int n_rd = 8;
     if (getenv("CORNETTO_BG_THREADS")) n_rd = atoi(getenv("CORNETTO_BG_THREADS"));
-    const int threaded = n_rd > 0 && fstat(fileno(ft), &st_t) == 0 && fstat(fileno(fq), &st_q) == 0 && S_ISREG(st_t.st_mode) && S_ISREG(st_q.st_mode);
+    const int threaded = !bam && n_rd > 0 && fstat(fileno(ft), &st_t) == 0 && fstat(fileno(fq), &st_q) == 0 && S_ISREG(st_t.st_mode) && S_ISREG(st_q.st_mode);
     int64_t piece = threaded ? 64ll << 20 : 256ll << 20; /* bytes of each file kept in flight */
     if (getenv("CORNETTO_BG_PIECE") && atoll(getenv("CORNETTO_BG_PIECE")) > 0) piece = atoll(getenv("CORNETTO_BG_PIECE"));
     int64_t cut_t[CLI_MAX_DEV], cut_q[CLI_MAX_DEV];
@@ -1167,7 +1187,13 @@ int boringbits_main(int argc, char *argv[], int8_t boring)
     cornetto_ivl_t *fun = NULL;
     int64_t n_recs = 0, n_fun = 0;
     int recs_are_malloced = 0, stage_done = 0;
-    if (runs) {
+    if (bam) { /* the first listed device reads the BAM; the finished coverage object is dealt out below like any other (bb_multi) */
+        h = cli_accel_open_end();
+        if (cli_bam_ingest(h, bam, bam_mapq, &cov, &n_ctg, &names, &n_clamped)) { /* it has said why: the sequential reader of the host path */
+            cornetto_accel_close(h);
+            return host_bits(ft, NULL, &opt, boring, panel_bed, lowq_bed, NULL, bam, bam_mapq);
+        }
+    } else if (runs) {
         h = cli_accel_open_end();
         runs_ingest(h, ft, fq, run_paths, piece, n_rd, &cov, &n_ctg, &names, &n_clamped);
     } else if (threaded) {
@@ -1244,7 +1270,7 @@ int boringbits_main(int argc, char *argv[], int8_t boring)
         cornetto_bgin_close(h, bg);
     }
     fclose(ft);
-    fclose(fq);
+    if (fq) fclose(fq);
     if (n_clamped) CLI_WARNING("%lld depth values were truncated to 65535", (long long)n_clamped);
     if (!stage_done) {
         lens = cornetto_cov_lens(cov);

@@ -234,6 +234,16 @@ void cli_host_get_depths(FILE *ft, FILE *fq, cli_host_cov_t *out);
 void cli_host_get_depths_runs(FILE *ft, FILE *fq, const char *path_t, const char *path_q, cli_host_cov_t *out);
 /* the one CLI_ERROR line of a failed check of the run-length readers (kinds of cornetto_bgrunerr_t), then exit(EXIT_FAILURE) */
 void cli_runs_fail(const char *path, int kind, long long record, int a, int b);
+/* the same from a BAM (`--bam`, an extension): read sequentially through zlib under the rules of cornetto_bamdepth_*() (include/cornetto_accel.h);
+ * contigs without positions are left out, as a per-base bedgraph leaves them out; exits through cli_bam_fail() on a malformed file */
+void cli_host_get_depths_bam(const char *path, int min_mapq, cli_host_cov_t *out);
+/* the one CLI_ERROR line of a failed check of the BAM readers (kinds of cornetto_bamerr_t; 7: no BAM header), then exit(EXIT_FAILURE) */
+void cli_bam_fail(const char *path, int kind, long long record, int a, int b);
+/* cli/bam.c: the BAM through the device (cornetto_bamdepth_*): the compressed file is read a chunk at a time into one pinned slab, its BGZF chain
+ * walked on the host, its blocks fed.  -> 0 with the coverage object (contigs without positions left out) and the malloc'd names; non-zero
+ * when a record is larger than the window or the device has no room for the depth arrays: a CLI_WARNING says which, the caller takes the host
+ * path; exits through cli_bam_fail() on a malformed file */
+int cli_bam_ingest(cornetto_accel_t *h, const char *path, int min_mapq, cornetto_cov_t **cov, int32_t *n_ctg, char ***names, int64_t *n_clamped);
 void cli_host_cov_free(cli_host_cov_t *c);
 /* get_regs() + the predicate of print_fun_bits (boring = 0) / print_boring_bits (1): the rows to print, malloc memory */
 void cli_host_cov_select(const cli_host_cov_t *c, int w, int inc, int32_t lo, int32_t hi, float low_mq, int32_t edge_len, int32_t min_ctg_len, int boring,

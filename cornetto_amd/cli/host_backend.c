@@ -11,6 +11,7 @@
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
+#include <zlib.h>
 
 #include "cli.h"
 
@@ -652,6 +653,231 @@ void cli_host_get_depths_runs(FILE *ft, FILE *fq, const char *path_t, const char
     for (int32_t k = 0; k < b.n_ctg; ++k) free(b.names[k]);
     free(b.names);
     free(b.lens);
+}
+
+/* ------------------------------------------------------------------------------------------------ get_depths, BAM
+ * `--bam` (an extension, see boringbits_main.c and include/cornetto_accel.h for the rules): the file read sequentially through zlib (a
+ * BGZF chain is a multi-member gzip file), one record at a time, the checks of the device reader in their order (csrc/bam.hpp). */
+void cli_bam_fail(const char *path, int kind, long long record, int a, int b)
+{
+    if (kind == 1) {
+        CLI_ERROR("%s: record %lld: block_size %d is below the 32 bytes of the fixed fields", path, record, a);
+    } else if (kind == 2 && record < 0) {
+        CLI_ERROR("%s: the file ends inside the BAM header", path);
+    } else if (kind == 2) {
+        CLI_ERROR("%s: record %lld: the file ends inside the record (%d bytes left, block_size %d)", path, record, a, b);
+    } else if (kind == 3) {
+        CLI_ERROR("%s: record %lld: the fixed fields ask for %d bytes, block_size is %d", path, record, a, b);
+    } else if (kind == 4) {
+        CLI_ERROR("%s: record %lld: refID %d is outside the %d contigs of the header", path, record, a, b);
+    } else if (kind == 5) {
+        CLI_ERROR("%s: record %lld: the CG array of %d operations runs past the record (%d bytes left)", path, record, a, b);
+    } else if (kind == 6) {
+        CLI_ERROR("%s: a BGZF block behind record %lld does not inflate to what its footer says", path, record);
+    } else {
+        CLI_ERROR("%s: not a BAM file", path);
+    }
+    exit(EXIT_FAILURE);
+}
+
+static uint32_t bam_u32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+static int32_t bam_cap31(int64_t v) { return v > 0x7fffffffll ? 0x7fffffff : (int32_t)v; }
+
+/* up to n bytes -> how many there were; a stream zlib cannot inflate: kind 6 */
+static int64_t bam_read(gzFile f, const char *path, long long record, uint8_t *buf, int64_t n)
+{
+    int64_t got = 0;
+    while (got < n) {
+        const int want = n - got > (1 << 30) ? 1 << 30 : (int)(n - got);
+        const int r = gzread(f, buf + got, (unsigned)want);
+        if (r < 0) cli_bam_fail(path, 6, record, 0, 0);
+        if (r == 0) break;
+        got += r;
+    }
+    return got;
+}
+
+/* csrc/bam.hpp: cnb_find_cg */
+static int bam_find_cg(const uint8_t *d, int64_t p, int64_t bs, const uint8_t **cig, int64_t *n_ops, int32_t *a, int32_t *b)
+{
+    while (bs - p >= 3) {
+        const uint8_t t0 = d[p], t1 = d[p + 1], ty = d[p + 2];
+        int64_t sz;
+        p += 3;
+        if (ty == 'A' || ty == 'c' || ty == 'C') sz = 1;
+        else if (ty == 's' || ty == 'S') sz = 2;
+        else if (ty == 'i' || ty == 'I' || ty == 'f') sz = 4;
+        else if (ty == 'Z' || ty == 'H') {
+            while (p < bs && d[p] != 0) ++p;
+            if (p >= bs) return 0;
+            sz = 1;
+        } else if (ty == 'B') {
+            if (bs - p < 5) return 0;
+            const uint8_t sub = d[p];
+            const int64_t cnt = (int64_t)bam_u32(d + p + 1);
+            int64_t es;
+            p += 5;
+            if (sub == 'c' || sub == 'C') es = 1;
+            else if (sub == 's' || sub == 'S') es = 2;
+            else if (sub == 'i' || sub == 'I' || sub == 'f') es = 4;
+            else return 0;
+            if (t0 == 'C' && t1 == 'G' && sub == 'I') {
+                if (cnt * 4 > bs - p) {
+                    *a = bam_cap31(cnt);
+                    *b = (int32_t)(bs - p);
+                    return -1;
+                }
+                *cig = d + p;
+                *n_ops = cnt;
+                return 1;
+            }
+            sz = cnt * es;
+        } else return 0;
+        if (sz > bs - p) return 0;
+        p += sz;
+    }
+    return 0;
+}
+
+void cli_host_get_depths_bam(const char *path, int min_mapq, cli_host_cov_t *out)
+{
+    gzFile f = gzopen(path, "rb");
+    if (!f) {
+        CLI_ERROR("Failed to open %s : No such file or directory.", path);
+        exit(EXIT_FAILURE);
+    }
+    gzbuffer(f, 1 << 20);
+    uint8_t w[8];
+    int64_t got = bam_read(f, path, -1, w, 8);
+    if (got > 0 && gzdirect(f)) cli_bam_fail(path, 7, -1, 0, 0);      /* (zlib hands bytes that are no gzip stream through as they are: no BAM, as on the device) */
+    const size_t n_magic = got < 0 ? 0 : (got < 4 ? (size_t)got : 4);
+    if (memcmp(w, "BAM\1", n_magic) != 0) cli_bam_fail(path, 7, -1, 0, 0);
+    if (got < 8) cli_bam_fail(path, 2, -1, 0, -1);
+    const int32_t l_text = (int32_t)bam_u32(w + 4);
+    if (l_text < 0) cli_bam_fail(path, 7, -1, 0, 0);
+    size_t cap = 1 << 16;
+    uint8_t *buf = (uint8_t *)cli_xmalloc(cap);
+    for (int64_t left = l_text; left > 0;) {
+        const int64_t n = left < (int64_t)cap ? left : (int64_t)cap;
+        if (bam_read(f, path, -1, buf, n) < n) cli_bam_fail(path, 2, -1, 0, -1);
+        left -= n;
+    }
+    if (bam_read(f, path, -1, w, 4) < 4) cli_bam_fail(path, 2, -1, 0, -1);
+    const int32_t n_ref = (int32_t)bam_u32(w);
+    if (n_ref < 0) cli_bam_fail(path, 7, -1, 0, 0);
+    /* every contig of the header, in its order; `all_first` places it in the arrays (a contig without positions has no line in a per-base
+     * bedgraph: it is not a contig of the result) */
+    int32_t *all_len = (int32_t *)cli_xmalloc(((size_t)n_ref + 1) * sizeof(int32_t));
+    int64_t *all_first = (int64_t *)cli_xmalloc(((size_t)n_ref + 1) * sizeof(int64_t));
+    memset(out, 0, sizeof(*out));
+    out->names = (char **)cli_xmalloc(((size_t)n_ref + 1) * sizeof(char *));
+    out->lens = (int32_t *)cli_xmalloc(((size_t)n_ref + 1) * sizeof(int32_t));
+    out->first = (int64_t *)cli_xmalloc(((size_t)n_ref + 2) * sizeof(int64_t));
+    out->first[0] = 0;
+    int64_t n_pos = 0;
+    for (int32_t i = 0; i < n_ref; ++i) {
+        if (bam_read(f, path, -1, w, 4) < 4) cli_bam_fail(path, 2, -1, 0, -1);
+        const int32_t l_name = (int32_t)bam_u32(w);
+        if (l_name < 1) cli_bam_fail(path, 7, -1, 0, 0);
+        if ((size_t)l_name + 4 > cap) buf = (uint8_t *)cli_xrealloc(buf, cap = (size_t)l_name + 4);
+        if (bam_read(f, path, -1, buf, (int64_t)l_name + 4) < (int64_t)l_name + 4) cli_bam_fail(path, 2, -1, 0, -1);
+        const int32_t l_ref = (int32_t)bam_u32(buf + l_name);
+        if (l_ref < 0) cli_bam_fail(path, 7, -1, 0, 0);
+        buf[l_name - 1] = 0;
+        all_len[i] = l_ref;
+        all_first[i] = n_pos;
+        if (l_ref > 0) {
+            out->names[out->n_ctg] = cli_xstrdup((const char *)buf);
+            out->lens[out->n_ctg] = l_ref;
+            out->first[++out->n_ctg] = n_pos + l_ref;
+        }
+        n_pos += l_ref;
+    }
+    int32_t *diff[2];
+    for (int q = 0; q < 2; ++q) {
+        diff[q] = (int32_t *)calloc((size_t)n_pos + 1, sizeof(int32_t));
+        if (!diff[q]) {
+            CLI_ERROR("cannot allocate the depth arrays of %lld positions", (long long)n_pos);
+            exit(EXIT_FAILURE);
+        }
+    }
+    for (long long rec = 0;; ++rec) {
+        got = bam_read(f, path, rec, w, 4);
+        if (got == 0) break;
+        if (got < 4) cli_bam_fail(path, 2, rec, (int)got, -1);
+        const int32_t bs = (int32_t)bam_u32(w);
+        if (bs < 32) cli_bam_fail(path, 1, rec, bs, 0);
+        got = 0;
+        for (int64_t n = 0; got == n && n < bs;) {      /* (the buffer grows with the bytes that are there, not with what block_size says) */
+            if ((size_t)bs > cap && (size_t)n == cap) buf = (uint8_t *)cli_xrealloc(buf, cap = cap * 2 < (size_t)bs ? cap * 2 : (size_t)bs);
+            n = (int64_t)cap < bs ? (int64_t)cap : bs;
+            got += bam_read(f, path, rec, buf + got, n - got);
+        }
+        if (got < bs) cli_bam_fail(path, 2, rec, bam_cap31(got + 4), bs);
+        const int32_t ref_id = (int32_t)bam_u32(buf), pos = (int32_t)bam_u32(buf + 4);
+        const int64_t l_read_name = buf[8], n_cigar = (int64_t)buf[12] | ((int64_t)buf[13] << 8), l_seq = (int64_t)bam_u32(buf + 16);
+        const int mapq = buf[9], flag = (int)buf[14] | ((int)buf[15] << 8);
+        const int64_t fixed = 32 + l_read_name + 4 * n_cigar + (l_seq + 1) / 2 + l_seq;
+        if (fixed > bs) cli_bam_fail(path, 3, rec, bam_cap31(fixed), bs);
+        if (ref_id < -1 || ref_id >= n_ref) cli_bam_fail(path, 4, rec, ref_id, n_ref);
+        if (ref_id < 0 || (flag & 0x704) != 0) continue;
+        const uint8_t *cig = buf + 32 + l_read_name;
+        int64_t n_ops = n_cigar;
+        if (n_cigar == 2) {
+            const uint32_t op0 = bam_u32(cig), op1 = bam_u32(cig + 4);
+            int32_t a = 0, b = 0;
+            if ((op0 & 15u) == 4u && (int64_t)(op0 >> 4) == l_seq && (op1 & 15u) == 3u && bam_find_cg(buf, fixed, bs, &cig, &n_ops, &a, &b) < 0)
+                cli_bam_fail(path, 5, rec, a, b);
+        }
+        const int64_t len = all_len[ref_id], base = all_first[ref_id];
+        int64_t at = pos;
+        for (int64_t i = 0; i < n_ops; ++i) {
+            const uint32_t op = bam_u32(cig + 4 * i), k = op & 15u;
+            const int64_t n = op >> 4;
+            if (k == 0 || k == 7 || k == 8) {
+                int64_t s = at, e = at + n;
+                s = s < 0 ? 0 : (s > len ? len : s);
+                e = e < 0 ? 0 : (e > len ? len : e);
+                if (s < e) {
+                    diff[0][base + s]++;
+                    diff[0][base + e]--;
+                    if (mapq >= min_mapq) {
+                        diff[1][base + s]++;
+                        diff[1][base + e]--;
+                    }
+                }
+                at += n;
+            } else if (k == 2 || k == 3) {
+                at += n;
+            }
+        }
+    }
+    gzclose(f);
+    free(buf);
+    free(all_len);
+    free(all_first);
+    out->depth = (uint16_t *)cli_xmalloc(((size_t)n_pos + 1) * sizeof(uint16_t));
+    out->mq = (uint16_t *)cli_xmalloc(((size_t)n_pos + 1) * sizeof(uint16_t));
+    for (int q = 0; q < 2; ++q) {
+        uint16_t *dst = q ? out->mq : out->depth;
+        double sum = 0.0;
+        int64_t run = 0;
+        for (int64_t i = 0; i < n_pos; ++i) {
+            run += diff[q][i];
+            int64_t v = run;
+            if (v > 65535) {
+                v = 65535;
+                out->n_clamped++;
+            }
+            dst[i] = (uint16_t)v;
+            sum += (double)v;
+        }
+        if (q) out->sum_mq = sum;
+        else out->sum_depth = sum;
+        free(diff[q]);
+    }
+    out->n_pos = n_pos;
+    out->positions = (double)n_pos;
 }
 
 void cli_host_cov_free(cli_host_cov_t *c)

@@ -554,6 +554,87 @@ int cornetto_text_inflate(cornetto_accel_t *h, cornetto_text_t *comp, cornetto_t
 int cornetto_text_gather(cornetto_accel_t *h, cornetto_text_t *t, const int64_t *at, const int32_t *len, int64_t n, char *dst);
 
 /* ---------------------------------------------------------------------------------------------------
+ * BAM: both per-base coverage tracks from a coordinate-sorted or unsorted BAM on the device: `(no)boringbits --bam`.  An EXTENSION (the
+ * reference's `depth` sub-command is a stub; the protocol runs `samtools depth -aa` and `samtools depth -Q 20 -aa` through awk).  The rules,
+ * a restatement of those two commands:
+ *   - contigs, their order and lengths: the binary reference list of the header; every contig appears, with or without reads;
+ *   - a record counts iff refID >= 0 and (flag & skip_flags) == 0 (0x704: UNMAP, SECONDARY, QCFAIL, DUP); it counts in the second track iff
+ *     also mapq >= min_mapq;
+ *   - its CIGAR is walked from pos: M = X count and advance, D N advance, I S H P (and the op codes 9-15) do neither; positions are cut to
+ *     [0, contig length); n_cigar_op == 0 covers nothing;
+ *   - n_cigar_op == 2 with the ops `<l_seq>S <x>N`: the CIGAR is the CG:B,I array of the auxiliary fields if there is one;
+ *   - depth above 65535 is stored as 65535 and counted (n_clamped).  No base-quality filter, no overlap handling.
+ * ------------------------------------------------------------------------------------------------- */
+
+/* The header of a BAM in buf[0 .. n), the first inflated bytes of the file.  Host only.  CORNETTO_OK: *n_ref contigs with names[i]
+ * (malloc: free every name, then the array) and lens[i] (malloc), *header_bytes = where the first record begins.  1: the header goes on
+ * behind buf, hand over more bytes (nothing is allocated).  CORNETTO_E_FORMAT: not a BAM header (magic, a negative count or length). */
+int cornetto_bam_header(const uint8_t *buf, int64_t n, int32_t *n_ref, char ***names, int32_t **lens, int64_t *header_bytes);
+
+typedef struct {
+    int32_t min_mapq;    /* second track: mapq >= this (20) */
+    uint32_t skip_flags; /* a record with one of these flag bits does not count (0x704) */
+    int64_t window;      /* bytes of inflated BAM held on the device at once: an operating parameter, never changes a result.  It must hold
+                            the largest record and one BGZF block more (CORNETTO_E_NOMEM otherwise) */
+    int32_t records;     /* 0: depth only; 1: also keep the record table (cornetto_bam_records); 2: the record table only — no depth array is
+                            allocated and cornetto_bamdepth_finish() returns no coverage object */
+    int32_t pad;
+} cornetto_bamdepth_opt_t;
+void cornetto_bamdepth_defaults(cornetto_bamdepth_opt_t *opt);
+
+/* which check failed; the record with the smallest index decides, within a record the order below */
+typedef struct {
+    int32_t kind;   /* 1: block_size < 32 (a = block_size)
+                       2: the file ends inside a record (a = bytes left, b = the record's block_size, -1 if that is cut off too); the callers
+                          of cornetto_bam_header() report a file that ends inside its header as kind 2 of record -1, and bytes that are no BAM
+                          header as kind 7
+                       3: the fixed fields say more than block_size: 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq (a, capped at
+                          2^31-1) > block_size (b)
+                       4: refID (a) outside [-1, n_ref (b))
+                       5: the CG:B,I array of a long-CIGAR record has more elements (a, capped) than the record has room for (b, bytes)
+                       6: BGZF block a of the file (counted from 0 over all feeds) is not what its footer says; every record that lies
+                          wholly in front of it has passed its checks; record = the number of those records */
+    int32_t a, b;
+    int32_t pad;
+    int64_t record; /* 0-based index of the record in the file */
+} cornetto_bamerr_t;
+
+/* one record as the depth kernel read it */
+typedef struct {
+    int64_t offset;  /* of its block_size field in the inflated file */
+    int32_t ref_id, pos, mapq, flag;
+    int32_t counted; /* 1 if it counts in the first track */
+    int32_t n_ops;   /* CIGAR operations walked (those of the CG array for a long-CIGAR record); 0 for a record that does not count */
+    int64_t span;    /* reference bases its CIGAR advances over (0 for a record that does not count: its CIGAR is not walked) */
+    int64_t bases;   /* positions it adds one to: its M = X bases inside [0, contig length) */
+} cornetto_bamrec_t;
+
+/* positions per workgroup of the scan kernel (tests plant contig and read ends at its multiples) */
+#define CORNETTO_BAM_SCAN_TILE 4096
+int32_t cornetto_bam_scan_tile(void);
+
+typedef struct cornetto_bamdepth cornetto_bamdepth_t;
+/* lens[0 .. n_ref): the contig lengths of the header.  Allocates two int32 difference arrays over all contigs (records != 2). */
+int cornetto_bamdepth_open(cornetto_accel_t *h, const cornetto_bamdepth_opt_t *opt, const int32_t *lens, int32_t n_ref, cornetto_bamdepth_t **out);
+void cornetto_bamdepth_close(cornetto_accel_t *h, cornetto_bamdepth_t *b);
+/* The next BGZF blocks of the file, in file order: `comp` holds their deflate streams at blocks[i].src (offsets into `comp`; dst is
+ * ignored: the blocks follow each other), put there with cornetto_text_put().  skip: inflated bytes to pass over before the first record
+ * (the header: cornetto_bam_header()), counted from the first block of the file: only a feed in front of the first record may skip
+ * (CORNETTO_E_ARG afterwards).  Blocks are inflated a window at a time
+ * (cornetto_text_inflate), records framed (bam_frame) and their CIGARs walked into the difference arrays (bam_depth); the bytes behind the
+ * last whole record of a window stay in front of the next one, across feeds too.  Synchronous: `comp` may be overwritten on return. */
+int cornetto_bamdepth_feed(cornetto_accel_t *h, cornetto_bamdepth_t *b, cornetto_text_t *comp, const cornetto_bgzf_block_t *blocks, int64_t n_blocks,
+                           int64_t skip);
+const cornetto_bamerr_t *cornetto_bamdepth_error(const cornetto_bamdepth_t *b);
+/* After the last feed (a file that ends inside a record: kind 2): the difference arrays are scanned and clamped (bam_scan) into the
+ * coverage object cornetto_cov_wrap() makes, ready for cornetto_cov_prepare().  n_records: records of the file; n_counted: those that count
+ * in the first track; n_clamped: positions above 65535 in either track.  Any of the three may be NULL. */
+int cornetto_bamdepth_finish(cornetto_accel_t *h, cornetto_bamdepth_t *b, cornetto_cov_t **cov, int64_t *n_records, int64_t *n_counted,
+                             int64_t *n_clamped);
+/* The record table of the feeds so far (opt.records != 0), in file order: cornetto_free(). */
+int cornetto_bam_records(cornetto_accel_t *h, cornetto_bamdepth_t *b, cornetto_bamrec_t **recs, int64_t *n_recs);
+
+/* ---------------------------------------------------------------------------------------------------
  * fixasm output text: the records of a resident assembly, renamed and reoriented
  * ------------------------------------------------------------------------------------------------- */
 
