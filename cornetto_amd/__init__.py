@@ -35,7 +35,32 @@ REGPK_DT = np.dtype([("st", "<i4"), ("depth", "<u2"), ("mq_depth", "<u2")])
 
 
 class BgErr(C.Structure):
-    _fields_ = [("kind", C.c_int32), ("record", C.c_int64), ("a", C.c_int32), ("b", C.c_int32)]
+    """cornetto_bgerr_t (include/cornetto_accel.h); `file` stands where the padding in front of `record` was"""
+    _fields_ = [("kind", C.c_int32), ("file", C.c_int32), ("record", C.c_int64), ("a", C.c_int32), ("b", C.c_int32)]
+
+
+class BgSrc(C.Structure):
+    """cornetto_bgsrc_t (include/cornetto_accel.h)"""
+    _fields_ = [("text", C.c_char_p), ("n", C.c_int64), ("comp", C.c_void_p), ("blocks", C.c_void_p), ("n_blocks", C.c_int64)]
+
+
+BG_BLOCK = 11  # kind of a damaged BGZF block in cornetto_bgerr_t / cornetto_bgrunerr_t
+
+
+class Bgzf:
+    """one depth file of Accel.bedgraph_ingest_src() / bedgraph_runs_ingest_src() as a BGZF blob: its blocks are handed over `per_feed` at a
+    time (an int, or a list with the number of blocks of every feed, zeros allowed; what the list leaves over goes into one more feed)"""
+
+    def __init__(self, blob, per_feed=1):
+        self.blob, self.per_feed = bytes(blob), per_feed
+
+    def counts(self, n_blocks):
+        if isinstance(self.per_feed, int):
+            k = max(1, self.per_feed)
+            return [min(k, n_blocks - i) for i in range(0, n_blocks, k)] or [0]
+        c = [int(x) for x in self.per_feed]
+        assert sum(c) <= n_blocks
+        return c + ([n_blocks - sum(c)] if sum(c) < n_blocks else [])
 
 
 class BgRunErr(C.Structure):
@@ -206,6 +231,8 @@ def lib(dev=False):
         "cornetto_bgrun_feed": (C.c_int, [vp, vp, C.c_int, cp, i64, C.c_int]),
         "cornetto_bgrun_error": (C.POINTER(BgRunErr), [vp]),
         "cornetto_bgrun_finish": (C.c_int, [vp, vp, pp, C.POINTER(i32), C.POINTER(C.POINTER(cp)), C.POINTER(i64)]),
+        "cornetto_bgin_feed_src": (C.c_int, [vp, vp, C.POINTER(BgSrc), C.POINTER(BgSrc), C.c_int]),
+        "cornetto_bgrun_feed_src": (C.c_int, [vp, vp, C.c_int, C.POINTER(BgSrc), C.c_int]),
         "cornetto_cov_download": (C.c_int, [vp, vp, i32, vp, vp]),
         "cornetto_bam_header": (C.c_int, [vp, i64, C.POINTER(i32), C.POINTER(C.POINTER(cp)), C.POINTER(C.POINTER(i32)), C.POINTER(i64)]),
         "cornetto_bamdepth_defaults": (None, [C.POINTER(BamDepthOpt)]),
@@ -926,6 +953,89 @@ class Accel:
             return self._ingested(cov, nc, names, ncl)
         finally:
             L.cornetto_bgrun_close(self.h, bg)
+
+    # ---- bedgraph ingest from sources (cornetto_bgsrc_t): plain pieces or the blocks of a BGZF blob ---------------------------------
+    def _src_feeds(self, f, texts):
+        """a depth file (a list of bytes pieces, or a Bgzf) -> its feeds: BgSrc structures with whatever they point to kept alive beside them"""
+        if not isinstance(f, Bgzf):
+            return [(BgSrc(p, len(p), None, None, 0), p) for p in (list(f) or [b""])]
+        blocks, resume, broken = bgzf_scan(f.blob)
+        if broken or resume != len(f.blob):
+            raise ValueError("not a chain of BGZF members")
+        comp = self._text_from(f.blob)
+        texts.append(comp)
+        out, at = [], 0
+        for k in f.counts(len(blocks)):
+            part = np.ascontiguousarray(blocks[at:at + k])
+            at += k
+            out.append((BgSrc(None, 0, comp, part.ctypes.data if k else None, k), part))
+        return out
+
+    def bedgraph_ingest_src(self, tot, mq, pending=None):
+        """bedgraph_ingest() through cornetto_bgin_feed_src(): each of tot / mq is a list of bytes pieces (plain text) or a Bgzf (the file as a
+        BGZF blob, inflated on the device); feed i takes piece / block group i of both.  pending: a list that receives
+        cornetto_bgin_pending() after every feed.  Raises BedgraphFormatError (kind 11: a damaged block; file, record = its index).  The
+        kernel times of all feeds are kept in self.bg_timing."""
+        L = self.L
+        bg, texts = C.c_void_p(), []
+        self.bg_timing = []
+        self._chk(L.cornetto_bgin_open(self.h, C.byref(bg)))
+        try:
+            ft, fq = self._src_feeds(tot, texts), self._src_feeds(mq, texts)
+            n_t, n_q = len(ft), len(fq)
+            nothing = (BgSrc(None, 0, None, None, 0), None)
+            for i in range(max(n_t, n_q)):
+                t, q = ft[i] if i < n_t else nothing, fq[i] if i < n_q else nothing
+                fin = (1 if i >= n_t - 1 else 0) | (2 if i >= n_q - 1 else 0)
+                rc = L.cornetto_bgin_feed_src(self.h, bg, C.byref(t[0]), C.byref(q[0]), fin)
+                self.bg_timing += self.last_timing()
+                if rc == -6:
+                    e = L.cornetto_bgin_error(bg).contents
+                    raise BedgraphFormatError(e.kind, e.record, e.a, e.b, e.file if e.kind == BG_BLOCK else None)
+                self._chk(rc)
+                if pending is not None:
+                    a, b = C.c_int64(), C.c_int64()
+                    L.cornetto_bgin_pending(bg, C.byref(a), C.byref(b))
+                    pending.append((a.value, b.value))
+                if L.cornetto_bgin_done(bg):
+                    break
+            cov, nc, names, ncl = C.c_void_p(), C.c_int32(), C.POINTER(C.c_char_p)(), C.c_int64()
+            self._chk(L.cornetto_bgin_finish(self.h, bg, C.byref(cov), C.byref(nc), C.byref(names), C.byref(ncl)))
+            return self._ingested(cov, nc, names, ncl)
+        finally:
+            L.cornetto_bgin_close(self.h, bg)
+            for t in texts:
+                L.cornetto_text_free(self.h, t)
+
+    def bedgraph_runs_ingest_src(self, tot, mq, alternate=True):
+        """bedgraph_runs_ingest() through cornetto_bgrun_feed_src(): each of tot / mq is a list of bytes pieces or a Bgzf"""
+        L = self.L
+        bg, texts = C.c_void_p(), []
+        self.bg_timing = []
+        self._chk(L.cornetto_bgrun_open(self.h, C.byref(bg)))
+        try:
+            feeds = [self._src_feeds(tot, texts), self._src_feeds(mq, texts)]
+            if alternate:
+                order = sorted((i, f) for f in (0, 1) for i in range(len(feeds[f])))
+            else:
+                order = [(i, f) for f in (0, 1) for i in range(len(feeds[f]))]
+
+            def check(rc):
+                if rc == -6:
+                    e = L.cornetto_bgrun_error(bg).contents
+                    raise BedgraphFormatError(e.kind, e.record, e.a, e.b, e.file)
+                self._chk(rc)
+            for i, f in order:
+                rc = L.cornetto_bgrun_feed_src(self.h, bg, f, C.byref(feeds[f][i][0]), 1 if i == len(feeds[f]) - 1 else 0)
+                self.bg_timing += self.last_timing()
+                check(rc)
+            cov, nc, names, ncl = C.c_void_p(), C.c_int32(), C.POINTER(C.c_char_p)(), C.c_int64()
+            check(L.cornetto_bgrun_finish(self.h, bg, C.byref(cov), C.byref(nc), C.byref(names), C.byref(ncl)))
+            return self._ingested(cov, nc, names, ncl)
+        finally:
+            L.cornetto_bgrun_close(self.h, bg)
+            for t in texts:
+                L.cornetto_text_free(self.h, t)
 
     def bedgraph_ingest(self, tot_pieces, mq_pieces, prefetch=0):
         """stream the two per-base bedgraphs (iterables of bytes pieces, any split points) through the device

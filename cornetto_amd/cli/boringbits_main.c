@@ -63,6 +63,7 @@ static void print_help(FILE *fp, const optp_t *o)
     fprintf(fp, "   --bam-mapq INT             (extension) mapping quality of the second track of --bam [20]\n");
     fprintf(fp, "   --runs                     (extension) the depth files are run-length bedgraphs: name start end value,\n");
     fprintf(fp, "                              one record per run (mosdepth, bedtools genomecov -bga); contigs start at 0, no gaps\n");
+    fprintf(fp, "                              (extension) either depth file may be bgzip or gzip compressed, with or without --runs\n");
     fprintf(fp, "   --hap FILE                 (extension, with --panel) PAF of a haplotype assembly against the primary one, 1 to %d times:\n", HP_MAX);
     fprintf(fp, "                              print the diploid boring bits (scripts/create-hapnetto.sh)\n");
     fprintf(fp, "   --dip FILE                 (extension, with --hap) the diploid boring bits go to FILE, stdout stays the primary panel\n");
@@ -524,6 +525,103 @@ static void runs_ingest(cornetto_accel_t *h, FILE *ft, FILE *fq, const char *con
     cornetto_bgrun_close(h, bg);
     cornetto_pinned_free(slab[0]);
     cornetto_pinned_free(slab[1]);
+}
+
+/* ---------------- a pair of depth files of which at least one is BGZF: inflated on the device (cornetto_bg*_feed_src) ----------------
+ * The compressed bytes of a BGZF file cross the bus (cli_bgz_*: pread() threads fill one pinned slab while the blocks of the other are fed), its
+ * text exists on the device only.  A file that is not BGZF — text, a FIFO, a gzip file behind its zlib stream — is read with fread() into a
+ * pinned piece and goes into the same feeds as plain bytes.  A round takes as many whole blocks as inflate to at most `piece` bytes; the
+ * per-base reader tops both files up to the same number of pending bytes, as the sequential loop of boringbits_main() does. */
+/* the next bytes of a file, `want` of them at most (of a BGZF file: whole blocks, one at least); *last: nothing follows */
+static void comp_next(cornetto_accel_t *h, cli_bgz_t *z, char *buf, FILE *fp, const char *path, int64_t want, cornetto_bgsrc_t *src, int *last)
+{
+    if (z) {
+        (void)cli_bgz_next(h, z, want, src, last);
+        return;
+    }
+    const size_t got = fread(buf, 1, (size_t)want, fp);
+    if (got < (size_t)want && ferror(fp)) {
+        CLI_ERROR("reading %s failed", path);
+        exit(EXIT_FAILURE);
+    }
+    memset(src, 0, sizeof(*src));
+    src->text = buf;
+    src->n = (int64_t)got;
+    *last = got < (size_t)want;
+}
+
+static void comp_ingest(cornetto_accel_t *h, FILE *const fp[2], const int kind[2], const char *const *paths, int64_t piece, int n_rd, int runs,
+                        cornetto_cov_t **cov, int32_t *n_ctg, char ***names, int64_t *n_clamped)
+{
+    cli_bgz_t *z[2] = {NULL, NULL};
+    char *buf[2] = {NULL, NULL};
+    int64_t slab = piece / 4; /* (bedgraph text shrinks several-fold: a slab of compressed bytes is about a round of text) */
+    if (slab > (64ll << 20)) slab = 64ll << 20;
+    for (int f = 0; f < 2; ++f) {
+        if (kind[f] == 1) z[f] = cli_bgz_open(h, paths[f], fileno(fp[f]), slab, n_rd);
+        else if (!(buf[f] = (char *)cornetto_pinned_alloc((size_t)piece))) {
+            CLI_ERROR("%s", "cannot allocate pinned read buffers");
+            exit(EXIT_FAILURE);
+        }
+    }
+    if (runs) {
+        cornetto_bgrun_t *bg = NULL;
+        cli_accel_check(h, cornetto_bgrun_open(h, &bg), "run-length bedgraph ingest");
+        int rc = CORNETTO_OK;
+        for (int f = 0; f < 2 && rc == CORNETTO_OK; ++f)
+            for (int last = 0; !last && rc == CORNETTO_OK;) {
+                cornetto_bgsrc_t src;
+                comp_next(h, z[f], buf[f], fp[f], paths[f], piece, &src, &last);
+                rc = cornetto_bgrun_feed_src(h, bg, f, &src, last);
+            }
+        if (rc == CORNETTO_OK) rc = cornetto_bgrun_finish(h, bg, cov, n_ctg, names, n_clamped);
+        if (rc == CORNETTO_E_FORMAT) {
+            const cornetto_bgrunerr_t *e = cornetto_bgrun_error(bg);
+            if (e->kind == 11) cli_bgz_fail_block(z[e->file], (long long)e->record);
+            cli_runs_fail(paths[e->file], e->kind, (long long)e->record, e->a, e->b);
+        }
+        cli_accel_check(h, rc, "run-length bedgraph ingest");
+        cornetto_bgrun_close(h, bg);
+    } else {
+        cornetto_bgin_t *bg = NULL;
+        cli_accel_check(h, cornetto_bgin_open(h, &bg), "bedgraph ingest");
+        int eof[2] = {0, 0};
+        while (!cornetto_bgin_done(bg)) {
+            int64_t pend[2] = {0, 0};
+            cornetto_bgin_pending(bg, &pend[0], &pend[1]);
+            /* top both files up to the same number of pending bytes, so the unmatched tail of either stays small */
+            const int64_t least = piece < 4096 ? piece : 4096;
+            cornetto_bgsrc_t src[2];
+            memset(src, 0, sizeof(src));
+            for (int f = 0; f < 2; ++f) {
+                if (eof[f]) continue;
+                const int64_t want = pend[f] < piece - least ? piece - pend[f] : least;
+                comp_next(h, z[f], buf[f], fp[f], paths[f], want, &src[f], &eof[f]);
+            }
+            const int rc = cornetto_bgin_feed_src(h, bg, &src[0], &src[1], eof[0] | (eof[1] << 1));
+            if (rc == CORNETTO_E_FORMAT) {
+                const cornetto_bgerr_t *e = cornetto_bgin_error(bg);
+                if (e->kind == 11) cli_bgz_fail_block(z[e->file], (long long)e->record);
+                bg_job_t g;
+                memset(&g, 0, sizeof(g));
+                g.fmt_kind = e->kind ? e->kind : 5;
+                g.fmt_a = e->a;
+                g.fmt_b = e->b;
+                bg_job_check(&g, paths[0], paths[1]);
+            }
+            cli_accel_check(h, rc, "bedgraph ingest");
+            if (eof[0] && eof[1] && !cornetto_bgin_done(bg)) { /* cannot happen: the final feed either finishes or fails */
+                CLI_ERROR("%s", "bedgraph ingest did not finish");
+                exit(EXIT_FAILURE);
+            }
+        }
+        cli_accel_check(h, cornetto_bgin_finish(h, bg, cov, n_ctg, names, n_clamped), "bedgraph ingest");
+        cornetto_bgin_close(h, bg);
+    }
+    for (int f = 0; f < 2; ++f) {
+        cli_bgz_close(h, z[f]);
+        cornetto_pinned_free(buf[f]);
+    }
 }
 
 /* ---------------- where to cut two per-base bedgraphs into shares of whole contigs ----------------
@@ -1143,6 +1241,24 @@ int boringbits_main(int argc, char *argv[], int8_t boring)
         exit(EXIT_FAILURE);
     }
     const char *const run_paths[2] = {covtotal, covmq};
+    /* Compressed depth files (regular files only, told by their first bytes).  BGZF is inflated on the device (comp_ingest); a gzip file that is
+     * not BGZF, every compressed file of the host path, and BGZF under $CORNETTO_BGZF=0 (an operating parameter: it never changes a result) go
+     * through zlib on this thread and are read as the text they hold by the code that reads text. */
+    int zkind[2] = {0, 0};
+    if (!bam) {
+        const int on_device = !cli_host_mode() && !(getenv("CORNETTO_BGZF") && !atoi(getenv("CORNETTO_BGZF")));
+        zkind[0] = cli_depth_kind(ft);
+        zkind[1] = cli_depth_kind(fq);
+        if (zkind[0] && !(zkind[0] == 1 && on_device)) {
+            ft = cli_zfile_open(covtotal, ft, zkind[0]);
+            zkind[0] = 0;
+        }
+        if (zkind[1] && !(zkind[1] == 1 && on_device)) {
+            fq = cli_zfile_open(covmq, fq, zkind[1]);
+            zkind[1] = 0;
+        }
+    }
+    const int on_device_bgzf = zkind[0] == 1 || zkind[1] == 1;
     if (cli_host_mode()) return host_bits(ft, fq, &opt, boring, panel_bed, lowq_bed, runs ? run_paths : NULL, bam, bam_mapq);
     int devs[CLI_MAX_DEV];
     const int n_dev = cli_device_list(devs);
@@ -1159,8 +1275,10 @@ int boringbits_main(int argc, char *argv[], int8_t boring)
     struct stat st_t, st_q;
     int n_rd = 8;
     if (getenv("CORNETTO_BG_THREADS")) n_rd = atoi(getenv("CORNETTO_BG_THREADS"));
-    const int threaded = !bam && n_rd > 0 && fstat(fileno(ft), &st_t) == 0 && fstat(fileno(fq), &st_q) == 0 && S_ISREG(st_t.st_mode) && S_ISREG(st_q.st_mode);
-    int64_t piece = threaded ? 64ll << 20 : 256ll << 20; /* bytes of each file kept in flight */
+    const int threaded = !bam && !on_device_bgzf && n_rd > 0 && fstat(fileno(ft), &st_t) == 0 && fstat(fileno(fq), &st_q) == 0 && S_ISREG(st_t.st_mode) && S_ISREG(st_q.st_mode);
+    int64_t piece = threaded ? 64ll << 20 : 256ll << 20; /* bytes of each file kept in flight (of a BGZF file: inflated bytes — a wave inflates a
+                                                           * block, and a round of 256 MB is a launch of four thousand of them: 64 MB rounds were 0.1 s
+                                                           * slower on a pair of 1.5 GB) */
     if (getenv("CORNETTO_BG_PIECE") && atoll(getenv("CORNETTO_BG_PIECE")) > 0) piece = atoll(getenv("CORNETTO_BG_PIECE"));
     int64_t cut_t[CLI_MAX_DEV], cut_q[CLI_MAX_DEV];
     int n_sh = 1;
@@ -1193,6 +1311,10 @@ int boringbits_main(int argc, char *argv[], int8_t boring)
             cornetto_accel_close(h);
             return host_bits(ft, NULL, &opt, boring, panel_bed, lowq_bed, NULL, bam, bam_mapq);
         }
+    } else if (on_device_bgzf) { /* (a compressed file cannot be cut between devices: the first one ingests, bb_multi() deals the coverage out below) */
+        FILE *const fps[2] = {ft, fq};
+        h = cli_accel_open_end();
+        comp_ingest(h, fps, zkind, run_paths, piece, n_rd, runs, &cov, &n_ctg, &names, &n_clamped);
     } else if (runs) {
         h = cli_accel_open_end();
         runs_ingest(h, ft, fq, run_paths, piece, n_rd, &cov, &n_ctg, &names, &n_clamped);

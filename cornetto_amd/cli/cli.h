@@ -245,6 +245,26 @@ void cli_bam_fail(const char *path, int kind, long long record, int a, int b);
  * path; exits through cli_bam_fail() on a malformed file */
 int cli_bam_ingest(cornetto_accel_t *h, const char *path, int min_mapq, cornetto_cov_t **cov, int32_t *n_ctg, char ***names, int64_t *n_clamped);
 void cli_host_cov_free(cli_host_cov_t *c);
+
+/* ---- cli/bgcomp.c: compressed depth files of (no)boringbits (mosdepth writes *.per-base.bed.gz, which is BGZF) ---- */
+int cli_bgzf_first_member(int fd);   /* is what begins the file a BGZF member? */
+/* what a depth file is, by its first bytes: 0 anything that is read as it is (not a regular file: never looked at; or no gzip magic), 1 BGZF, 2 another gzip */
+int cli_depth_kind(FILE *fp);
+/* The file through zlib on this thread: a FILE * (fopencookie) that hands out the inflated bytes, for the readers that take a FILE *.  kind 1: the BGZF
+ * chain is walked block by block (raw inflate, CRC-32 and ISIZE of every footer), kind 2: gzread().  Takes `fp` over (closed with the new one).  What
+ * is wrong with the file is one CLI_ERROR line that names it (a BGZF block with its index and offset), then exit(EXIT_FAILURE). */
+FILE *cli_zfile_open(const char *path, FILE *fp, int kind);
+/* the one CLI_ERROR line of a BGZF file that is not one to its end, then exit(EXIT_FAILURE).  what 0: the block is not what its footer says,
+ * 1: what begins there is not a BGZF member, 2: the file ends inside the block */
+void cli_bgz_fail(const char *path, int what, long long index, long long offset);
+/* A BGZF file for the device readers: pread() threads fill one pinned slab with compressed bytes while the blocks of the other are fed; the chain is
+ * walked on the host (cornetto_bgzf_scan), a block cut by the end of a slab opens the next one.  cli_bgz_next(): the next whole blocks that inflate
+ * to at most `want` bytes (one block at least) as a source of the cornetto_bg*_feed_src() calls -> their inflated bytes; *last: nothing follows. */
+typedef struct cli_bgz cli_bgz_t;
+cli_bgz_t *cli_bgz_open(cornetto_accel_t *h, const char *path, int fd, int64_t slab_bytes, int n_rd);
+int64_t cli_bgz_next(cornetto_accel_t *h, cli_bgz_t *z, int64_t want, cornetto_bgsrc_t *src, int *last);
+void cli_bgz_fail_block(const cli_bgz_t *z, long long index);   /* cli_bgz_fail(.., 0, ..) for block `index` of the file, one of the last source */
+void cli_bgz_close(cornetto_accel_t *h, cli_bgz_t *z);
 /* get_regs() + the predicate of print_fun_bits (boring = 0) / print_boring_bits (1): the rows to print, malloc memory */
 void cli_host_cov_select(const cli_host_cov_t *c, int w, int inc, int32_t lo, int32_t hi, float low_mq, int32_t edge_len, int32_t min_ctg_len, int boring,
                          cornetto_regrec_t **recs, int64_t *n_recs);

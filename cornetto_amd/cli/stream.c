@@ -462,19 +462,6 @@ static void bgzf_fallback(stream_t *s, const char *why)
     if (s->trace) fprintf(stderr, "[cli trace] bgzf: fallback (%s)\n", why);
 }
 
-/* is what begins the file a BGZF member? */
-static int bgzf_first_member(int fd)
-{
-    uint8_t *head = (uint8_t *)cli_xmalloc(65536);
-    const int64_t have = cli_read_at(fd, (char *)head, 65536, 0, NULL);
-    cornetto_bgzf_block_t b;
-    int64_t dst = 0, n = 0, resume = 0;
-    int32_t broken = 0;
-    const int ok = have > 0 && cornetto_bgzf_scan(head, have, 0, &dst, &b, 1, &n, &resume, &broken) == CORNETTO_OK && n == 1;
-    free(head);
-    return ok;
-}
-
 /* the names of the text's records, packed on the device and copied once -> r[0 .. nrec), its names in *names_out */
 static cli_recname_t *bgzf_names(stream_t *s, const cornetto_farec_t *recs, int64_t nrec, char **names_out)
 {
@@ -625,7 +612,7 @@ static void stream_run(stream_t *s, int must_open)
         int bz = 0;
         if (whole && s->raw_fd < 0 && strcmp(s->path, "-") && !gzdirect(s->fp) && !(be && !atoi(be)) && stat(s->path, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0) {
             const int fd = open(s->path, O_RDONLY);
-            const int is_bgzf = fd >= 0 && bgzf_first_member(fd);
+            const int is_bgzf = fd >= 0 && cli_bgzf_first_member(fd);
             if (fd >= 0) close(fd);
             if (!is_bgzf) bgzf_fallback(s, "not BGZF");
             else if (!fasta) bgzf_fallback(s, "not FASTA");

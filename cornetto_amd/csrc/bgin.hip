@@ -14,7 +14,9 @@
 //                          contig iff its name differs from the previous record's; the expected start is 1 after a
 //                          contig start and previous start + 1 otherwise), so no sequential state is needed.
 // The host side streams arbitrary pieces of the two files: unconsumed tail bytes and the last two consumed
-// records (context for the local rules) are carried to the next piece.
+// records (context for the local rules) are carried to the next piece.  A piece is plain bytes from the host or the next BGZF blocks of the
+// file (cornetto_bgsrc_t): those are inflated behind the carry in the text workspace itself (bgtok.hpp: bgsrc_inflate), and from a file's
+// first compressed source on its carry stays on the device (BgCarry).
 #include <algorithm>
 #include <string>
 
@@ -127,7 +129,9 @@ __global__ __launch_bounds__(256) void bg_records(BgArgs A)
 
 struct cornetto_bgin {
     std::string pend[2];           // per file: context records (already consumed) + bytes not yet consumed
-    int32_t ctx = 0;               // context records at the head of pend[]
+    BgCarry dc[2];                 // ... on the device instead, from the file's first compressed source on (cornetto_bgin_feed_src)
+    int64_t n_pend(int f) const { return dc[f].on ? dc[f].n : (int64_t)pend[f].size(); }
+    int32_t ctx = 0;             // context records at the head of pend[]
     bool started = false;          // at least one record consumed
     int64_t n_rec = 0;             // records consumed so far
     uint16_t *d_a = nullptr, *d_b = nullptr;
@@ -137,7 +141,7 @@ struct cornetto_bgin {
     unsigned long long n_clamp = 0;
     unsigned long long neg_corr[2] = {0, 0};   // (see BgArgs::neg_corr)
     std::vector<unsigned long long> neg;       // {record index << 1 | file, difference} of every negative value (BgArgs::neg_list)
-    cornetto_bgerr_t err{0, 0, 0, 0};
+    cornetto_bgerr_t err{0, 0, 0, 0, 0};
     bool finished = false;
     int64_t left_mq = 0;      // tokens of cov-mq behind the last record when cov-total ended (the reference never looks at them: :204-207)
     // cornetto_bgin_prefetch(): the pieces of the feeds to come on their way to the device while this feed's kernels run — two staging sets: one
@@ -182,6 +186,7 @@ void cornetto_bgin_close(cornetto_accel_t *h, cornetto_bgin_t *b)
     if (h) (void)hipSetDevice(h->device);
     if (b->d_a) (void)hipFree(b->d_a);
     if (b->d_b) (void)hipFree(b->d_b);
+    for (auto &c : b->dc) c.release();
     if (b->pf_stream) { (void)hipStreamSynchronize(b->pf_stream); (void)hipStreamDestroy(b->pf_stream); }
     for (auto &st : b->pf) {
         if (st.ev) (void)hipEventDestroy(st.ev);
@@ -228,8 +233,8 @@ int cornetto_bgin_prefetch(cornetto_accel_t *h, cornetto_bgin_t *b, const char *
 
 void cornetto_bgin_pending(const cornetto_bgin_t *b, int64_t *pend_tot, int64_t *pend_mq)
 {
-    if (pend_tot) *pend_tot = b ? (int64_t)b->pend[0].size() : 0;
-    if (pend_mq) *pend_mq = b ? (int64_t)b->pend[1].size() : 0;
+    if (pend_tot) *pend_tot = b ? b->n_pend(0) : 0;
+    if (pend_mq) *pend_mq = b ? b->n_pend(1) : 0;
 }
 
 int64_t cornetto_bgin_unmatched_mq(const cornetto_bgin_t *b) { return b && b->finished ? b->left_mq : 0; }
@@ -238,47 +243,78 @@ const cornetto_bgerr_t *cornetto_bgin_error(const cornetto_bgin_t *b) { return b
 
 int cornetto_bgin_done(const cornetto_bgin_t *b) { return b && b->finished; }
 
-int cornetto_bgin_feed(cornetto_accel_t *h, cornetto_bgin_t *b, const char *tot, int64_t n_tot, const char *mq, int64_t n_mq, int final)
+}  // extern "C"
+
+// The feed over two sources (cornetto_bgsrc_t), each plain host bytes or BGZF blocks on the device: what cornetto_bgin_feed() and
+// cornetto_bgin_feed_src() run.  A file that has had a compressed source keeps its carry on the device (BgCarry) from then on.
+static int bgin_feed_core(cornetto_accel_t *h, cornetto_bgin_t *b, const cornetto_bgsrc_t *const S[2], int final)
 {
-    if (!h || !b || n_tot < 0 || n_mq < 0 || (n_tot > 0 && !tot) || (n_mq > 0 && !mq)) return cn_fail(h, CORNETTO_E_ARG, "bgin_feed: bad argument");
     if (b->finished) return CORNETTO_OK;   // cov-total is exhausted: whatever follows in cov-mq is ignored, as in the reference
     if (b->err.kind) return CORNETTO_E_FORMAT;
+    int64_t nnew[2], n[2];
+    const char *src[2];
+    bool comp[2];
+    for (int f = 0; f < 2; ++f) {
+        if (!bgsrc_size(S[f], &nnew[f])) return cn_fail(h, CORNETTO_E_ARG, "bgin_feed: bad source for file %d", f);
+        comp[f] = bgsrc_compressed(S[f]);
+        src[f] = comp[f] || !S[f] ? nullptr : S[f]->text;
+        n[f] = b->n_pend(f) + nnew[f];
+        if (n[f] > 0xF0000000ll) return cn_fail(h, CORNETTO_E_ARG, "bgin_feed: more than 3.75 GiB pending for one file; feed smaller pieces");
+    }
     CN_HIP(h, hipSetDevice(h->device));
     cn_timing_begin(h);
-    const char *src[2] = {tot, mq};
-    const int64_t nnew[2] = {n_tot, n_mq};
-    int64_t n[2];
     uint8_t *d_text[2];
     for (int f = 0; f < 2; ++f) {
-        n[f] = (int64_t)b->pend[f].size() + nnew[f];
-        if (n[f] > 0xF0000000ll) return cn_fail(h, CORNETTO_E_ARG, "bgin_feed: more than 3.75 GiB pending for one file; feed smaller pieces");
+        if (comp[f] && !b->dc[f].on) {   // the file's first compressed source: what it carries moves to the device and stays there
+            CN_TRY(bg_carry_from_host(h, b->dc[f], b->pend[f]));
+            b->pend[f].clear();
+        }
         d_text[f] = (uint8_t *)cn_ws(h, f ? WS_BG_TEXT_B : WS_BG_TEXT_A, (size_t)n[f] + 64);
         if (!d_text[f]) return cn_fail(h, CORNETTO_E_NOMEM, "bgin_feed: workspace allocation failed");
-        if (!b->pend[f].empty()) CN_HIP(h, hipMemcpyAsync(d_text[f], b->pend[f].data(), b->pend[f].size(), hipMemcpyHostToDevice, h->stream));
+        if (b->dc[f].on) {
+            if (b->dc[f].n) CN_HIP(h, hipMemcpyAsync(d_text[f], b->dc[f].d, (size_t)b->dc[f].n, hipMemcpyDeviceToDevice, h->stream));
+        } else if (!b->pend[f].empty()) {
+            CN_HIP(h, hipMemcpyAsync(d_text[f], b->pend[f].data(), b->pend[f].size(), hipMemcpyHostToDevice, h->stream));
+        }
     }
+    const int64_t np0[2] = {b->n_pend(0), b->n_pend(1)};
     // the new bytes: staged on the device by cornetto_bgin_prefetch() (the same pointers and lengths) — a copy inside the device behind what is
     // left over from the last feed — or from the host now
     cornetto_bgin::Staged *st = nullptr;
-    for (auto &x : b->pf)
-        if (x.valid && x.src[0] == tot && x.src[1] == mq && x.n[0] == n_tot && x.n[1] == n_mq) st = &x;
+    if (!comp[0] && !comp[1])
+        for (auto &x : b->pf)
+            if (x.valid && x.src[0] == src[0] && x.src[1] == src[1] && x.n[0] == nnew[0] && x.n[1] == nnew[1]) st = &x;
     if (st) {
         CN_HIP(h, hipStreamWaitEvent(h->stream, st->ev, 0));
         st->valid = false;
     }
+    int64_t bad[2] = {-1, -1};   // per file: the first block of this feed that is not what its footer says
+    bool eof[2] = {(final & 1) != 0, (final & 2) != 0};
     for (int f = 0; f < 2; ++f) {
-        if (!nnew[f]) continue;
-        if (st) CN_HIP(h, hipMemcpyAsync(d_text[f] + b->pend[f].size(), st->buf[f], (size_t)nnew[f], hipMemcpyDeviceToDevice, h->stream));
-        else CN_HIP(h, hipMemcpyAsync(d_text[f] + b->pend[f].size(), src[f], (size_t)nnew[f], hipMemcpyHostToDevice, h->stream));
+        if (!nnew[f] && !comp[f]) continue;
+        if (comp[f]) {
+            // its blocks inflate behind the carry, in the text workspace itself; the text ends in front of a bad block, and the file is not
+            // at its end there: the last token in front of the block counts as cut
+            int64_t good = 0;
+            CN_TRY(bgsrc_inflate(h, S[f], d_text[f], np0[f], &bad[f], &good));
+            if (bad[f] >= 0) {
+                n[f] = np0[f] + good;
+                eof[f] = false;
+            }
+        } else if (st) CN_HIP(h, hipMemcpyAsync(d_text[f] + np0[f], st->buf[f], (size_t)nnew[f], hipMemcpyDeviceToDevice, h->stream));
+        else CN_HIP(h, hipMemcpyAsync(d_text[f] + np0[f], src[f], (size_t)nnew[f], hipMemcpyHostToDevice, h->stream));
     }
     // a token cut by the end of the buffer is not complete yet (unless this is the end of the file)
-    auto last_byte = [&](int f) -> int {
-        if (n[f] == 0) return ' ';
-        return nnew[f] ? (unsigned char)src[f][nnew[f] - 1] : (unsigned char)b->pend[f].back();
-    };
+    int last[2] = {' ', ' '};
+    for (int f = 0; f < 2; ++f) {
+        if (n[f] == 0) continue;
+        if (b->dc[f].on) CN_TRY(bg_byte_at(h, d_text[f], n[f] - 1, &last[f]));      // (the device text: inflated bytes have no copy on the host)
+        else last[f] = nnew[f] ? (unsigned char)src[f][nnew[f] - 1] : (unsigned char)b->pend[f].back();
+    }
+    auto last_byte = [&](int f) -> int { return last[f]; };
     CN_TRACE("bgin_feed: copies queued");
     uint32_t *d_tok[2];
     int64_t ntok[2], all_tok[2];
-    const bool eof[2] = {(final & 1) != 0, (final & 2) != 0};
     for (int f = 0; f < 2; ++f) {
         CN_TRY(tokenize(h, d_text[f], n[f], f ? WS_BG_TOK_B : WS_BG_TOK_A, f ? WS_BG_CNT_B : WS_BG_CNT_A, &d_tok[f], &ntok[f]));
         const int lb = last_byte(f);
@@ -295,6 +331,7 @@ int cornetto_bgin_feed(cornetto_accel_t *h, cornetto_bgin_t *b, const char *tot,
     if (!d_small || !p_small) return cn_fail(h, CORNETTO_E_NOMEM, "bgin_feed: workspace allocation failed");
     uint32_t break_cap = 1u << 16;
     std::vector<uint4> brk;
+    uint4 *d_brk = nullptr;
     if (fresh > 0) {
         if (b->n_rec + fresh > b->cap) {   // grow the flat depth arrays (amortised doubling)
             int64_t ncap = std::max<int64_t>(b->cap * 2, b->n_rec + fresh + (1 << 20));
@@ -315,7 +352,7 @@ int cornetto_bgin_feed(cornetto_accel_t *h, cornetto_bgin_t *b, const char *tot,
         for (int attempt = 0; attempt < 2; ++attempt) {
             // (the contig-start list, and behind it the list of negative values: 16 bytes each)
             constexpr uint32_t NEG_CAP = 1u << 16;
-            uint4 *d_brk = (uint4 *)cn_ws(h, WS_BG_BRK, ((size_t)break_cap + NEG_CAP) * sizeof(uint4));
+            d_brk = (uint4 *)cn_ws(h, WS_BG_BRK, ((size_t)break_cap + NEG_CAP) * sizeof(uint4));
             if (!d_brk) return cn_fail(h, CORNETTO_E_NOMEM, "bgin_feed: workspace allocation failed");
             unsigned long long *d_neg = reinterpret_cast<unsigned long long *>(d_brk + break_cap);
             CN_HIP(h, hipMemsetAsync(d_small, 0, 256, h->stream));
@@ -358,6 +395,13 @@ int cornetto_bgin_feed(cornetto_accel_t *h, cornetto_bgin_t *b, const char *tot,
         b->neg_corr[0] += p_small[14];
         b->neg_corr[1] += p_small[15];
     }
+    for (int f = 0; f < 2; ++f)
+        if (bad[f] >= 0) {   // every record in front of the block that has its partner has passed: the block itself is what is wrong
+            const int64_t at = S[f]->blocks[bad[f]].src;
+            b->err = cornetto_bgerr_t{BG_BLOCK, f, b->dc[f].blocks + bad[f], (int32_t)(uint32_t)(at & 0xFFFFFFFFll), (int32_t)(at >> 32)};
+            cn_timing_end(h);
+            return CORNETTO_E_FORMAT;
+        }
     CN_TRACE("bgin_feed: records");
     // offsets needed for the carry: start of the first unconsumed token, start of the context (last two consumed records)
     int64_t cut[2], ctx_start[2];
@@ -371,7 +415,7 @@ int cornetto_bgin_feed(cornetto_accel_t *h, cornetto_bgin_t *b, const char *tot,
         cut[f] = t_cut < all_tok[f] ? (int64_t)v[0] : n[f];
         ctx_start[f] = nrec > 0 ? (int64_t)v[1] : cut[f];
     }
-    // contig names: copy from the host bytes of file 0 before they go away
+    // contig names: copy from the host bytes of file 0 before they go away (a file with its carry on the device: gathered from the device text)
     auto byte_at = [&](int f, int64_t off, int64_t len) -> std::string {   // bytes [off, off+len) of (pend[f] | new data)
         std::string s;
         if (len <= 0) return s;
@@ -384,10 +428,13 @@ int cornetto_bgin_feed(cornetto_accel_t *h, cornetto_bgin_t *b, const char *tot,
         }
         return s;
     };
-    for (const uint4 &x : brk) {
+    std::vector<std::string> dev_names;
+    if (b->dc[0].on) CN_TRY(bg_fetch_names(h, d_text[0], d_brk, brk, 0, &dev_names));
+    for (size_t i = 0; i < brk.size(); ++i) {
+        const uint4 &x = brk[i];
         cornetto_bgin::Brk k;
         k.index = (int64_t)x.x | ((int64_t)x.y << 32);
-        k.name = byte_at(0, x.z, x.w);
+        k.name = b->dc[0].on ? dev_names[i] : byte_at(0, x.z, x.w);
         b->breaks.push_back(std::move(k));
     }
     {
@@ -396,14 +443,14 @@ int cornetto_bgin_feed(cornetto_accel_t *h, cornetto_bgin_t *b, const char *tot,
         const int64_t complete_a = ntok[0] / 4, left_a = ntok[0] - 4 * complete_a, left_b = ntok[1] - 4 * nrec;
         const int64_t at = b->n_rec + std::max<int64_t>(0, fresh);
         if (eof[1] && complete_a > nrec) {
-            b->err = cornetto_bgerr_t{(left_b >= 1 && left_b <= 3) ? BG_COLUMNS_B : BG_ORDER, at, (int32_t)left_b, 0};
+            b->err = cornetto_bgerr_t{(left_b >= 1 && left_b <= 3) ? BG_COLUMNS_B : BG_ORDER, 0, at, (int32_t)left_b, 0};
             cn_timing_end(h);
             return CORNETTO_E_FORMAT;
         }
         if (eof[0] && complete_a == nrec) {
             if (left_a >= 1) {
                 // a trailing partial record of cov-total: fscanf converts 1..3 fields, then cov-mq must still deliver
-                b->err = cornetto_bgerr_t{BG_COLUMNS_A, at, (int32_t)left_a, 0};
+                b->err = cornetto_bgerr_t{BG_COLUMNS_A, 0, at, (int32_t)left_a, 0};
                 cn_timing_end(h);
                 return CORNETTO_E_FORMAT;
             }
@@ -414,9 +461,15 @@ int cornetto_bgin_feed(cornetto_accel_t *h, cornetto_bgin_t *b, const char *tot,
     // carry: context records + everything not consumed
     for (int f = 0; f < 2; ++f) {
         const int64_t from = nrec > 0 ? ctx_start[f] : (b->ctx ? 0 : cut[f]);
+        if (b->dc[f].on) {
+            CN_TRY(bg_carry_store(h, b->dc[f], d_text[f] + from, n[f] - from));
+            if (comp[f]) b->dc[f].blocks += S[f]->n_blocks;
+            continue;
+        }
         std::string np = byte_at(f, from, n[f] - from);
         b->pend[f].swap(np);
     }
+    if (b->dc[0].on || b->dc[1].on) CN_HIP(h, hipStreamSynchronize(h->stream));   // (the carry has left the text workspace)
     if (fresh > 0) {
         b->n_rec += fresh;
         b->started = true;
@@ -425,6 +478,23 @@ int cornetto_bgin_feed(cornetto_accel_t *h, cornetto_bgin_t *b, const char *tot,
     CN_TRACE("bgin_feed: carry");
     cn_timing_end(h);
     return CORNETTO_OK;
+}
+
+extern "C" {
+
+int cornetto_bgin_feed(cornetto_accel_t *h, cornetto_bgin_t *b, const char *tot, int64_t n_tot, const char *mq, int64_t n_mq, int final)
+{
+    if (!h || !b || n_tot < 0 || n_mq < 0 || (n_tot > 0 && !tot) || (n_mq > 0 && !mq)) return cn_fail(h, CORNETTO_E_ARG, "bgin_feed: bad argument");
+    const cornetto_bgsrc_t st{tot, n_tot, nullptr, nullptr, 0}, sq{mq, n_mq, nullptr, nullptr, 0};
+    const cornetto_bgsrc_t *const S[2] = {&st, &sq};
+    return bgin_feed_core(h, b, S, final);
+}
+
+int cornetto_bgin_feed_src(cornetto_accel_t *h, cornetto_bgin_t *b, const cornetto_bgsrc_t *tot, const cornetto_bgsrc_t *mq, int final)
+{
+    if (!h || !b) return cn_fail(h, CORNETTO_E_ARG, "bgin_feed_src: bad argument");
+    const cornetto_bgsrc_t *const S[2] = {tot, mq};
+    return bgin_feed_core(h, b, S, final);
 }
 
 int cornetto_bgin_finish(cornetto_accel_t *h, cornetto_bgin_t *b, cornetto_cov_t **cov, int32_t *n_ctg, char ***names, int64_t *n_clamped)

@@ -249,6 +249,7 @@ struct cornetto_bgrun {
     struct Brk { int64_t pos; std::string name; };
     struct File {
         std::string pend;          // the context record (the last consumed one) + bytes not yet consumed
+        BgCarry dc;                // ... on the device instead, from the file's first compressed source on (cornetto_bgrun_feed_src)
         int32_t ctx = 0;           // context records at the head of pend: 0 or 1
         int64_t n_rec = 0, n_pos = 0;
         uint16_t *d = nullptr;     // the flat array
@@ -297,40 +298,76 @@ void cornetto_bgrun_close(cornetto_accel_t *h, cornetto_bgrun_t *b)
 {
     if (!b) return;
     if (h) (void)hipSetDevice(h->device);
-    for (auto &f : b->f)
+    for (auto &f : b->f) {
         if (f.d) (void)hipFree(f.d);
+        f.dc.release();
+    }
     delete b;
 }
 
 const cornetto_bgrunerr_t *cornetto_bgrun_error(const cornetto_bgrun_t *b) { return b ? &b->err : nullptr; }
 
-int cornetto_bgrun_feed(cornetto_accel_t *h, cornetto_bgrun_t *b, int file, const char *text, int64_t n_new, int final)
+}  // extern "C"
+
+// The feed over a source (cornetto_bgsrc_t), plain host bytes or BGZF blocks on the device: what cornetto_bgrun_feed() and
+// cornetto_bgrun_feed_src() run.  A file that has had a compressed source keeps its carry on the device (BgCarry) from then on.
+static int bgrun_feed_core(cornetto_accel_t *h, cornetto_bgrun_t *b, int file, const cornetto_bgsrc_t *S, int final)
 {
-    if (!h || !b || file < 0 || file > 1 || n_new < 0 || (n_new > 0 && !text)) return cn_fail(h, CORNETTO_E_ARG, "bgrun_feed: bad argument");
     if (b->err.kind) return CORNETTO_E_FORMAT;
     cornetto_bgrun::File &F = b->f[file];
-    if (F.eof) return n_new == 0 ? CORNETTO_OK : cn_fail(h, CORNETTO_E_ARG, "bgrun_feed: file %d has had its final feed", file);
+    int64_t n_new = 0;
+    if (!bgsrc_size(S, &n_new)) return cn_fail(h, CORNETTO_E_ARG, "bgrun_feed: bad source");
+    const bool comp = bgsrc_compressed(S);
+    const char *text = comp || !S ? nullptr : S->text;
+    if (F.eof) return n_new == 0 && !comp ? CORNETTO_OK : cn_fail(h, CORNETTO_E_ARG, "bgrun_feed: file %d has had its final feed", file);
+    // (the work space slots are the per-base reader's: the contents of a slot do not outlive a call)
+    const int64_t n_pend = F.dc.on ? F.dc.n : (int64_t)F.pend.size();
+    int64_t n = n_pend + n_new;
+    if (n > 0xF0000000ll) return cn_fail(h, CORNETTO_E_ARG, "bgrun_feed: more than 3.75 GiB pending; feed smaller pieces");
     CN_HIP(h, hipSetDevice(h->device));
     cn_timing_begin(h);
-    // (the work space slots are the per-base reader's: the contents of a slot do not outlive a call)
-    const int64_t n_pend = (int64_t)F.pend.size(), n = n_pend + n_new;
-    if (n > 0xF0000000ll) return cn_fail(h, CORNETTO_E_ARG, "bgrun_feed: more than 3.75 GiB pending; feed smaller pieces");
+    if (comp && !F.dc.on) {   // the file's first compressed source: what it carries moves to the device and stays there
+        CN_TRY(bg_carry_from_host(h, F.dc, F.pend));
+        F.pend.clear();
+    }
     uint8_t *d_text = (uint8_t *)cn_ws(h, WS_BG_TEXT_A, (size_t)n + 64);
     if (!d_text) return cn_fail(h, CORNETTO_E_NOMEM, "bgrun_feed: workspace allocation failed");
-    if (n_pend) CN_HIP(h, hipMemcpyAsync(d_text, F.pend.data(), (size_t)n_pend, hipMemcpyHostToDevice, h->stream));
-    if (n_new) CN_HIP(h, hipMemcpyAsync(d_text + n_pend, text, (size_t)n_new, hipMemcpyHostToDevice, h->stream));
+    if (F.dc.on) {
+        if (n_pend) CN_HIP(h, hipMemcpyAsync(d_text, F.dc.d, (size_t)n_pend, hipMemcpyDeviceToDevice, h->stream));
+    } else if (n_pend) CN_HIP(h, hipMemcpyAsync(d_text, F.pend.data(), (size_t)n_pend, hipMemcpyHostToDevice, h->stream));
+    int64_t bad = -1;   // the first block of this feed that is not what its footer says
+    if (comp) {
+        // its blocks inflate behind the carry, in the text workspace itself; the text ends in front of a bad block, and the file is not at its
+        // end there: the last token in front of the block counts as cut
+        int64_t good = 0;
+        CN_TRY(bgsrc_inflate(h, S, d_text, n_pend, &bad, &good));
+        if (bad >= 0) {
+            n = n_pend + good;
+            final = 0;
+        }
+    } else if (n_new) CN_HIP(h, hipMemcpyAsync(d_text + n_pend, text, (size_t)n_new, hipMemcpyHostToDevice, h->stream));
     uint32_t *d_tok = nullptr;
     int64_t all_tok = 0;
     CN_TRY(tokenize(h, d_text, n, WS_BG_TOK_A, WS_BG_CNT_A, &d_tok, &all_tok));
     int64_t ntok = all_tok;
     {   // a token cut by the end of the buffer is not complete yet (unless this is the end of the file)
-        const int lb = n == 0 ? ' ' : (n_new ? (unsigned char)text[n_new - 1] : (unsigned char)F.pend.back());
+        int lb = ' ';
+        if (n > 0) {
+            if (F.dc.on) CN_TRY(bg_byte_at(h, d_text, n - 1, &lb));      // (the device text: inflated bytes have no copy on the host)
+            else lb = n_new ? (unsigned char)text[n_new - 1] : (unsigned char)F.pend.back();
+        }
         if (!final && !host_ws((unsigned char)lb) && ntok > 0) --ntok;
     }
     const int64_t nrec = ntok / 4, fresh = nrec - F.ctx;
     auto byte_at = [&](int64_t off, int64_t len) -> std::string {   // bytes [off, off + len) of (pend | new data)
         std::string s;
         if (len <= 0) return s;
+        if (F.dc.on) {   // from the device text (a few bytes behind the last record of a file; the names of a feed come packed: bg_fetch_names)
+            s.resize((size_t)len);
+            if (hipMemcpyAsync(&s[0], d_text + off, (size_t)len, hipMemcpyDeviceToHost, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess)
+                s.assign((size_t)len, ' ');
+            return s;
+        }
         s.reserve((size_t)len);
         if (off < n_pend) s.append(F.pend, (size_t)off, (size_t)std::min<int64_t>(len, n_pend - off));
         if (off + len > n_pend) {
@@ -417,12 +454,19 @@ int cornetto_bgrun_feed(cornetto_accel_t *h, cornetto_bgrun_t *b, int file, cons
         }
         CN_HIP(h, hipStreamSynchronize(h->stream));
         const size_t at = F.breaks.size();
-        for (uint32_t k = 0; k < nb; ++k) F.breaks.push_back(cornetto_bgrun::Brk{F.n_pos + (int64_t)bpos[k], byte_at(brk[k].y, brk[k].z)});
+        std::vector<std::string> dev_names;
+        if (F.dc.on) CN_TRY(bg_fetch_names(h, d_text, d_brk, brk, 1, &dev_names));
+        for (uint32_t k = 0; k < nb; ++k) F.breaks.push_back(cornetto_bgrun::Brk{F.n_pos + (int64_t)bpos[k], F.dc.on ? dev_names[k] : byte_at(brk[k].y, brk[k].z)});
         std::sort(F.breaks.begin() + (std::ptrdiff_t)at, F.breaks.end(), [](const cornetto_bgrun::Brk &x, const cornetto_bgrun::Brk &y) { return x.pos < y.pos; });
         b->n_clamp += clamped;
         F.n_pos += total;
         F.n_rec += fresh;
     }
+    if (bad >= 0) {   // every record in front of the block has passed its checks: the block itself is what is wrong
+        const int64_t at = S->blocks[bad].src;
+        return rl_format_error(h, b, BG_BLOCK, file, F.dc.blocks + bad, (int32_t)(uint32_t)(at & 0xFFFFFFFFll), (int32_t)(at >> 32));
+    }
+    if (comp) F.dc.blocks += S->n_blocks;
     // the tokens behind the last whole record, and where the carry starts
     const int64_t t_cut = 4 * nrec, n_left = all_tok - t_cut;
     uint32_t v[4] = {0, 0, 0, 0};   // [0..2]: the first tokens that are left, [3]: the last consumed record
@@ -430,26 +474,47 @@ int cornetto_bgrun_feed(cornetto_accel_t *h, cornetto_bgrun_t *b, int file, cons
     if (nrec > 0) CN_HIP(h, hipMemcpy(&v[3], d_tok + 4 * (nrec - 1), 4, hipMemcpyDeviceToHost));
     if (final) {
         if (n_left >= 1) {   // 1..3 tokens: a record with fewer than four converted fields
-            const std::string rest = byte_at(0, n);
+            const std::string rest = byte_at(v[0], n - v[0]);   // (v[0]: the first of those tokens)
             int conv = 1;
-            if (n_left >= 2 && host_token_is_int(rest, v[1])) {
+            if (n_left >= 2 && host_token_is_int(rest, v[1] - v[0])) {
                 conv = 2;
-                if (n_left >= 3 && host_token_is_int(rest, v[2])) conv = 3;
+                if (n_left >= 3 && host_token_is_int(rest, v[2] - v[0])) conv = 3;
             }
             return rl_format_error(h, b, RL_COLUMNS + file, file, F.n_rec, conv, 0);
         }
         F.eof = true;
         F.pend.clear();
+        F.dc.n = 0;
         F.ctx = 0;
     } else {
         const int64_t cut = n_left > 0 ? (int64_t)v[0] : n;
         const int64_t from = nrec > 0 ? (int64_t)v[3] : cut;
-        std::string np = byte_at(from, n - from);
-        F.pend.swap(np);
+        if (F.dc.on) {
+            CN_TRY(bg_carry_store(h, F.dc, d_text + from, n - from));
+            CN_HIP(h, hipStreamSynchronize(h->stream));   // (the carry has left the text workspace)
+        } else {
+            std::string np = byte_at(from, n - from);
+            F.pend.swap(np);
+        }
         F.ctx = nrec > 0 ? 1 : 0;
     }
     cn_timing_end(h);
     return CORNETTO_OK;
+}
+
+extern "C" {
+
+int cornetto_bgrun_feed(cornetto_accel_t *h, cornetto_bgrun_t *b, int file, const char *text, int64_t n_new, int final)
+{
+    if (!h || !b || file < 0 || file > 1 || n_new < 0 || (n_new > 0 && !text)) return cn_fail(h, CORNETTO_E_ARG, "bgrun_feed: bad argument");
+    const cornetto_bgsrc_t s{text, n_new, nullptr, nullptr, 0};
+    return bgrun_feed_core(h, b, file, &s, final);
+}
+
+int cornetto_bgrun_feed_src(cornetto_accel_t *h, cornetto_bgrun_t *b, int file, const cornetto_bgsrc_t *src, int final)
+{
+    if (!h || !b || file < 0 || file > 1) return cn_fail(h, CORNETTO_E_ARG, "bgrun_feed_src: bad argument");
+    return bgrun_feed_core(h, b, file, src, final);
 }
 
 int cornetto_bgrun_finish(cornetto_accel_t *h, cornetto_bgrun_t *b, cornetto_cov_t **cov, int32_t *n_ctg, char ***names, int64_t *n_clamped)

@@ -5,7 +5,10 @@
 #include <algorithm>
 #include <string>
 
+#include <vector>
+
 #include "common.hpp"
+#include "internal.hpp"
 #include "marks.hpp"
 
 namespace {   // internal linkage: every translation unit that includes this gets its own copy
@@ -115,6 +118,132 @@ int tokenize(cornetto_accel_t *h, const uint8_t *d_text, int64_t n, int slot_tok
     CN_TRY(cnmarks::count<tokstart_mask>(h, "bedgraph ingest", "tk_count", "tk_scan", d_text, n, slot_cnt, 0, &mk));
     CN_TRY(cnmarks::scatter<tokstart_mask>(h, "bedgraph ingest", "tk_scatter", d_text, n, mk, slot_tok, (size_t)mk.total, tok_out));
     *ntok = mk.total;
+    return CORNETTO_OK;
+}
+
+// ---- compressed sources (cornetto_bgsrc_t): what both readers need to take BGZF blocks and to keep their carry on the device ----------------
+enum { BG_BLOCK = 11 };   // the kind of a damaged block in cornetto_bgerr_t / cornetto_bgrunerr_t
+
+// the bytes a source adds to its file (inflated bytes for a compressed one); false: not a source the feeds take
+inline bool bgsrc_size(const cornetto_bgsrc_t *s, int64_t *n_new)
+{
+    *n_new = 0;
+    if (!s) return true;
+    if (s->n < 0 || s->n_blocks < 0 || s->n_blocks > 0x7fffffffLL || (s->n > 0 && (!s->text || s->n_blocks > 0)) || (s->n_blocks > 0 && (!s->comp || !s->blocks)))
+        return false;
+    for (int64_t i = 0; i < s->n_blocks; ++i) {
+        const cornetto_bgzf_block_t &k = s->blocks[i];
+        if (k.src < 0 || k.n_src < 0 || k.src > s->comp->cap - k.n_src || k.n_dst < 0 || k.n_dst > 65536) return false;
+        *n_new += k.n_dst;
+    }
+    if (s->n > 0) *n_new = s->n;
+    return true;
+}
+inline bool bgsrc_compressed(const cornetto_bgsrc_t *s) { return s && s->n_blocks > 0; }
+
+// what a file carries from one feed to the next, on the device (a buffer of its own: cn_ws() does not keep what a slot held when it grows)
+struct BgCarry {
+    uint8_t *d = nullptr;
+    size_t cap = 0;
+    int64_t n = 0;
+    bool on = false;     // the file has had a compressed source: its carry lives here, not in the host string
+    int64_t blocks = 0;  // BGZF blocks of the file handed over so far
+    void release() { if (d) (void)hipFree(d); d = nullptr; cap = 0; n = 0; }
+};
+
+inline int bg_carry_reserve(cornetto_accel_t *h, BgCarry &c, int64_t len)
+{
+    if ((size_t)len <= c.cap) return CORNETTO_OK;
+    c.release();
+    const size_t cap = (size_t)len + (size_t)len / 4 + 4096;
+    if (hipMalloc((void **)&c.d, cap) != hipSuccess) { c.d = nullptr; return cn_fail(h, CORNETTO_E_NOMEM, "bedgraph ingest: device allocation of %zu bytes failed", cap); }
+    c.cap = cap;
+    return CORNETTO_OK;
+}
+
+// carry <- bytes [from, from + len) of the text workspace (another allocation: the ranges never overlap); queued on the handle's stream
+inline int bg_carry_store(cornetto_accel_t *h, BgCarry &c, const uint8_t *d_from, int64_t len)
+{
+    CN_TRY(bg_carry_reserve(h, c, len));
+    if (len > 0) CN_HIP(h, hipMemcpyAsync(c.d, d_from, (size_t)len, hipMemcpyDeviceToDevice, h->stream));
+    c.n = len;
+    return CORNETTO_OK;
+}
+
+// the file's first compressed source: what the host string carried goes to the device (the caller clears the string)
+inline int bg_carry_from_host(cornetto_accel_t *h, BgCarry &c, const std::string &pend)
+{
+    CN_TRY(bg_carry_reserve(h, c, (int64_t)pend.size()));
+    if (!pend.empty()) {
+        CN_HIP(h, hipMemcpyAsync(c.d, pend.data(), pend.size(), hipMemcpyHostToDevice, h->stream));
+        CN_HIP(h, hipStreamSynchronize(h->stream));
+    }
+    c.n = (int64_t)pend.size();
+    c.on = true;
+    return CORNETTO_OK;
+}
+
+// Inflate the blocks of a compressed source behind the n_pend carried bytes of d_text (which has room for n_pend + the sum of n_dst).  *n_good: the
+// inflated bytes in front of the first bad block (all of them when *first_bad is -1).
+inline int bgsrc_inflate(cornetto_accel_t *h, const cornetto_bgsrc_t *s, uint8_t *d_text, int64_t n_pend, int64_t *first_bad, int64_t *n_good)
+{
+    for (int i = 0; i < 4; ++i) CN_HIP(h, hipStreamSynchronize(s->comp->q[i]));     // every slab is on the device
+    std::vector<cornetto_bgzf_block_t> blk(s->blocks, s->blocks + s->n_blocks);
+    int64_t at = n_pend;
+    for (auto &k : blk) {
+        k.dst = at;
+        at += k.n_dst;
+    }
+    CN_TRY(cn_bgzf_inflate_raw(h, s->comp->d, d_text, blk.data(), s->n_blocks, first_bad));
+    *n_good = (*first_bad >= 0 ? blk[(size_t)*first_bad].dst : at) - n_pend;
+    return CORNETTO_OK;
+}
+
+// one byte of a device text, behind everything queued on the handle's stream
+inline int bg_byte_at(cornetto_accel_t *h, const uint8_t *d_text, int64_t at, int *out)
+{
+    uint8_t *p = (uint8_t *)cn_pin(h, PIN_SMALL, 256);
+    if (!p) return cn_fail(h, CORNETTO_E_NOMEM, "bedgraph ingest: workspace allocation failed");
+    CN_HIP(h, hipMemcpyAsync(p + 248, d_text + at, 1, hipMemcpyDeviceToHost, h->stream));
+    CN_HIP(h, hipStreamSynchronize(h->stream));
+    *out = p[248];
+    return CORNETTO_OK;
+}
+
+// The contig names of a feed's contig starts, packed on the device and copied once: a block of 64 lanes per name.  brk[k] holds the name's
+// offset and length in the text (.z / .w in the per-base reader's list, .y / .z in the run reader's); both lie inside the text (name_of()).
+__global__ __launch_bounds__(64) void bg_names(const uint8_t *__restrict__ text, const uint4 *__restrict__ brk, uint32_t n, int runs, const uint32_t *__restrict__ to,
+                                                uint8_t *__restrict__ pack)
+{
+    const uint32_t k = blockIdx.x;
+    if (k >= n) return;
+    const uint4 x = brk[k];
+    const uint32_t off = runs ? x.y : x.z, len = runs ? x.z : x.w;
+    for (uint32_t i = threadIdx.x; i < len; i += 64) pack[to[k] + i] = text[off + i];
+}
+
+int bg_fetch_names(cornetto_accel_t *h, const uint8_t *d_text, const uint4 *d_brk, const std::vector<uint4> &brk, int runs, std::vector<std::string> *names)
+{
+    names->assign(brk.size(), std::string());
+    const uint32_t nb = (uint32_t)brk.size();
+    if (!nb) return CORNETTO_OK;
+    std::vector<uint32_t> to(nb);
+    size_t total = 0;
+    for (uint32_t k = 0; k < nb; ++k) {
+        to[k] = (uint32_t)total;
+        total += runs ? brk[k].z : brk[k].w;
+    }
+    if (total == 0) return CORNETTO_OK;
+    if (total > 0xF0000000ull) return cn_fail(h, CORNETTO_E_UNSUPPORTED, "bedgraph ingest: the contig names of one feed have more than 3.75 GiB");
+    const size_t head = ((size_t)nb * 4 + 15) & ~(size_t)15;
+    uint8_t *d_pack = (uint8_t *)cn_ws(h, WS_BZ_PACK, head + total);
+    if (!d_pack) return cn_fail(h, CORNETTO_E_NOMEM, "bedgraph ingest: workspace allocation failed");
+    std::string pack(total, '\0');
+    CN_HIP(h, hipMemcpyAsync(d_pack, to.data(), (size_t)nb * 4, hipMemcpyHostToDevice, h->stream));
+    CN_LAUNCH(h, "bg_names", bg_names<<<dim3(nb), dim3(64), 0, h->stream>>>(d_text, d_brk, nb, runs, reinterpret_cast<const uint32_t *>(d_pack), d_pack + head));
+    CN_HIP(h, hipMemcpyAsync(&pack[0], d_pack + head, total, hipMemcpyDeviceToHost, h->stream));
+    CN_HIP(h, hipStreamSynchronize(h->stream));
+    for (uint32_t k = 0; k < nb; ++k) (*names)[k].assign(pack, to[k], runs ? brk[k].z : brk[k].w);
     return CORNETTO_OK;
 }
 

@@ -10,6 +10,7 @@
 //   text_gather    ranges of a device text packed back to back (the record names of an inflated FASTA text).
 #include "common.hpp"
 #include "inflate.hpp"
+#include "internal.hpp"
 
 namespace {
 
@@ -77,6 +78,28 @@ __global__ void __launch_bounds__(256) text_gather(const uint8_t *__restrict__ t
 
 }   // namespace
 
+// The two kernels over raw device pointers (internal.hpp): what cornetto_text_inflate() runs between its checks and its timing bracket, and what
+// the bedgraph feeds run into their own text workspaces.  The caller has checked that every block lies inside both buffers and that the
+// compressed bytes are on the device.  Synchronises the handle's stream.  *first_bad: -1, or the lowest index of a bad block.
+int cn_bgzf_inflate_raw(cornetto_accel_t *h, const uint8_t *d_comp, uint8_t *d_out, const cornetto_bgzf_block_t *blocks, int64_t n_blocks, int64_t *first_bad)
+{
+    *first_bad = -1;
+    if (n_blocks <= 0) return CORNETTO_OK;
+    cornetto_bgzf_block_t *d_blk = (cornetto_bgzf_block_t *)cn_ws(h, WS_BZ_BLOCKS, (size_t)n_blocks * sizeof(cornetto_bgzf_block_t));
+    int32_t *d_st = (int32_t *)cn_ws(h, WS_BZ_STATUS, ((size_t)n_blocks + 4) * 4);
+    unsigned int *p_bad = (unsigned int *)cn_pin(h, PIN_SMALL, 64);
+    if (!d_blk || !d_st || !p_bad) return cn_fail(h, CORNETTO_E_NOMEM, "text_inflate: workspace allocation failed");
+    unsigned int *d_bad = (unsigned int *)(d_st + n_blocks);
+    CN_HIP(h, hipMemcpyAsync(d_blk, blocks, (size_t)n_blocks * sizeof(cornetto_bgzf_block_t), hipMemcpyHostToDevice, h->stream));
+    CN_HIP(h, hipMemsetAsync(d_bad, 0xFF, 4, h->stream));
+    CN_LAUNCH(h, "bgzf_inflate", bgzf_inflate<<<dim3((unsigned)n_blocks), dim3(64), 0, h->stream>>>(d_comp, d_out, d_blk, n_blocks, d_st));
+    CN_LAUNCH(h, "bgzf_crc32", bgzf_crc32<<<dim3((unsigned)n_blocks), dim3(64), 0, h->stream>>>(d_out, d_blk, n_blocks, d_st, d_bad));
+    CN_HIP(h, hipMemcpyAsync(p_bad, d_bad, 4, hipMemcpyDeviceToHost, h->stream));
+    CN_HIP(h, hipStreamSynchronize(h->stream));
+    if (p_bad[0] != 0xFFFFFFFFu) *first_bad = (int64_t)p_bad[0];
+    return CORNETTO_OK;
+}
+
 extern "C" int cornetto_bgzf_scan(const uint8_t *buf, int64_t n, int64_t file_off, int64_t *dst, cornetto_bgzf_block_t *blocks, int64_t cap, int64_t *n_blocks,
                                   int64_t *resume, int32_t *broken)
 {
@@ -99,22 +122,9 @@ extern "C" int cornetto_text_inflate(cornetto_accel_t *h, cornetto_text_t *comp,
     CN_HIP(h, hipSetDevice(h->device));
     for (int i = 0; i < 4; ++i) CN_HIP(h, hipStreamSynchronize(comp->q[i]));     // every slab is on the device
     cn_timing_begin(h);
-    cornetto_bgzf_block_t *d_blk = (cornetto_bgzf_block_t *)cn_ws(h, WS_BZ_BLOCKS, (size_t)n_blocks * sizeof(cornetto_bgzf_block_t));
-    int32_t *d_st = (int32_t *)cn_ws(h, WS_BZ_STATUS, ((size_t)n_blocks + 4) * 4);
-    unsigned int *p_bad = (unsigned int *)cn_pin(h, PIN_SMALL, 64);
-    if (!d_blk || !d_st || !p_bad) return cn_fail(h, CORNETTO_E_NOMEM, "text_inflate: workspace allocation failed");
-    unsigned int *d_bad = (unsigned int *)(d_st + n_blocks);
-    CN_HIP(h, hipMemcpyAsync(d_blk, blocks, (size_t)n_blocks * sizeof(cornetto_bgzf_block_t), hipMemcpyHostToDevice, h->stream));
-    CN_HIP(h, hipMemsetAsync(d_bad, 0xFF, 4, h->stream));
-    CN_LAUNCH(h, "bgzf_inflate", bgzf_inflate<<<dim3((unsigned)n_blocks), dim3(64), 0, h->stream>>>(comp->d, out->d, d_blk, n_blocks, d_st));
-    CN_LAUNCH(h, "bgzf_crc32", bgzf_crc32<<<dim3((unsigned)n_blocks), dim3(64), 0, h->stream>>>(out->d, d_blk, n_blocks, d_st, d_bad));
-    CN_HIP(h, hipMemcpyAsync(p_bad, d_bad, 4, hipMemcpyDeviceToHost, h->stream));
-    CN_HIP(h, hipStreamSynchronize(h->stream));
+    CN_TRY(cn_bgzf_inflate_raw(h, comp->d, out->d, blocks, n_blocks, first_bad));
     cn_timing_end(h);
-    if (p_bad[0] != 0xFFFFFFFFu) {
-        *first_bad = (int64_t)p_bad[0];
-        return cn_fail(h, CORNETTO_E_FORMAT, "text_inflate: block %lld is not what its footer says", (long long)*first_bad);
-    }
+    if (*first_bad >= 0) return cn_fail(h, CORNETTO_E_FORMAT, "text_inflate: block %lld is not what its footer says", (long long)*first_bad);
     return CORNETTO_OK;
 }
 

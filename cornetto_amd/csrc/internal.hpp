@@ -59,5 +59,9 @@ int cn_telo_marks_impl(cornetto_accel_t *h, const cornetto_asm_t *a, const char 
 // A cornetto_sdust_asm_begin() nobody finished is finished and dropped first; that runs a timing bracket of its own, so a caller with a
 // bracket calls cn_sdust_drop_pending() BEFORE it opens it (cn_sdust_list_impl() drops too: a no-op then).
 void cn_sdust_drop_pending(cornetto_accel_t *h);
+
+// cornetto_text_inflate() over raw device pointers, without its checks and its timing bracket (inflate.hip): the bedgraph feeds inflate into
+// their own text workspaces with it.  Every block must lie inside both buffers.  Synchronises the handle's stream.
+int cn_bgzf_inflate_raw(cornetto_accel_t *h, const uint8_t *d_comp, uint8_t *d_out, const cornetto_bgzf_block_t *blocks, int64_t n_blocks, int64_t *first_bad);
 int cn_sdust_list_impl(cornetto_accel_t *h, const cornetto_asm_t *a, int32_t T, int32_t W, const cornetto_ivl_t **d_ivls, int64_t *n_ivls);
 int cn_telo_hits_impl(cornetto_accel_t *h, const cornetto_asm_t *a, const char *motif, const cornetto_hit_t **d_hits, int64_t *n_hits);

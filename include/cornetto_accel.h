@@ -372,7 +372,11 @@ typedef struct {
                        2: cov-mq record has != 4 columns (a = converted fields)      :219-222
                        3: "The two files are not in the same order"                  :214-217,:224-227
                        4: not incremental at one base resolution (a = prev_pos, b = start)  :249-252
-                       5: end != start + 1 (a = start, b = end)                      :256-259 */
+                       5: end != start + 1 (a = start, b = end)                      :256-259
+                       11: a BGZF block of a compressed source (cornetto_bgin_feed_src) is not what its footer says: record = the block's index in
+                           its file counted over all feeds, a / b = the low / high 32 bits of blocks[].src as it was handed over, file = the file.
+                           Every record that lies wholly in front of the block and has its partner has passed its checks */
+    int32_t file;   /* kind 11: 0 cov-total, 1 cov-mq; else 0 (it takes the place of what was padding: no member moved) */
     int64_t record; /* 0-based index of the record */
     int32_t a, b;
 } cornetto_bgerr_t;
@@ -431,7 +435,9 @@ typedef struct {
                        8: end <= start (a = start, b = end)
                        9: negative value (a = value)
                        10: at finish, the files disagree: contig `record` is missing in one of them (its length there: 0) or differs in
-                           name or length (a, b = its length in cov-total, cov-mq) */
+                           name or length (a, b = its length in cov-total, cov-mq)
+                       11: a BGZF block of a compressed source (cornetto_bgrun_feed_src) is not what its footer says: record = the block's index
+                           in its file counted over all feeds, a / b = the low / high 32 bits of blocks[].src as it was handed over */
     int32_t file;   /* 0: cov-total, 1: cov-mq */
     int64_t record; /* 0-based index of the record in its file (kind 10: of the contig) */
     int32_t a, b;
@@ -552,6 +558,26 @@ int cornetto_text_inflate(cornetto_accel_t *h, cornetto_text_t *comp, cornetto_t
 /* The bytes [at[i], at[i] + len[i]) of a device text, i = 0 .. n - 1, packed back to back on the device (one kernel) and copied to dst
  * (one copy; host memory of sum(len) bytes): how the record names of an inflated text reach the host. */
 int cornetto_text_gather(cornetto_accel_t *h, cornetto_text_t *t, const int64_t *at, const int32_t *len, int64_t n, char *dst);
+
+/* Bedgraph text from a bgzip-compressed depth file (mosdepth writes *.per-base.bed.gz only): the next bytes of one file for the two bedgraph
+ * readers, either plain bytes in host memory or the next BGZF blocks of the file, whose deflate streams are on the device.  The feed gives a
+ * compressed source's blocks their places behind the bytes it carries over from the last feed IN THE READER'S OWN TEXT WORKSPACE, inflates
+ * them there (bgzf_inflate, bgzf_crc32) and tokenises in place: inflated text never crosses PCIe, and from the first compressed source of a
+ * file on, what is carried over between its feeds stays on the device.  n == 0 && n_blocks == 0 (or a NULL source): nothing new for the
+ * file.  A source with both is CORNETTO_E_ARG, and so is a block that lies outside `comp` or says more than 65536 bytes. */
+typedef struct cornetto_bgsrc {
+    const char *text; int64_t n;                 /* plain bytes in host memory (ordinary or pinned), or */
+    cornetto_text_t *comp;                       /* a device text holding deflate streams, put there with cornetto_text_put() */
+    const cornetto_bgzf_block_t *blocks;         /* the next blocks of the file in file order: src = offsets into comp, dst ignored */
+    int64_t n_blocks;
+} cornetto_bgsrc_t;
+/* cornetto_bgin_feed() / cornetto_bgrun_feed() over such sources: the same records, checks, results and errors; the two files of a pair may be
+ * of different kinds, and a file may change kind between feeds.  The limit of 0xF0000000 bytes per file and feed counts carried plus inflated
+ * bytes (the sum of n_dst): CORNETTO_E_ARG beyond, before anything runs.  Synchronous: `comp` may be overwritten on return.
+ * A damaged block is kind 11 of cornetto_bgerr_t / cornetto_bgrunerr_t: what is reported is that block or a failed check of a record that lies
+ * wholly in front of it, never anything made from its bytes or from bytes behind it, and no depth value from such bytes is stored. */
+int cornetto_bgin_feed_src(cornetto_accel_t *h, cornetto_bgin_t *b, const cornetto_bgsrc_t *tot, const cornetto_bgsrc_t *mq, int final);
+int cornetto_bgrun_feed_src(cornetto_accel_t *h, cornetto_bgrun_t *b, int file, const cornetto_bgsrc_t *src, int final);
 
 /* ---------------------------------------------------------------------------------------------------
  * BAM: both per-base coverage tracks from a coordinate-sorted or unsorted BAM on the device: `(no)boringbits --bam`.  An EXTENSION (the
