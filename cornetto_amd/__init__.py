@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-__all__ = ["lib", "Accel", "bgzf_scan", "bam_header", "BGZF_DT", "BAMREC_DT", "BAM_SCAN_TILE", "BamFormatError", "AccelError", "HIT_DT", "WIN_DT", "IVL_DT", "TELROW_DT", "HAP_ROW_DT", "khash_str_order", "panel_boring", "REG_DT", "REGREC_DT", "build",
+__all__ = ["lib", "Accel", "bgzf_scan", "bam_header", "BGZF_DT", "BAMREC_DT", "BAMFQREC_DT", "BAM_SCAN_TILE", "BamFormatError", "AccelError", "HIT_DT", "WIN_DT", "IVL_DT", "TELROW_DT", "HAP_ROW_DT", "khash_str_order", "panel_boring", "REG_DT", "REGREC_DT", "build",
            "LIB_PATH", "CLI_PATH"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -78,6 +78,12 @@ class BamDepthOpt(C.Structure):
     _fields_ = [("min_mapq", C.c_int32), ("skip_flags", C.c_uint32), ("window", C.c_int64), ("records", C.c_int32), ("pad", C.c_int32)]
 
 
+class BamFqOpt(C.Structure):
+    """cornetto_bamfq_opt_t (include/cornetto_accel.h)"""
+    _fields_ = [("min_len", C.c_int32), ("duplex", C.c_int32), ("window", C.c_int64), ("n_ref", C.c_int32), ("records", C.c_int32)]
+
+
+BAMFQREC_DT = np.dtype([("offset", "<i8"), ("l_seq", "<i4"), ("flag", "<i4"), ("name_len", "<i4"), ("kept", "<i4")])
 BAMREC_DT = np.dtype([("offset", "<i8"), ("ref_id", "<i4"), ("pos", "<i4"), ("mapq", "<i4"), ("flag", "<i4"), ("counted", "<i4"), ("n_ops", "<i4"), ("span", "<i8"),
                       ("bases", "<i8")])
 BAM_SCAN_TILE = 4096  # CORNETTO_BAM_SCAN_TILE: positions per workgroup of the depth scan (checked against the library when it is loaded)
@@ -243,6 +249,16 @@ def lib(dev=False):
         "cornetto_bamdepth_error": (C.POINTER(BamErr), [vp]),
         "cornetto_bamdepth_finish": (C.c_int, [vp, vp, pp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]),
         "cornetto_bam_records": (C.c_int, [vp, vp, pp, C.POINTER(i64)]),
+        "cornetto_bamfq_defaults": (None, [C.POINTER(BamFqOpt)]),
+        "cornetto_bamfq_open": (C.c_int, [vp, C.POINTER(BamFqOpt), pp]),
+        "cornetto_bamfq_close": (None, [vp, vp]),
+        "cornetto_bamfq_feed": (C.c_int, [vp, vp, vp, vp, i64, i64, C.POINTER(i64), C.POINTER(i64)]),
+        "cornetto_bamfq_get": (C.c_int, [vp, vp, vp, i64, i64, C.c_int]),
+        "cornetto_bamfq_wait": (C.c_int, [vp, vp, C.c_int]),
+        "cornetto_bamfq_finish": (C.c_int, [vp, vp]),
+        "cornetto_bamfq_stats": (None, [vp, C.POINTER(i64)]),
+        "cornetto_bamfq_error": (C.POINTER(BamErr), [vp]),
+        "cornetto_bamfq_records": (C.c_int, [vp, vp, pp, C.POINTER(i64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError if the library does not export a declared symbol
@@ -925,6 +941,117 @@ class Accel:
     def bam_records(self, blob, window=None):
         """the records of the BAM file `blob` as the depth kernel reads them (BAMREC_DT); no depth array is allocated"""
         return self._bam_run(blob, window, 20, 2)[2]
+
+    def _bam_head(self, blob):
+        """the BGZF blocks of the BAM file `blob` and its header (zlib + cornetto_bam_header) -> (blocks, names, lens, header bytes)"""
+        import zlib
+        blocks, resume, broken = bgzf_scan(blob)
+        if broken or resume != len(blob):
+            raise BamFormatError(7 if not len(blocks) else 6, 0, 0, 0)
+        head, hdr = b"", None
+        for b in blocks:
+            try:
+                head += zlib.decompress(bytes(blob[int(b["src"]):int(b["src"]) + int(b["n_src"])]), -15)
+            except zlib.error:
+                raise BamFormatError(6, 0, 0, 0)
+            try:
+                hdr = bam_header(head)
+            except ValueError:
+                raise BamFormatError(7, -1, 0, 0)
+            if hdr is not None:
+                break
+        if hdr is None:
+            raise BamFormatError(2, -1, 0, -1)
+        return (blocks,) + tuple(hdr)
+
+    def bam_fastq(self, blob, min_len=0, duplex=False, window=None, slab=None, feeds=1):
+        """the BAM file `blob` (bytes) through the feed / get loop of cornetto_bamfq_*: the FASTQ text `seq --bam` prints -> (text, stats,
+        records): stats = [reads, bases of `total reads`, reads, bases of `reads >= min_len`], records = the record table (BAMFQREC_DT).
+        window: bytes of inflated BAM on the device at once; slab: bytes per get (the whole text of a window by default), the gets take
+        turns on the four copy slots; feeds: the blocks are handed over in that many parts.  Neither changes a result.  Raises
+        BamFormatError, which carries text, stats and records of the records in front of the failing one; a record larger than the window
+        raises AccelError (status -4).  The kernel times of the feeds are kept in self.bam_timing."""
+        L = self.L
+        blocks, _names, lens, skip = self._bam_head(blob)
+        comp = self._text_from(blob)
+        fq = None
+        pins, cap = [None] * 4, [0] * 4
+        out = []
+        self.bam_timing = []
+
+        def result():
+            st = (C.c_int64 * 5)()
+            L.cornetto_bamfq_stats(fq, st)
+            p, n = C.c_void_p(), C.c_int64()
+            self._chk(L.cornetto_bamfq_records(self.h, fq, C.byref(p), C.byref(n)))
+            return b"".join(out), list(st)[:4], _take(L, p, n.value, BAMFQREC_DT)
+
+        def fail():
+            e = L.cornetto_bamfq_error(fq).contents
+            err = BamFormatError(e.kind, e.record, e.a, e.b)
+            err.text, err.stats, err.records = result()
+            return err
+
+        def pull(n_text):
+            pend, at, k = [0] * 4, 0, 0
+            while at < n_text or any(pend):
+                s = k & 3
+                k += 1
+                if pend[s]:
+                    self._chk(L.cornetto_bamfq_wait(self.h, fq, s))
+                    out.append(C.string_at(pins[s], pend[s]))
+                    pend[s] = 0
+                if at < n_text:
+                    n = min(slab or n_text, n_text - at)
+                    if cap[s] < n:
+                        if pins[s]:
+                            L.cornetto_pinned_free(pins[s])
+                        pins[s] = L.cornetto_pinned_alloc(n)
+                        cap[s] = n
+                        if not pins[s]:
+                            raise MemoryError("cornetto_pinned_alloc(%d)" % n)
+                    self._chk(L.cornetto_bamfq_get(self.h, fq, pins[s], at, n, s))
+                    pend[s] = n
+                    at += n
+        try:
+            opt = BamFqOpt()
+            L.cornetto_bamfq_defaults(C.byref(opt))
+            opt.min_len, opt.duplex, opt.n_ref, opt.records = min_len, int(bool(duplex)), len(lens), 1
+            if window is not None:
+                opt.window = window
+            fq = C.c_void_p()
+            self._chk(L.cornetto_bamfq_open(self.h, C.byref(opt), C.byref(fq)))
+            cuts = [len(blocks) * i // feeds for i in range(feeds + 1)]
+            for i in range(feeds):
+                part = np.ascontiguousarray(blocks[cuts[i]:cuts[i + 1]])
+                at, first = 0, True
+                while at < part.size or (first and i == 0):
+                    taken, n_text = C.c_int64(), C.c_int64()
+                    rc = L.cornetto_bamfq_feed(self.h, fq, comp, part[at:].ctypes.data if at < part.size else None, part.size - at, skip if i == 0 and first else 0,
+                                               C.byref(taken), C.byref(n_text))
+                    self.bam_timing += self.last_timing()
+                    first = False
+                    if rc not in (0, -6):
+                        self._chk(rc)
+                    pull(n_text.value)
+                    if rc == -6:
+                        raise fail()
+                    at += taken.value
+                    if part.size == 0:
+                        break
+            rc = L.cornetto_bamfq_finish(self.h, fq)
+            self.bam_timing += self.last_timing()          # (bamfq_text in all)
+            if rc == -6 and L.cornetto_bamfq_error(fq).contents.kind:
+                raise fail()
+            self._chk(rc)
+            return result()
+        finally:
+            for p in pins:
+                if p:
+                    L.cornetto_pinned_free(p)
+            if fq is not None and fq.value:
+                L.cornetto_bamfq_close(self.h, fq)
+            L.cornetto_text_free(self.h, comp)
 
     def bedgraph_runs_ingest(self, tot_pieces, mq_pieces, alternate=True):
         """stream two RUN-LENGTH bedgraphs (iterables of bytes pieces, any split points) through cornetto_bgrun_*; returns what

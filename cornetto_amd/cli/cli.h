@@ -245,6 +245,14 @@ void cli_bam_fail(const char *path, int kind, long long record, int a, int b);
  * path; exits through cli_bam_fail() on a malformed file */
 int cli_bam_ingest(cornetto_accel_t *h, const char *path, int min_mapq, cornetto_cov_t **cov, int32_t *n_ctg, char ***names, int64_t *n_clamped);
 void cli_host_cov_free(cli_host_cov_t *c);
+/* `seq --bam` (an extension): the FASTQ text of the BAM's records under the rules of cornetto_bamfq_*() (include/cornetto_accel.h) on stdout, read
+ * sequentially through zlib; the first skip_records records are checked and passed over (a caller printed and counted them); stats: reads and
+ * bases of both summary lines, added to; exits through cli_bam_fail() on a malformed file, the records in front of the failing one printed */
+void cli_host_bam_fastq(const char *path, int min_len, int duplex, int64_t skip_records, uint64_t stats[4]);
+/* cli/bam.c: the same through the device (cornetto_bamfq_*), a window of $CORNETTO_BAM_WINDOW bytes at a time, its text pulled in slabs of
+ * $CORNETTO_EMIT_SLAB bytes.  -> 0; non-zero when a record is larger than the window (a CLI_WARNING says so): *n_done records are printed and
+ * counted in stats, the caller reads the rest on the host */
+int cli_bam_fastq(cornetto_accel_t *h, const char *path, int min_len, int duplex, uint64_t stats[4], int64_t *n_done);
 
 /* ---- cli/bgcomp.c: compressed depth files of (no)boringbits (mosdepth writes *.per-base.bed.gz, which is BGZF) ---- */
 int cli_bgzf_first_member(int fd);   /* is what begins the file a BGZF member? */

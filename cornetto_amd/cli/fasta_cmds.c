@@ -326,12 +326,37 @@ int assbed_main(int argc, char *argv[])
 }
 
 /* ---------------------------------------------------------------- seq */
+static void seq_summary(int min_len, uint64_t before_n, uint64_t before, uint64_t after_n, uint64_t after)
+{
+    fprintf(stderr, "total reads: %lu\t%lu bases\t%.2f Gbases\n", (unsigned long)before_n, (unsigned long)before, before / 1e9);
+    fprintf(stderr, "reads >= %d: %lu\t%lu bases\t%.2f Gbases\n", min_len, (unsigned long)after_n, (unsigned long)after, after / 1e9);
+}
+
+/* `seq --bam FILE [--duplex]` (an extension; include/cornetto_accel.h states the rules): a basecaller's BAM to the text `seq` prints */
+static int seq_bam(const char *bam, int min_len, int duplex)
+{
+    uint64_t stats[4] = {0, 0, 0, 0};
+    int64_t n_done = 0;
+    if (!cli_host_mode()) {
+        cornetto_accel_t *h = cli_accel_open();
+        const int rest = cli_bam_fastq(h, bam, min_len, duplex, stats, &n_done);
+        cornetto_accel_close(h);
+        if (rest) cli_host_bam_fastq(bam, min_len, duplex, n_done, stats);
+    } else {
+        cli_host_bam_fastq(bam, min_len, duplex, 0, stats);
+    }
+    seq_summary(min_len, stats[0], stats[1], stats[2], stats[3]);
+    return 0;
+}
+
 int seq_main(int argc, char *argv[])
 {
-    static const struct option lo[] = {{"verbose", required_argument, 0, 'v'}, {"min-len", required_argument, 0, 'm'}, {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
+    static const struct option lo[] = {{"verbose", required_argument, 0, 'v'}, {"min-len", required_argument, 0, 'm'}, {"help", no_argument, 0, 'h'},
+                                       {"bam", required_argument, 0, 0}, {"duplex", no_argument, 0, 0}, {"accel", required_argument, 0, 0}, {0, 0, 0, 0}};
     FILE *fp_help = stderr;
     int min_len = 30000; /* src/seq.c:63 */
-    int c, li = 0;
+    int c, li = 0, duplex = 0;
+    const char *bam = NULL;
     optind = 1;
     while ((c = getopt_long(argc, argv, "hm:", lo, &li)) >= 0) {
         if (c == 'h') {
@@ -342,17 +367,40 @@ int seq_main(int argc, char *argv[])
                 fprintf(stderr, "Error: min-len must be a positive integer\n");
                 exit(EXIT_FAILURE);
             }
+        } else if (c == 0 && li == 3) {
+            bam = optarg;
+        } else if (c == 0 && li == 4) {
+            duplex = 1;
+        } else if (c == 0 && li == 5) {
+            if (strcmp(optarg, "no") == 0 || strcmp(optarg, "n") == 0) {
+                cli_host_set(1);
+            } else if (strcmp(optarg, "yes") == 0 || strcmp(optarg, "y") == 0) {
+                cli_host_set(0);
+            } else {
+                fprintf(stderr, "option '--accel' only accepts 'yes' or 'no'.\n");
+            }
         } else {
             fprintf(stderr, "Unknown option: %s\n", argv[optind - 1]);
             exit(EXIT_FAILURE);
         }
     }
-    if (argc - optind != 1 || fp_help == stdout) {
+    if (fp_help != stdout && bam && argc - optind != 0) {
+        CLI_ERROR("%s", "--bam takes the place of the FASTQ file: no positional file with it");
+        exit(EXIT_FAILURE);
+    }
+    if (fp_help != stdout && duplex && !bam) {
+        CLI_ERROR("%s", "--duplex: only with --bam (the dx tag is a field of a BAM record)");
+        exit(EXIT_FAILURE);
+    }
+    if ((!bam && argc - optind != 1) || fp_help == stdout) {
         fprintf(fp_help, "Usage: cornetto seq <reads.fastq> \n");
         fprintf(fp_help, "   -m INT                     min length [%d]\n", 30000);
         fprintf(fp_help, "   -h                         help\n");
+        fprintf(fp_help, "   --bam FILE                 (extension) the reads of a basecaller's BAM in place of <reads.fastq>, decoded on the device\n");
+        fprintf(fp_help, "   --duplex                   (extension) with --bam: only the reads with the tag dx:i:1\n");
         exit(fp_help == stdout ? EXIT_SUCCESS : EXIT_FAILURE);
     }
+    if (bam) return seq_bam(bam, min_len, duplex);
     cli_fastx_t *fx = cli_fastx_open(argv[optind], 1);
     cli_rec_t *r;
     uint64_t before = 0, after = 0, before_n = 0, after_n = 0;
@@ -368,8 +416,7 @@ int seq_main(int argc, char *argv[])
             printf("\n%s\n+\n%s\n", r->seq.s, r->qual.s);
         }
     }
-    fprintf(stderr, "total reads: %lu\t%lu bases\t%.2f Gbases\n", (unsigned long)before_n, (unsigned long)before, before / 1e9);
-    fprintf(stderr, "reads >= %d: %lu\t%lu bases\t%.2f Gbases\n", min_len, (unsigned long)after_n, (unsigned long)after, after / 1e9);
+    seq_summary(min_len, before_n, before, after_n, after);
     cli_fastx_close(fx);
     return 0;
 }

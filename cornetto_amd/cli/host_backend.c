@@ -739,7 +739,8 @@ static int bam_find_cg(const uint8_t *d, int64_t p, int64_t bs, const uint8_t **
     return 0;
 }
 
-void cli_host_get_depths_bam(const char *path, int min_mapq, cli_host_cov_t *out)
+/* the file opened, its magic, header text and contig count read (a buffer of *cap bytes comes back with it) -> n_ref; the contigs follow */
+static int32_t bam_host_open(const char *path, gzFile *fo, uint8_t **bufo, size_t *capo)
 {
     gzFile f = gzopen(path, "rb");
     if (!f) {
@@ -765,6 +766,61 @@ void cli_host_get_depths_bam(const char *path, int min_mapq, cli_host_cov_t *out
     if (bam_read(f, path, -1, w, 4) < 4) cli_bam_fail(path, 2, -1, 0, -1);
     const int32_t n_ref = (int32_t)bam_u32(w);
     if (n_ref < 0) cli_bam_fail(path, 7, -1, 0, 0);
+    *fo = f;
+    *bufo = buf;
+    *capo = cap;
+    return n_ref;
+}
+
+/* the next contig of the header -> its length, its name (NUL-terminated) in *buf */
+static int32_t bam_host_contig(gzFile f, const char *path, uint8_t **bufp, size_t *capp)
+{
+    uint8_t w[4];
+    if (bam_read(f, path, -1, w, 4) < 4) cli_bam_fail(path, 2, -1, 0, -1);
+    const int32_t l_name = (int32_t)bam_u32(w);
+    if (l_name < 1) cli_bam_fail(path, 7, -1, 0, 0);
+    if ((size_t)l_name + 4 > *capp) *bufp = (uint8_t *)cli_xrealloc(*bufp, *capp = (size_t)l_name + 4);
+    if (bam_read(f, path, -1, *bufp, (int64_t)l_name + 4) < (int64_t)l_name + 4) cli_bam_fail(path, 2, -1, 0, -1);
+    const int32_t l_ref = (int32_t)bam_u32(*bufp + l_name);
+    if (l_ref < 0) cli_bam_fail(path, 7, -1, 0, 0);
+    (*bufp)[l_name - 1] = 0;
+    return l_ref;
+}
+
+/* record `rec` of the file into *buf, checks 1 to 4 passed -> its block_size, or -1: the file ends in front of it */
+static int32_t bam_host_record(gzFile f, const char *path, long long rec, int32_t n_ref, uint8_t **bufp, size_t *capp)
+{
+    uint8_t w[4];
+    uint8_t *buf = *bufp;
+    size_t cap = *capp;
+    int64_t got = bam_read(f, path, rec, w, 4);
+    if (got == 0) return -1;
+    if (got < 4) cli_bam_fail(path, 2, rec, (int)got, -1);
+    const int32_t bs = (int32_t)bam_u32(w);
+    if (bs < 32) cli_bam_fail(path, 1, rec, bs, 0);
+    got = 0;
+    for (int64_t n = 0; got == n && n < bs;) {      /* (the buffer grows with the bytes that are there, not with what block_size says) */
+        if ((size_t)bs > cap && (size_t)n == cap) buf = (uint8_t *)cli_xrealloc(buf, cap = cap * 2 < (size_t)bs ? cap * 2 : (size_t)bs);
+        n = (int64_t)cap < bs ? (int64_t)cap : bs;
+        got += bam_read(f, path, rec, buf + got, n - got);
+    }
+    *bufp = buf;
+    *capp = cap;
+    if (got < bs) cli_bam_fail(path, 2, rec, bam_cap31(got + 4), bs);
+    const int32_t ref_id = (int32_t)bam_u32(buf);
+    const int64_t l_read_name = buf[8], n_cigar = (int64_t)buf[12] | ((int64_t)buf[13] << 8), l_seq = (int64_t)bam_u32(buf + 16);
+    const int64_t fixed = 32 + l_read_name + 4 * n_cigar + (l_seq + 1) / 2 + l_seq;
+    if (fixed > bs) cli_bam_fail(path, 3, rec, bam_cap31(fixed), bs);
+    if (ref_id < -1 || ref_id >= n_ref) cli_bam_fail(path, 4, rec, ref_id, n_ref);
+    return bs;
+}
+
+void cli_host_get_depths_bam(const char *path, int min_mapq, cli_host_cov_t *out)
+{
+    gzFile f = NULL;
+    uint8_t *buf = NULL;
+    size_t cap = 0;
+    const int32_t n_ref = bam_host_open(path, &f, &buf, &cap);
     /* every contig of the header, in its order; `all_first` places it in the arrays (a contig without positions has no line in a per-base
      * bedgraph: it is not a contig of the result) */
     int32_t *all_len = (int32_t *)cli_xmalloc(((size_t)n_ref + 1) * sizeof(int32_t));
@@ -776,14 +832,7 @@ void cli_host_get_depths_bam(const char *path, int min_mapq, cli_host_cov_t *out
     out->first[0] = 0;
     int64_t n_pos = 0;
     for (int32_t i = 0; i < n_ref; ++i) {
-        if (bam_read(f, path, -1, w, 4) < 4) cli_bam_fail(path, 2, -1, 0, -1);
-        const int32_t l_name = (int32_t)bam_u32(w);
-        if (l_name < 1) cli_bam_fail(path, 7, -1, 0, 0);
-        if ((size_t)l_name + 4 > cap) buf = (uint8_t *)cli_xrealloc(buf, cap = (size_t)l_name + 4);
-        if (bam_read(f, path, -1, buf, (int64_t)l_name + 4) < (int64_t)l_name + 4) cli_bam_fail(path, 2, -1, 0, -1);
-        const int32_t l_ref = (int32_t)bam_u32(buf + l_name);
-        if (l_ref < 0) cli_bam_fail(path, 7, -1, 0, 0);
-        buf[l_name - 1] = 0;
+        const int32_t l_ref = bam_host_contig(f, path, &buf, &cap);
         all_len[i] = l_ref;
         all_first[i] = n_pos;
         if (l_ref > 0) {
@@ -802,24 +851,12 @@ void cli_host_get_depths_bam(const char *path, int min_mapq, cli_host_cov_t *out
         }
     }
     for (long long rec = 0;; ++rec) {
-        got = bam_read(f, path, rec, w, 4);
-        if (got == 0) break;
-        if (got < 4) cli_bam_fail(path, 2, rec, (int)got, -1);
-        const int32_t bs = (int32_t)bam_u32(w);
-        if (bs < 32) cli_bam_fail(path, 1, rec, bs, 0);
-        got = 0;
-        for (int64_t n = 0; got == n && n < bs;) {      /* (the buffer grows with the bytes that are there, not with what block_size says) */
-            if ((size_t)bs > cap && (size_t)n == cap) buf = (uint8_t *)cli_xrealloc(buf, cap = cap * 2 < (size_t)bs ? cap * 2 : (size_t)bs);
-            n = (int64_t)cap < bs ? (int64_t)cap : bs;
-            got += bam_read(f, path, rec, buf + got, n - got);
-        }
-        if (got < bs) cli_bam_fail(path, 2, rec, bam_cap31(got + 4), bs);
+        const int32_t bs = bam_host_record(f, path, rec, n_ref, &buf, &cap);
+        if (bs < 0) break;
         const int32_t ref_id = (int32_t)bam_u32(buf), pos = (int32_t)bam_u32(buf + 4);
         const int64_t l_read_name = buf[8], n_cigar = (int64_t)buf[12] | ((int64_t)buf[13] << 8), l_seq = (int64_t)bam_u32(buf + 16);
         const int mapq = buf[9], flag = (int)buf[14] | ((int)buf[15] << 8);
         const int64_t fixed = 32 + l_read_name + 4 * n_cigar + (l_seq + 1) / 2 + l_seq;
-        if (fixed > bs) cli_bam_fail(path, 3, rec, bam_cap31(fixed), bs);
-        if (ref_id < -1 || ref_id >= n_ref) cli_bam_fail(path, 4, rec, ref_id, n_ref);
         if (ref_id < 0 || (flag & 0x704) != 0) continue;
         const uint8_t *cig = buf + 32 + l_read_name;
         int64_t n_ops = n_cigar;
@@ -878,6 +915,106 @@ void cli_host_get_depths_bam(const char *path, int min_mapq, cli_host_cov_t *out
     }
     out->n_pos = n_pos;
     out->positions = (double)n_pos;
+}
+
+/* ------------------------------------------------------------------------------------------------ seq --bam
+ * The FASTQ text of a BAM (an extension, see fasta_cmds.c and include/cornetto_accel.h for the rules): the file read sequentially through
+ * zlib, one record at a time, the checks and rules of the device reader in their order (csrc/bamfq.hpp). */
+/* csrc/bamfq.hpp: cnq_find_dx */
+static int bam_find_dx(const uint8_t *d, int64_t p, int64_t bs, int64_t *val)
+{
+    while (bs - p >= 3) {
+        const uint8_t t0 = d[p], t1 = d[p + 1], ty = d[p + 2];
+        int64_t sz;
+        p += 3;
+        if (ty == 'A' || ty == 'c' || ty == 'C') sz = 1;
+        else if (ty == 's' || ty == 'S') sz = 2;
+        else if (ty == 'i' || ty == 'I' || ty == 'f') sz = 4;
+        else if (ty == 'Z' || ty == 'H') {
+            while (p < bs && d[p] != 0) ++p;
+            if (p >= bs) return 0;
+            sz = 1;
+        } else if (ty == 'B') {
+            if (bs - p < 5) return 0;
+            const uint8_t sub = d[p];
+            const int64_t cnt = (int64_t)bam_u32(d + p + 1);
+            int64_t es;
+            p += 5;
+            if (sub == 'c' || sub == 'C') es = 1;
+            else if (sub == 's' || sub == 'S') es = 2;
+            else if (sub == 'i' || sub == 'I' || sub == 'f') es = 4;
+            else return 0;
+            sz = cnt * es;
+        } else return 0;
+        if (sz > bs - p) return 0;
+        if (t0 == 'd' && t1 == 'x' && (ty == 'c' || ty == 'C' || ty == 's' || ty == 'S' || ty == 'i' || ty == 'I')) {
+            const uint32_t lo16 = (uint32_t)d[p] | (sz > 1 ? (uint32_t)d[p + 1] << 8 : 0u);
+            if (ty == 'c') *val = (int8_t)d[p];
+            else if (ty == 'C') *val = d[p];
+            else if (ty == 's') *val = (int16_t)lo16;
+            else if (ty == 'S') *val = (int64_t)lo16;
+            else if (ty == 'i') *val = (int32_t)bam_u32(d + p);
+            else *val = (int64_t)bam_u32(d + p);
+            return 1;
+        }
+        p += sz;
+    }
+    return 0;
+}
+
+void cli_host_bam_fastq(const char *path, int min_len, int duplex, int64_t skip_records, uint64_t stats[4])
+{
+    static const char fwd[] = "=ACMGRSVTWYHKDBN", rev[] = "=TGKCYSBAWRDMHVN";
+    gzFile f = NULL;
+    uint8_t *buf = NULL;
+    size_t cap = 0, cap_line = 0;
+    char *line = NULL;
+    const int32_t n_ref = bam_host_open(path, &f, &buf, &cap);
+    for (int32_t i = 0; i < n_ref; ++i) (void)bam_host_contig(f, path, &buf, &cap);
+    for (long long rec = 0;; ++rec) {
+        const int32_t bs = bam_host_record(f, path, rec, n_ref, &buf, &cap);
+        if (bs < 0) break;
+        if (rec < skip_records) continue;      /* (printed and counted by the caller already) */
+        const int64_t l_read_name = buf[8], n_cigar = (int64_t)buf[12] | ((int64_t)buf[13] << 8), l_seq = (int64_t)bam_u32(buf + 16);
+        const int flag = (int)buf[14] | ((int)buf[15] << 8);
+        if (flag & 0x900) continue;
+        stats[0]++;
+        stats[1] += (uint64_t)l_seq;
+        if (l_seq < min_len) continue;
+        if (duplex) {
+            int64_t v = 0;
+            if (!bam_find_dx(buf, 32 + l_read_name + 4 * n_cigar + (l_seq + 1) / 2 + l_seq, bs, &v) || v != 1) continue;
+        }
+        stats[2]++;
+        stats[3] += (uint64_t)l_seq;
+        const int64_t name_len = l_read_name ? l_read_name - 1 : 0;
+        const size_t need = (size_t)(name_len + 2 * l_seq + 6);
+        if (need > cap_line) line = (char *)cli_xrealloc(line, cap_line = need * 2);
+        const uint8_t *seq = buf + 32 + l_read_name + 4 * n_cigar, *qual = seq + (l_seq + 1) / 2;
+        const int rv = (flag & 0x10) != 0, no_qual = l_seq > 0 && qual[0] == 0xFF;
+        char *o = line;
+        *o++ = '@';
+        memcpy(o, buf + 32, (size_t)name_len);
+        o += name_len;
+        *o++ = '\n';
+        for (int64_t i = 0; i < l_seq; ++i) {
+            const int64_t j = rv ? l_seq - 1 - i : i;
+            const int nib = (j & 1) ? (seq[j >> 1] & 15) : (seq[j >> 1] >> 4);
+            *o++ = rv ? rev[nib] : fwd[nib];
+        }
+        *o++ = '\n';
+        *o++ = '+';
+        *o++ = '\n';
+        for (int64_t i = 0; i < l_seq; ++i) {
+            const int q = qual[rv ? l_seq - 1 - i : i];
+            *o++ = no_qual ? '"' : (char)((q > 93 ? 93 : q) + 33);
+        }
+        *o++ = '\n';
+        fwrite(line, 1, need, stdout);
+    }
+    gzclose(f);
+    free(buf);
+    free(line);
 }
 
 void cli_host_cov_free(cli_host_cov_t *c)

@@ -1,8 +1,8 @@
 // bam.hip — both per-base coverage tracks from a BAM (include/cornetto_accel.h: cornetto_bamdepth_*, cornetto_bam_records).  The caller
 // puts the compressed bytes on the device and walks the BGZF chain (cornetto_bgzf_scan); per window of inflated bytes:
 //   bgzf_inflate / bgzf_crc32   (inflate.hip) the window's blocks behind the tail the last window left
-//   bam_frame     the record chain — block_size, then that many bytes — followed by one wave (its first lane: every hop is one dependent
-//                 load): the offsets of the records that lie wholly in the window
+//   bam_frame     (bamwin.hpp: the window is shared with bamfq.hip) the record chain — block_size, then that many bytes — followed by one
+//                 wave (its first lane: every hop is one dependent load): the offsets of the records that lie wholly in the window
 //   bam_depth     a wave per record, grid-stride: the checks and the CIGAR walk of bam.hpp, 64 operations per batch, one wave scan of the
 //                 reference-advancing lengths per batch; a +1 / -1 pair of integer atomics per run of M = X operations into an int32
 //                 difference array per track, laid out like the coverage object (every contig at a multiple of 64 elements): the -1 at a
@@ -12,6 +12,7 @@
 //                 mod 2^32, and every prefix is a depth >= 0), clamped to uint16 with the clamped positions counted: the two arrays
 //                 cornetto_cov_wrap() takes.
 #include "bam.hpp"
+#include "bamwin.hpp"
 #include "common.hpp"
 #include "scan.hpp"
 
@@ -49,20 +50,8 @@ struct NoSink {
     __device__ void add(int64_t, int, bool) {}
 };
 
-// words of the small device block
-enum { SM_NREC = 0, SM_END = 1, SM_FERR = 2, SM_FERR_A = 3, SM_ERR = 4, SM_COUNTED = 5, SM_CLAMP = 6, SM_DET = 8, SM_WORDS = 16 };
-
-__global__ void __launch_bounds__(64) bam_frame(const uint8_t *__restrict__ text, int64_t at, int64_t n, uint32_t *__restrict__ off, int64_t cap, unsigned long long *sm)
-{
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    int64_t end;
-    int32_t err, a;
-    const int64_t k = cnb_frame(text, at, n, off, cap, &end, &err, &a);
-    sm[SM_NREC] = (unsigned long long)k;
-    sm[SM_END] = (unsigned long long)end;
-    sm[SM_FERR] = (unsigned long long)err;
-    sm[SM_FERR_A] = (unsigned long long)(long long)a;
-}
+// words of the small device block behind the window's own (bamwin.hpp)
+enum { SM_ERR = cnbw::BW_ERR, SM_COUNTED = cnbw::BW_OWN, SM_CLAMP = 6, SM_DET = 8, SM_WORDS = cnbw::BW_WORDS };
 
 struct BdArgs {
     const uint8_t *text;
@@ -194,13 +183,9 @@ struct cornetto_bamdepth {
     int32_t *d_len = nullptr;
     int64_t *d_off = nullptr;
     int32_t *d_diff[2] = {nullptr, nullptr};
-    cornetto_text_t *win = nullptr;    // the window: opt.window bytes
-    uint8_t *d_tail = nullptr;         // staging of a tail that overlaps its new place
-    uint32_t *d_recoff = nullptr;
-    int64_t rec_cap = 0;
+    cnbw::Win w;                       // the window: opt.window bytes, its tail, record offsets and counters
     cornetto_bamrec_t *d_recs = nullptr;
-    unsigned long long *d_sm = nullptr;
-    int64_t carry = 0, skip_left = 0, text_off = 0, n_rec = 0, n_counted = 0, n_blocks = 0;
+    int64_t n_counted = 0;
     std::vector<cornetto_bamrec_t> recs;
     cornetto_bamerr_t err{0, 0, 0, 0, 0};
     bool finished = false;
@@ -217,18 +202,18 @@ int bam_error(cornetto_accel_t *h, cornetto_bamdepth_t *b, int kind, int64_t rec
 BdArgs bd_args(const cornetto_bamdepth_t *b, int64_t n)
 {
     BdArgs A{};
-    A.text = b->win->d;
-    A.off = b->d_recoff;
+    A.text = b->w.win->d;
+    A.off = b->w.d_recoff;
     A.n_rec = n;
-    A.base_rec = b->n_rec;
-    A.text_off = b->text_off;
+    A.base_rec = b->w.n_rec;
+    A.text_off = b->w.text_off;
     A.R = CnbRefs{b->n_ref, b->d_len, b->d_off};
     A.min_mapq = b->opt.min_mapq;
     A.skip_flags = b->opt.skip_flags;
     A.diff[0] = b->d_diff[0];
     A.diff[1] = b->d_diff[1];
     A.recs = b->d_recs;
-    A.sm = b->d_sm;
+    A.sm = b->w.d_sm;
     return A;
 }
 
@@ -237,27 +222,19 @@ int bam_window(cornetto_accel_t *h, cornetto_bamdepth_t *b, int64_t n_text)
 {
     unsigned long long *p_sm = (unsigned long long *)cn_pin(h, PIN_SMALL, SM_WORDS * 8);
     if (!p_sm) return cn_fail(h, CORNETTO_E_NOMEM, "bamdepth_feed: pinned allocation failed");
-    const int64_t start = std::min(b->skip_left, n_text);      // (bytes are skipped only while nothing is carried)
-    b->skip_left -= start;
-    CN_HIP(h, hipMemsetAsync(b->d_sm, 0, SM_WORDS * 8, h->stream));
-    CN_HIP(h, hipMemsetAsync(b->d_sm + SM_ERR, 0xFF, 8, h->stream));
-    CN_LAUNCH(h, "bam_frame", bam_frame<<<dim3(1), dim3(64), 0, h->stream>>>(b->win->d, start, n_text, b->d_recoff, b->rec_cap, b->d_sm));
-    CN_HIP(h, hipMemcpyAsync(p_sm, b->d_sm, 32, hipMemcpyDeviceToHost, h->stream));
-    CN_HIP(h, hipStreamSynchronize(h->stream));
-    const int64_t n = (int64_t)p_sm[SM_NREC], end = (int64_t)p_sm[SM_END];
-    const int ferr = (int)p_sm[SM_FERR];
-    const int64_t ferr_a = (int64_t)p_sm[SM_FERR_A];
-    if (n < 0 || n > b->rec_cap || end < start || end > n_text) return cn_fail(h, CORNETTO_E_HIP, "bamdepth_feed: the record chain left its window");
+    int64_t n = 0, end = 0, ferr_a = 0;
+    int ferr = CNB_OK;
+    CN_TRY(cnbw::win_frame(h, b->w, "bamdepth_feed", n_text, p_sm, &n, &end, &ferr, &ferr_a));
     BdArgs A = bd_args(b, n);
     if (n > 0) {
         const int64_t blocks = std::min<int64_t>((n + 3) / 4, 16384);
         CN_LAUNCH(h, "bam_depth", bam_depth<<<dim3((unsigned)blocks), dim3(256), 0, h->stream>>>(A));
-        CN_HIP(h, hipMemcpyAsync(p_sm + SM_ERR, b->d_sm + SM_ERR, 16, hipMemcpyDeviceToHost, h->stream));
+        CN_HIP(h, hipMemcpyAsync(p_sm + SM_ERR, b->w.d_sm + SM_ERR, 16, hipMemcpyDeviceToHost, h->stream));
         CN_HIP(h, hipStreamSynchronize(h->stream));
         if (p_sm[SM_ERR] != ~0ull) {
             const int64_t rec = (int64_t)(p_sm[SM_ERR] >> 4);
-            CN_LAUNCH(h, "bam_detail", bam_detail<<<dim3(1), dim3(64), 0, h->stream>>>(A, rec - b->n_rec));
-            CN_HIP(h, hipMemcpyAsync(p_sm + SM_DET, b->d_sm + SM_DET, 16, hipMemcpyDeviceToHost, h->stream));
+            CN_LAUNCH(h, "bam_detail", bam_detail<<<dim3(1), dim3(64), 0, h->stream>>>(A, rec - b->w.n_rec));
+            CN_HIP(h, hipMemcpyAsync(p_sm + SM_DET, b->w.d_sm + SM_DET, 16, hipMemcpyDeviceToHost, h->stream));
             CN_HIP(h, hipStreamSynchronize(h->stream));
             return bam_error(h, b, (int)(p_sm[SM_ERR] & 15), rec, (int64_t)p_sm[SM_DET], (int64_t)p_sm[SM_DET + 1]);
         }
@@ -269,21 +246,9 @@ int bam_window(cornetto_accel_t *h, cornetto_bamdepth_t *b, int64_t n_text)
             CN_HIP(h, hipStreamSynchronize(h->stream));
         }
     }
-    b->n_rec += n;
-    if (ferr != CNB_OK) return bam_error(h, b, ferr, b->n_rec, ferr_a, 0);
-    const int64_t carry = n_text - end;
-    if (carry > 0 && end > 0) {
-        if (carry <= end) {
-            CN_HIP(h, hipMemcpyAsync(b->win->d, b->win->d + end, (size_t)carry, hipMemcpyDeviceToDevice, h->stream));
-        } else {
-            CN_HIP(h, hipMemcpyAsync(b->d_tail, b->win->d + end, (size_t)carry, hipMemcpyDeviceToDevice, h->stream));
-            CN_HIP(h, hipMemcpyAsync(b->win->d, b->d_tail, (size_t)carry, hipMemcpyDeviceToDevice, h->stream));
-        }
-        CN_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    b->carry = carry;
-    b->text_off += end;
-    return CORNETTO_OK;
+    b->w.n_rec += n;
+    if (ferr != CNB_OK) return bam_error(h, b, ferr, b->w.n_rec, ferr_a, 0);
+    return cnbw::win_carry(h, b->w, n_text, end);
 }
 
 }  // namespace
@@ -312,8 +277,8 @@ void cornetto_bamdepth_close(cornetto_accel_t *h, cornetto_bamdepth_t *b)
 {
     if (!b) return;
     if (h) (void)hipSetDevice(h->device);
-    if (b->win) cornetto_text_free(h, b->win);
-    void *blocks[] = {b->d_len, b->d_off, b->d_diff[0], b->d_diff[1], b->d_tail, b->d_recoff, b->d_recs, b->d_sm};
+    cnbw::win_close(h, b->w);
+    void *blocks[] = {b->d_len, b->d_off, b->d_diff[0], b->d_diff[1], b->d_recs};
     for (void *p : blocks)
         if (p) (void)hipFree(p);
     delete b;
@@ -340,13 +305,12 @@ int cornetto_bamdepth_open(cornetto_accel_t *h, const cornetto_bamdepth_opt_t *o
         pos = cn_align_up(pos + lens[i], 64);
     }
     b->n_alloc = cn_align_up(pos + 64, BS_TILE);
-    b->rec_cap = opt->window / 36 + 2;
     const int rc = [&]() -> int {
-        CN_TRY(cornetto_text_open(h, opt->window, &b->win));
-        bool ok = hipMalloc((void **)&b->d_len, (size_t)std::max(n_ref, 1) * 4) == hipSuccess && hipMalloc((void **)&b->d_off, (size_t)std::max(n_ref, 1) * 8) == hipSuccess &&
-                  hipMalloc((void **)&b->d_tail, (size_t)opt->window) == hipSuccess && hipMalloc((void **)&b->d_recoff, (size_t)b->rec_cap * 4) == hipSuccess &&
-                  hipMalloc((void **)&b->d_sm, SM_WORDS * 8) == hipSuccess;
-        if (ok && opt->records) ok = hipMalloc((void **)&b->d_recs, (size_t)b->rec_cap * sizeof(cornetto_bamrec_t)) == hipSuccess;
+        const int ro = cnbw::win_open(h, b->w, opt->window);
+        if (ro != CORNETTO_OK && ro != CORNETTO_E_NOMEM) return ro;
+        bool ok = ro == CORNETTO_OK && hipMalloc((void **)&b->d_len, (size_t)std::max(n_ref, 1) * 4) == hipSuccess &&
+                  hipMalloc((void **)&b->d_off, (size_t)std::max(n_ref, 1) * 8) == hipSuccess;
+        if (ok && opt->records) ok = hipMalloc((void **)&b->d_recs, (size_t)b->w.rec_cap * sizeof(cornetto_bamrec_t)) == hipSuccess;
         if (ok && opt->records != 2)
             for (int q = 0; q < 2 && ok; ++q) ok = hipMalloc((void **)&b->d_diff[q], (size_t)b->n_alloc * 4) == hipSuccess;
         if (!ok) return cn_fail(h, CORNETTO_E_NOMEM, "bamdepth_open: device allocation failed (%lld positions)", (long long)b->n_alloc);
@@ -374,29 +338,22 @@ int cornetto_bamdepth_feed(cornetto_accel_t *h, cornetto_bamdepth_t *b, cornetto
     if (!h || !b || !comp || n_blocks < 0 || (n_blocks > 0 && !blocks) || skip < 0) return cn_fail(h, CORNETTO_E_ARG, "bamdepth_feed: bad argument");
     if (b->finished) return cn_fail(h, CORNETTO_E_ARG, "bamdepth_feed: the object is finished");
     if (b->err.kind) return CORNETTO_E_FORMAT;
-    if (skip > 0 && (b->carry > 0 || b->n_rec > 0 || b->text_off > 0))
+    if (skip > 0 && (b->w.carry > 0 || b->w.n_rec > 0 || b->w.text_off > 0))
         return cn_fail(h, CORNETTO_E_ARG, "bamdepth_feed: bytes can be skipped only in front of the first record");
     for (int64_t i = 0; i < n_blocks; ++i)
         if (blocks[i].n_dst < 0 || blocks[i].n_dst > 65536) return cn_fail(h, CORNETTO_E_ARG, "bamdepth_feed: block %lld has no BGZF size", (long long)i);
     CN_HIP(h, hipSetDevice(h->device));
-    b->skip_left += skip;
+    b->w.skip_left += skip;
     std::vector<std::pair<const char *, float>> times;      // (every inflate call opens a timing bracket of its own: the call's kernels are put together here)
     std::vector<cornetto_bgzf_block_t> grp;
     int64_t i = 0;
     while (i < n_blocks) {
-        grp.clear();
-        int64_t fill = b->carry, j = i;
-        while (j < n_blocks && fill + blocks[j].n_dst <= b->opt.window) {
-            cornetto_bgzf_block_t x = blocks[j];
-            x.dst = fill;
-            fill += x.n_dst;
-            grp.push_back(x);
-            ++j;
-        }
+        int64_t fill = 0;
+        const int64_t j = i + cnbw::win_place(b->w, blocks + i, n_blocks - i, grp, &fill);
         if (j == i) return cn_fail(h, CORNETTO_E_NOMEM, "bamdepth_feed: a record of more than %lld bytes does not fit the window of %lld with one more block",
-                                   (long long)b->carry, (long long)b->opt.window);
+                                   (long long)b->w.carry, (long long)b->opt.window);
         int64_t bad = -1;
-        const int rc = cornetto_text_inflate(h, comp, b->win, grp.data(), (int64_t)grp.size(), &bad);
+        const int rc = cornetto_text_inflate(h, comp, b->w.win, grp.data(), (int64_t)grp.size(), &bad);
         times.insert(times.end(), h->last.begin(), h->last.end());
         if (rc != CORNETTO_OK && !(rc == CORNETTO_E_FORMAT && bad >= 0)) return rc;
         const int64_t n_text = bad >= 0 ? grp[(size_t)bad].dst : fill;     // a bad block: the records in front of it first
@@ -407,13 +364,13 @@ int cornetto_bamdepth_feed(cornetto_accel_t *h, cornetto_bamdepth_t *b, cornetto
         h->last = times;
         if (rw != CORNETTO_OK) return rw;
         if (bad >= 0) {
-            const int re = bam_error(h, b, CNB_BGZF, b->n_rec, b->n_blocks + i + bad, 0);
+            const int re = bam_error(h, b, CNB_BGZF, b->w.n_rec, b->w.n_blocks + i + bad, 0);
             h->last = times;
             return re;
         }
         i = j;
     }
-    b->n_blocks += n_blocks;
+    b->w.n_blocks += n_blocks;
     return CORNETTO_OK;
 }
 
@@ -424,13 +381,13 @@ int cornetto_bamdepth_finish(cornetto_accel_t *h, cornetto_bamdepth_t *b, cornet
     if (b->finished) return cn_fail(h, CORNETTO_E_ARG, "bamdepth_finish: the object is finished");
     *cov = nullptr;
     CN_HIP(h, hipSetDevice(h->device));
-    if (b->skip_left > 0) return bam_error(h, b, CNB_TRUNC, -1, 0, -1);
-    if (b->carry > 0) {       // bytes that are no whole record
+    if (b->w.skip_left > 0) return bam_error(h, b, CNB_TRUNC, -1, 0, -1);
+    if (b->w.carry > 0) {       // bytes that are no whole record
         uint8_t head[4] = {0, 0, 0, 0};
-        if (b->carry >= 4) CN_HIP(h, hipMemcpy(head, b->win->d, 4, hipMemcpyDeviceToHost));
-        return bam_error(h, b, CNB_TRUNC, b->n_rec, b->carry, b->carry >= 4 ? (int64_t)(int32_t)cnb_u32(head) : -1);
+        if (b->w.carry >= 4) CN_HIP(h, hipMemcpy(head, b->w.win->d, 4, hipMemcpyDeviceToHost));
+        return bam_error(h, b, CNB_TRUNC, b->w.n_rec, b->w.carry, b->w.carry >= 4 ? (int64_t)(int32_t)cnb_u32(head) : -1);
     }
-    if (n_records) *n_records = b->n_rec;
+    if (n_records) *n_records = b->w.n_rec;
     if (n_counted) *n_counted = b->n_counted;
     if (n_clamped) *n_clamped = 0;
     if (b->opt.records == 2) {
@@ -448,10 +405,10 @@ int cornetto_bamdepth_finish(cornetto_accel_t *h, cornetto_bamdepth_t *b, cornet
     const int rc = [&]() -> int {
         if (!ok) return cn_fail(h, CORNETTO_E_NOMEM, "bamdepth_finish: device allocation failed (%lld positions)", (long long)b->n_alloc);
         CN_HIP(h, hipMemsetAsync(state.p, 0, state.bytes, h->stream));
-        CN_HIP(h, hipMemsetAsync(b->d_sm, 0, SM_WORDS * 8, h->stream));
-        BsArgs A{{b->d_diff[0], b->d_diff[1]}, {d_out[0], d_out[1]}, np, reinterpret_cast<unsigned long long *>((uint8_t *)state.p + 64), (uint32_t *)state.p, b->d_sm + SM_CLAMP};
+        CN_HIP(h, hipMemsetAsync(b->w.d_sm, 0, SM_WORDS * 8, h->stream));
+        BsArgs A{{b->d_diff[0], b->d_diff[1]}, {d_out[0], d_out[1]}, np, reinterpret_cast<unsigned long long *>((uint8_t *)state.p + 64), (uint32_t *)state.p, b->w.d_sm + SM_CLAMP};
         CN_LAUNCH(h, "bam_scan", bam_scan<<<dim3((unsigned)(2 * np)), dim3(BS_THREADS), 0, h->stream>>>(A));
-        CN_HIP(h, hipMemcpyAsync(p_sm, b->d_sm + SM_CLAMP, 8, hipMemcpyDeviceToHost, h->stream));
+        CN_HIP(h, hipMemcpyAsync(p_sm, b->w.d_sm + SM_CLAMP, 8, hipMemcpyDeviceToHost, h->stream));
         CN_HIP(h, hipStreamSynchronize(h->stream));
         return CORNETTO_OK;
     }();

@@ -661,6 +661,66 @@ int cornetto_bamdepth_finish(cornetto_accel_t *h, cornetto_bamdepth_t *b, cornet
 int cornetto_bam_records(cornetto_accel_t *h, cornetto_bamdepth_t *b, cornetto_bamrec_t **recs, int64_t *n_recs);
 
 /* ---------------------------------------------------------------------------------------------------
+ * BAM to FASTQ: the length-filtered FASTQ text of a basecaller's (unaligned or aligned) BAM on the device: `seq --bam`.  An EXTENSION (the
+ * reference's `seq` reads FASTQ text, src/seq.c:63-129; the protocol leaves the step from dorado's BAM to that text to the user, who runs
+ * `samtools view -d dx:1 | samtools fastq` in front of it).  The rules:
+ *   - records are taken in file order; the header is skipped with cornetto_bam_header() (no reference contig is the normal case); the checks
+ *     of cornetto_bamerr_t kinds 1, 2, 3, 4 and 6 apply unchanged, and nothing of a record is printed before its checks have passed;
+ *   - a record with flag & 0x900 (SECONDARY, SUPPLEMENTARY) is passed over: it counts nowhere.  Every other record counts in `total reads`
+ *     with l_seq bases;
+ *   - a record is kept iff l_seq >= min_len and, with `duplex`, it has an auxiliary field dx of an integer type (c C s S i I) with the value
+ *     1.  The search obeys the rule of the CG search: every field is checked against the record's end before it is read, fields that do not
+ *     parse end the search; a dx of any other type is no tag;
+ *   - a kept record prints as "@name\nBASES\n+\nQUALITIES\n" (what src/seq.c:120-129 prints for a record without a comment):
+ *     name: the first l_read_name - 1 bytes of read_name (none if l_read_name is 0); bases: "=ACMGRSVTWYHKDBN"[nibble], high nibble first;
+ *     qualities: min(q, 93) + 33, and if the first quality byte is 0xFF they are absent and every one prints as '"' (samtools fastq -v 1);
+ *   - flag & 0x10 reverses the bases and complements them with "=TGKCYSBAWRDMHVN", and reverses the qualities;
+ *   - so l_seq == 0 with min_len 0 prints "@name\n\n+\n\n".
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t min_len;     /* keep l_seq >= this (30000: src/seq.c:63) */
+    int32_t duplex;      /* non-zero: keep only records with dx:1 */
+    int64_t window;      /* bytes of inflated BAM held on the device at once, at most 2^31: an operating parameter, never changes a result.
+                            It must hold the largest record and one BGZF block more (CORNETTO_E_NOMEM otherwise) */
+    int32_t n_ref;       /* reference contigs of the header (check 4) */
+    int32_t records;     /* non-zero: keep the record table (cornetto_bamfq_records) */
+} cornetto_bamfq_opt_t;
+void cornetto_bamfq_defaults(cornetto_bamfq_opt_t *opt);
+
+/* one record as the size pass read it */
+typedef struct {
+    int64_t offset;   /* of its block_size field in the inflated file */
+    int32_t l_seq, flag, name_len;
+    int32_t kept;     /* 1: printed; 0: too short or without dx:1; -1: passed over (flag & 0x900) */
+} cornetto_bamfqrec_t;
+
+typedef struct cornetto_bamfq cornetto_bamfq_t;
+int cornetto_bamfq_open(cornetto_accel_t *h, const cornetto_bamfq_opt_t *opt, cornetto_bamfq_t **out);
+void cornetto_bamfq_close(cornetto_accel_t *h, cornetto_bamfq_t *b);
+/* ONE window: the leading blocks of blocks[0 .. n_blocks) that fit behind the tail the last window left (*taken of them; blocks, comp and
+ * skip as in cornetto_bamdepth_feed()) are inflated and framed, every record checked and sized (bamfq_size: name_len + 2 l_seq + 6 bytes
+ * for a kept record, 0 otherwise), the sizes scanned into text offsets (scan.hpp).  *n_text: bytes of the window's text, ready for
+ * cornetto_bamfq_get() until the next feed.  CORNETTO_E_FORMAT (cornetto_bamfq_error(); the record with the lowest index decides): the
+ * window's text is that of the records in front of the failing one, and may be fetched; no further feed is taken.  CORNETTO_E_NOMEM with
+ * *taken == 0: the first block does not fit the window behind the carried bytes.  Synchronous: `comp` may be overwritten on return. */
+int cornetto_bamfq_feed(cornetto_accel_t *h, cornetto_bamfq_t *b, cornetto_text_t *comp, const cornetto_bgzf_block_t *blocks, int64_t n_blocks,
+                        int64_t skip, int64_t *taken, int64_t *n_text);
+/* Bytes [at, at + n) of the window's text into `dst_pinned` (cornetto_pinned_alloc), through a device slab (bamfq_text: a workgroup writes a
+ * tile of the text, a thread 16 bytes) on copy slot 0..3, asynchronously as cornetto_emit_get(): the copy of one slab runs beside the
+ * kernel of the next.  cornetto_bamfq_wait(): the last get of the slot is in its buffer.  Every get of a window ends before the next feed
+ * (the feed waits for all four slots). */
+int cornetto_bamfq_get(cornetto_accel_t *h, cornetto_bamfq_t *b, char *dst_pinned, int64_t at, int64_t n, int slot);
+int cornetto_bamfq_wait(cornetto_accel_t *h, cornetto_bamfq_t *b, int slot);
+/* After the last feed: a file that ends inside a record is kind 2. */
+int cornetto_bamfq_finish(cornetto_accel_t *h, cornetto_bamfq_t *b);
+/* stats[0 .. 5): reads and bases of `total reads`, reads and bases of `reads >= min_len`, then the records taken (the passed-over ones
+ * among them), over the feeds so far (on an error: of the records in front of the failing one) */
+void cornetto_bamfq_stats(const cornetto_bamfq_t *b, int64_t *stats);
+const cornetto_bamerr_t *cornetto_bamfq_error(const cornetto_bamfq_t *b);
+/* The record table of the feeds so far (opt.records), in file order: cornetto_free(). */
+int cornetto_bamfq_records(cornetto_accel_t *h, cornetto_bamfq_t *b, cornetto_bamfqrec_t **recs, int64_t *n_recs);
+
+/* ---------------------------------------------------------------------------------------------------
  * fixasm output text: the records of a resident assembly, renamed and reoriented
  * ------------------------------------------------------------------------------------------------- */
 
