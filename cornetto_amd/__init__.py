@@ -186,6 +186,7 @@ def lib(dev=False):
         "cornetto_bgzf_scan": (C.c_int, [vp, i64, i64, C.POINTER(i64), vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]),
         "cornetto_text_inflate": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(i64)]),
         "cornetto_text_gather": (C.c_int, [vp, vp, vp, vp, i64, vp]),
+        "cornetto_text_deflate": (C.c_int, [vp, vp, i64, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)]),
         "cornetto_emit_open": (C.c_int, [vp, vp, vp, i64, vp, i64, pp, C.POINTER(i64)]),
         "cornetto_emit_get": (C.c_int, [vp, vp, vp, i64, i64, C.c_int]),
         "cornetto_emit_wait": (C.c_int, [vp, vp, C.c_int]),
@@ -255,6 +256,8 @@ def lib(dev=False):
         "cornetto_bamfq_feed": (C.c_int, [vp, vp, vp, vp, i64, i64, C.POINTER(i64), C.POINTER(i64)]),
         "cornetto_bamfq_get": (C.c_int, [vp, vp, vp, i64, i64, C.c_int]),
         "cornetto_bamfq_wait": (C.c_int, [vp, vp, C.c_int]),
+        "cornetto_bamfq_get_bgzf": (C.c_int, [vp, vp, vp, i64, i64, i64, C.c_int]),
+        "cornetto_bamfq_wait_bgzf": (C.c_int, [vp, vp, C.c_int, C.POINTER(i64)]),
         "cornetto_bamfq_finish": (C.c_int, [vp, vp]),
         "cornetto_bamfq_stats": (None, [vp, C.POINTER(i64)]),
         "cornetto_bamfq_error": (C.POINTER(BamErr), [vp]),
@@ -576,6 +579,26 @@ class Accel:
             return self._text_bytes(out, total), bad.value
         finally:
             self.L.cornetto_text_free(self.h, comp)
+            if out is not None:
+                self.L.cornetto_text_free(self.h, out)
+
+    def bgzf_deflate(self, data, at=0, n=None, out_cap=None):
+        """bytes [at, at + n) of `data` (by default: from `at` to its end) deflated into BGZF members on the device (cornetto_text_deflate:
+        text_open, put, deflate, gather) -> the bytes of the chain, a member for every 65280 bytes, no end-of-file block.  out_cap: the
+        capacity of the output text (by default what the call asks for: 65536 bytes a member).  The kernel times are kept in
+        self.deflate_timing, the number of members in self.deflate_members."""
+        n = len(data) - at if n is None else n
+        n_mem = (n + 65279) // 65280
+        text = self._text_from(data)
+        out = None
+        try:
+            out = self._text_from(b"", cap=n_mem * 65536 if out_cap is None else out_cap)
+            n_out, members = C.c_int64(-1), C.c_int64(-1)
+            self._chk(self.L.cornetto_text_deflate(self.h, text, at, n, out, 0, C.byref(n_out), C.byref(members)))
+            self.deflate_timing, self.deflate_members = self.last_timing(), members.value
+            return self._text_bytes(out, n_out.value) if n_out.value else b""
+        finally:
+            self.L.cornetto_text_free(self.h, text)
             if out is not None:
                 self.L.cornetto_text_free(self.h, out)
 

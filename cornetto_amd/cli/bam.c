@@ -1,4 +1,4 @@
-/* bam.c — `(no)boringbits --bam FILE`: both coverage tracks from the BAM on the device, and `seq --bam FILE`: its FASTQ text (extensions;
+/* bam.c — `(no)boringbits --bam FILE`: both coverage tracks from the BAM on the device, and `seq --bam FILE [--bgzf]`: its FASTQ text (extensions;
  * include/cornetto_accel.h states the rules of both; they share the reader below and differ in the object they feed).
  * The compressed file is read a chunk at a time into ONE pinned slab (no ring, no reader thread yet: read, upload and kernels follow
  * each other); the host walks the BGZF chain of the chunk
@@ -264,7 +264,10 @@ int cli_bam_fastq(cornetto_accel_t *h, const char *path, int min_len, int duplex
     (void)cornetto_accel_set_timing(h, 0);      /* (nobody reads the kernel times here: no event packets beside the kernels) */
     bam_reader_t R;
     bam_reader_open(h, &R, path, opt.window);
-    char *pin[2] = {(char *)cornetto_pinned_alloc((size_t)slab_bytes), (char *)cornetto_pinned_alloc((size_t)slab_bytes)};
+    /* --bgzf: the slab's text is deflated on the device, its members come back: 64 KiB of room for every 65280 bytes of text */
+    const int bgzf = cli_bgzf_out_active();
+    const int64_t pin_bytes = bgzf ? (slab_bytes + 65279) / 65280 * 65536 : slab_bytes;
+    char *pin[2] = {(char *)cornetto_pinned_alloc((size_t)pin_bytes), (char *)cornetto_pinned_alloc((size_t)pin_bytes)};
     if (!pin[0] || !pin[1]) {
         CLI_ERROR("%s", "cannot allocate the pinned output buffers");
         exit(EXIT_FAILURE);
@@ -300,7 +303,12 @@ int cli_bam_fastq(cornetto_accel_t *h, const char *path, int min_len, int duplex
             int64_t at = 0, len[2] = {0, 0};
             for (int k = 0; at < n_text || len[0] || len[1]; ++k) {
                 const int s = k & 1;
-                if (len[s]) {
+                if (len[s] && bgzf) {
+                    int64_t n_comp = 0;
+                    cli_accel_check(h, cornetto_bamfq_wait_bgzf(h, b, s, &n_comp), "BAM to FASTQ");
+                    cli_bgzf_out_members(pin[s], (size_t)n_comp);
+                    len[s] = 0;
+                } else if (len[s]) {
                     cli_accel_check(h, cornetto_bamfq_wait(h, b, s), "BAM to FASTQ");
                     if (fwrite(pin[s], 1, (size_t)len[s], stdout) != (size_t)len[s]) {
                         CLI_ERROR("%s", "cannot write to the standard output");
@@ -310,7 +318,8 @@ int cli_bam_fastq(cornetto_accel_t *h, const char *path, int min_len, int duplex
                 }
                 if (at < n_text) {
                     len[s] = n_text - at < slab_bytes ? n_text - at : slab_bytes;
-                    cli_accel_check(h, cornetto_bamfq_get(h, b, pin[s], at, len[s], s), "BAM to FASTQ");
+                    if (bgzf) cli_accel_check(h, cornetto_bamfq_get_bgzf(h, b, pin[s], pin_bytes, at, len[s], s), "BAM to FASTQ");
+                    else cli_accel_check(h, cornetto_bamfq_get(h, b, pin[s], at, len[s], s), "BAM to FASTQ");
                     at += len[s];
                 }
             }

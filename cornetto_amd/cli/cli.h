@@ -253,6 +253,16 @@ void cli_host_bam_fastq(const char *path, int min_len, int duplex, int64_t skip_
  * $CORNETTO_EMIT_SLAB bytes.  -> 0; non-zero when a record is larger than the window (a CLI_WARNING says so): *n_done records are printed and
  * counted in stats, the caller reads the rest on the host */
 int cli_bam_fastq(cornetto_accel_t *h, const char *path, int min_len, int duplex, uint64_t stats[4], int64_t *n_done);
+/* cli/bgzf_out.c: `seq --bam --bgzf` (an extension): between _begin() and _end() the text of both readers above leaves as a BGZF stream on stdout.
+ * _text(): text, collected into members of 65280 bytes through zlib; _members(): members the device made (cornetto_bamfq_get_bgzf), behind the
+ * pending text; _flush(): the pending text as a member — cli_bam_fail() calls it, so a malformed file leaves the members of the records in front
+ * of the failing one; _end(): the same and the 28-byte end-of-file block, on success only */
+void cli_bgzf_out_begin(void);
+int cli_bgzf_out_active(void);
+void cli_bgzf_out_text(const void *p, size_t n);
+void cli_bgzf_out_members(const void *p, size_t n);
+void cli_bgzf_out_flush(void);
+void cli_bgzf_out_end(void);
 
 /* ---- cli/bgcomp.c: compressed depth files of (no)boringbits (mosdepth writes *.per-base.bed.gz, which is BGZF) ---- */
 int cli_bgzf_first_member(int fd);   /* is what begins the file a BGZF member? */

@@ -332,11 +332,12 @@ static void seq_summary(int min_len, uint64_t before_n, uint64_t before, uint64_
     fprintf(stderr, "reads >= %d: %lu\t%lu bases\t%.2f Gbases\n", min_len, (unsigned long)after_n, (unsigned long)after, after / 1e9);
 }
 
-/* `seq --bam FILE [--duplex]` (an extension; include/cornetto_accel.h states the rules): a basecaller's BAM to the text `seq` prints */
-static int seq_bam(const char *bam, int min_len, int duplex)
+/* `seq --bam FILE [--duplex] [--bgzf]` (an extension; include/cornetto_accel.h states the rules): a basecaller's BAM to the text `seq` prints */
+static int seq_bam(const char *bam, int min_len, int duplex, int bgzf)
 {
     uint64_t stats[4] = {0, 0, 0, 0};
     int64_t n_done = 0;
+    if (bgzf) cli_bgzf_out_begin();      /* both readers write members from here on; a malformed file exits without the end-of-file block */
     if (!cli_host_mode()) {
         cornetto_accel_t *h = cli_accel_open();
         const int rest = cli_bam_fastq(h, bam, min_len, duplex, stats, &n_done);
@@ -345,6 +346,7 @@ static int seq_bam(const char *bam, int min_len, int duplex)
     } else {
         cli_host_bam_fastq(bam, min_len, duplex, 0, stats);
     }
+    if (bgzf) cli_bgzf_out_end();
     seq_summary(min_len, stats[0], stats[1], stats[2], stats[3]);
     return 0;
 }
@@ -352,10 +354,11 @@ static int seq_bam(const char *bam, int min_len, int duplex)
 int seq_main(int argc, char *argv[])
 {
     static const struct option lo[] = {{"verbose", required_argument, 0, 'v'}, {"min-len", required_argument, 0, 'm'}, {"help", no_argument, 0, 'h'},
-                                       {"bam", required_argument, 0, 0}, {"duplex", no_argument, 0, 0}, {"accel", required_argument, 0, 0}, {0, 0, 0, 0}};
+                                       {"bam", required_argument, 0, 0}, {"duplex", no_argument, 0, 0}, {"accel", required_argument, 0, 0}, {"bgzf", no_argument, 0, 0},
+                                       {0, 0, 0, 0}};
     FILE *fp_help = stderr;
     int min_len = 30000; /* src/seq.c:63 */
-    int c, li = 0, duplex = 0;
+    int c, li = 0, duplex = 0, bgzf = 0;
     const char *bam = NULL;
     optind = 1;
     while ((c = getopt_long(argc, argv, "hm:", lo, &li)) >= 0) {
@@ -371,6 +374,8 @@ int seq_main(int argc, char *argv[])
             bam = optarg;
         } else if (c == 0 && li == 4) {
             duplex = 1;
+        } else if (c == 0 && li == 6) {
+            bgzf = 1;
         } else if (c == 0 && li == 5) {
             if (strcmp(optarg, "no") == 0 || strcmp(optarg, "n") == 0) {
                 cli_host_set(1);
@@ -392,15 +397,20 @@ int seq_main(int argc, char *argv[])
         CLI_ERROR("%s", "--duplex: only with --bam (the dx tag is a field of a BAM record)");
         exit(EXIT_FAILURE);
     }
+    if (fp_help != stdout && bgzf && !bam) {
+        CLI_ERROR("%s", "--bgzf: only with --bam (the text of a FASTQ file is printed as it is)");
+        exit(EXIT_FAILURE);
+    }
     if ((!bam && argc - optind != 1) || fp_help == stdout) {
         fprintf(fp_help, "Usage: cornetto seq <reads.fastq> \n");
         fprintf(fp_help, "   -m INT                     min length [%d]\n", 30000);
         fprintf(fp_help, "   -h                         help\n");
         fprintf(fp_help, "   --bam FILE                 (extension) the reads of a basecaller's BAM in place of <reads.fastq>, decoded on the device\n");
         fprintf(fp_help, "   --duplex                   (extension) with --bam: only the reads with the tag dx:i:1\n");
+        fprintf(fp_help, "   --bgzf                     (not in the reference) with --bam: the text leaves as BGZF, deflated on the device (as bgzip writes it)\n");
         exit(fp_help == stdout ? EXIT_SUCCESS : EXIT_FAILURE);
     }
-    if (bam) return seq_bam(bam, min_len, duplex);
+    if (bam) return seq_bam(bam, min_len, duplex, bgzf);
     cli_fastx_t *fx = cli_fastx_open(argv[optind], 1);
     cli_rec_t *r;
     uint64_t before = 0, after = 0, before_n = 0, after_n = 0;

@@ -677,6 +677,7 @@ void cli_bam_fail(const char *path, int kind, long long record, int a, int b)
     } else {
         CLI_ERROR("%s: not a BAM file", path);
     }
+    cli_bgzf_out_flush();      /* (`seq --bam --bgzf`: the text of the records in front as a member; no end-of-file block) */
     exit(EXIT_FAILURE);
 }
 
@@ -1010,7 +1011,8 @@ void cli_host_bam_fastq(const char *path, int min_len, int duplex, int64_t skip_
             *o++ = no_qual ? '"' : (char)((q > 93 ? 93 : q) + 33);
         }
         *o++ = '\n';
-        fwrite(line, 1, need, stdout);
+        if (cli_bgzf_out_active()) cli_bgzf_out_text(line, need);
+        else fwrite(line, 1, need, stdout);
     }
     gzclose(f);
     free(buf);

@@ -12,10 +12,14 @@
 //                 (uniform); per chunk a search inside that short range, then cnq_chunk(): 16 bases from 9 source bytes through the nibble
 //                 table held in two 64-bit registers, 16 qualities with a SWAR clamp and add, both mirrored for a reverse-strand record, and
 //                 every other chunk (header, newlines, a record border, the end of the range) byte by byte into the same two registers.
+// or, for cornetto_bamfq_get_bgzf(), behind bamfq_text on the slab
+//   bgzf_deflate / bgzf_scan / bgzf_pack   (deflate.hip) the slab's text as BGZF members, packed: only those cross the bus.
 // Sizes are 32-bit: a window is at most 2^31 bytes, a record of b bytes prints at most 4 b / 3, so the text of a window is below 2^32.
 #include "bamfq.hpp"
 #include "bamwin.hpp"
 #include "common.hpp"
+#include "deflate.hpp"
+#include "internal.hpp"
 #include "scan.hpp"
 
 namespace {
@@ -136,6 +140,14 @@ struct cornetto_bamfq {
     bool tk_on[4] = {false, false, false, false};
     float text_ms = 0.f;                                       // bamfq_text in all: handed to cornetto_accel_last_timing() by the finish
     int64_t text_n = 0;
+    // cornetto_bamfq_get_bgzf(): the slot's packed members on the device, their length (a device word and its pinned copy), where they go
+    uint8_t *zpack[4] = {nullptr, nullptr, nullptr, nullptr};
+    int64_t zpack_cap[4] = {0, 0, 0, 0};
+    unsigned long long *d_ztot = nullptr, *p_ztot = nullptr;   // [4]
+    hipEvent_t zev[4][2] = {};                                 // the slot's text is written / its members are packed (the handle's stream deflates)
+    char *zdst[4] = {nullptr, nullptr, nullptr, nullptr};
+    int64_t zdst_cap[4] = {0, 0, 0, 0};
+    bool zpend[4] = {false, false, false, false};
 };
 
 namespace {
@@ -284,7 +296,12 @@ void cornetto_bamfq_close(cornetto_accel_t *h, cornetto_bamfq_t *b)
         if (b->tk[i][0]) (void)hipEventDestroy(b->tk[i][0]);
         if (b->tk[i][1]) (void)hipEventDestroy(b->tk[i][1]);
         if (b->slab[i]) (void)hipFree(b->slab[i]);
+        if (b->zpack[i]) (void)hipFree(b->zpack[i]);
+        if (b->zev[i][0]) (void)hipEventDestroy(b->zev[i][0]);
+        if (b->zev[i][1]) (void)hipEventDestroy(b->zev[i][1]);
     }
+    if (b->d_ztot) (void)hipFree(b->d_ztot);
+    if (b->p_ztot) (void)hipHostFree(b->p_ztot);
     cnbw::win_close(h, b->w);
     void *blocks[] = {b->d_size, b->d_out, b->d_recs};
     for (void *p : blocks)
@@ -390,11 +407,9 @@ int cornetto_bamfq_finish(cornetto_accel_t *h, cornetto_bamfq_t *b)
     return CORNETTO_OK;
 }
 
-int cornetto_bamfq_get(cornetto_accel_t *h, cornetto_bamfq_t *b, char *dst_pinned, int64_t at, int64_t n, int slot)
+// bytes [at, at + n) of the window's text into the slot's device slab: bamfq_text queued on the slot's queue
+static int fq_text_queue(cornetto_accel_t *h, cornetto_bamfq_t *b, int64_t at, int64_t n, int slot)
 {
-    if (!h || !b || at < 0 || n < 0 || at > b->text_cur - n || slot < 0 || slot > 3 || (n > 0 && !dst_pinned)) return cn_fail(h, CORNETTO_E_ARG, "bamfq_get: bad argument");
-    if (n == 0) return CORNETTO_OK;
-    CN_HIP(h, hipSetDevice(h->device));
     hipStream_t q = b->q[slot];
     const int64_t need = cn_align_up(n, 16);
     if (b->slab_cap[slot] < need) {              // (the slot's last copy out of the old slab must be through first)
@@ -424,8 +439,81 @@ int cornetto_bamfq_get(cornetto_accel_t *h, cornetto_bamfq_t *b, char *dst_pinne
         CN_HIP(h, hipEventRecord(b->tk[slot][1], q));
         b->tk_on[slot] = true;
     }
-    CN_HIP(h, hipMemcpyAsync(dst_pinned, b->slab[slot], (size_t)n, hipMemcpyDeviceToHost, q));
+    return CORNETTO_OK;
+}
+
+int cornetto_bamfq_get(cornetto_accel_t *h, cornetto_bamfq_t *b, char *dst_pinned, int64_t at, int64_t n, int slot)
+{
+    if (!h || !b || at < 0 || n < 0 || at > b->text_cur - n || slot < 0 || slot > 3 || (n > 0 && !dst_pinned)) return cn_fail(h, CORNETTO_E_ARG, "bamfq_get: bad argument");
+    if (n == 0) return CORNETTO_OK;
+    CN_HIP(h, hipSetDevice(h->device));
+    CN_TRY(fq_text_queue(h, b, at, n, slot));
+    CN_HIP(h, hipMemcpyAsync(dst_pinned, b->slab[slot], (size_t)n, hipMemcpyDeviceToHost, b->q[slot]));
+    CN_HIP(h, hipEventRecord(b->ev[slot], b->q[slot]));
+    return CORNETTO_OK;
+}
+
+int cornetto_bamfq_get_bgzf(cornetto_accel_t *h, cornetto_bamfq_t *b, char *dst_pinned, int64_t dst_cap, int64_t at, int64_t n, int slot)
+{
+    if (!h || !b || at < 0 || n < 0 || at > b->text_cur - n || slot < 0 || slot > 3 || dst_cap < 0 || (n > 0 && !dst_pinned))
+        return cn_fail(h, CORNETTO_E_ARG, "bamfq_get_bgzf: bad argument");
+    const int64_t n_mem = (n + CND_MEMBER - 1) / CND_MEMBER, need = n_mem * CND_STRIDE;
+    if (need > dst_cap) return cn_fail(h, CORNETTO_E_ARG, "bamfq_get_bgzf: %lld members want room for %lld bytes, the buffer has %lld", (long long)n_mem, (long long)need, (long long)dst_cap);
+    if (n == 0) {
+        b->zpend[slot] = false;
+        return CORNETTO_OK;
+    }
+    CN_HIP(h, hipSetDevice(h->device));
+    hipStream_t q = b->q[slot];
+    if (!b->d_ztot) {
+        if (hipMalloc((void **)&b->d_ztot, 4 * 8) != hipSuccess || hipHostMalloc((void **)&b->p_ztot, 4 * 8, hipHostMallocDefault) != hipSuccess)
+            return cn_fail(h, CORNETTO_E_NOMEM, "bamfq_get_bgzf: allocation of the length words failed");
+    }
+    for (int k = 0; k < 2; ++k)
+        if (!b->zev[slot][k]) CN_HIP(h, hipEventCreateWithFlags(&b->zev[slot][k], hipEventDisableTiming));
+    if (b->zpack_cap[slot] < need) {             // (the slot's last copy out of the old block must be through first)
+        CN_HIP(h, hipStreamSynchronize(q));
+        if (b->zpack[slot]) (void)hipFree(b->zpack[slot]);
+        b->zpack[slot] = nullptr;
+        b->zpack_cap[slot] = 0;
+        if (hipMalloc((void **)&b->zpack[slot], (size_t)need) != hipSuccess) {
+            b->zpack[slot] = nullptr;
+            return cn_fail(h, CORNETTO_E_NOMEM, "bamfq_get_bgzf: device block of %lld bytes", (long long)need);
+        }
+        b->zpack_cap[slot] = need;
+    }
+    CN_TRY(fq_text_queue(h, b, at, n, slot));
+    // the handle's stream deflates behind the slot's text kernel; the slot's queue goes on behind the packed members and their length
+    CN_HIP(h, hipEventRecord(b->zev[slot][0], q));
+    CN_HIP(h, hipStreamWaitEvent(h->stream, b->zev[slot][0], 0));
+    CN_TRY(cn_bgzf_deflate_queue(h, b->slab[slot], n, b->zpack[slot], b->d_ztot + slot));
+    CN_HIP(h, hipMemcpyAsync(b->p_ztot + slot, b->d_ztot + slot, 8, hipMemcpyDeviceToHost, h->stream));
+    CN_HIP(h, hipEventRecord(b->zev[slot][1], h->stream));
+    CN_HIP(h, hipStreamWaitEvent(q, b->zev[slot][1], 0));
     CN_HIP(h, hipEventRecord(b->ev[slot], q));
+    b->zdst[slot] = dst_pinned;
+    b->zdst_cap[slot] = dst_cap;
+    b->zpend[slot] = true;
+    return CORNETTO_OK;
+}
+
+int cornetto_bamfq_wait_bgzf(cornetto_accel_t *h, cornetto_bamfq_t *b, int slot, int64_t *n_bytes)
+{
+    if (!h || !b || slot < 0 || slot > 3 || !n_bytes) return cn_fail(h, CORNETTO_E_ARG, "bamfq_wait_bgzf: bad argument");
+    *n_bytes = 0;
+    CN_HIP(h, hipSetDevice(h->device));
+    CN_HIP(h, hipEventSynchronize(b->ev[slot]));
+    fq_timed(b, slot);
+    if (!b->zpend[slot]) return CORNETTO_OK;
+    b->zpend[slot] = false;
+    const unsigned long long total = b->p_ztot[slot];
+    if (total > (unsigned long long)b->zdst_cap[slot] || total > (unsigned long long)b->zpack_cap[slot])
+        return cn_fail(h, CORNETTO_E_HIP, "bamfq_wait_bgzf: %llu bytes of members for a buffer of %lld", total, (long long)b->zdst_cap[slot]);
+    if (total) {
+        CN_HIP(h, hipMemcpyAsync(b->zdst[slot], b->zpack[slot], (size_t)total, hipMemcpyDeviceToHost, b->q[slot]));
+        CN_HIP(h, hipStreamSynchronize(b->q[slot]));
+    }
+    *n_bytes = (int64_t)total;
     return CORNETTO_OK;
 }
 

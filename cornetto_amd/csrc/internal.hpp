@@ -63,5 +63,9 @@ void cn_sdust_drop_pending(cornetto_accel_t *h);
 // cornetto_text_inflate() over raw device pointers, without its checks and its timing bracket (inflate.hip): the bedgraph feeds inflate into
 // their own text workspaces with it.  Every block must lie inside both buffers.  Synchronises the handle's stream.
 int cn_bgzf_inflate_raw(cornetto_accel_t *h, const uint8_t *d_comp, uint8_t *d_out, const cornetto_bgzf_block_t *blocks, int64_t n_blocks, int64_t *first_bad);
+// cornetto_text_deflate() over raw device pointers (deflate.hip): the BGZF members of d_src[0 .. n), cut every 65280 bytes, packed back to back from
+// d_out on (room for 65536 bytes a member), the chain's length to the device word *d_total.  Queued on the handle's stream: nothing is waited for,
+// staging and sizes live in the handle's workspaces (calls follow each other on that stream).
+int cn_bgzf_deflate_queue(cornetto_accel_t *h, const uint8_t *d_src, int64_t n, uint8_t *d_out, unsigned long long *d_total);
 int cn_sdust_list_impl(cornetto_accel_t *h, const cornetto_asm_t *a, int32_t T, int32_t W, const cornetto_ivl_t **d_ivls, int64_t *n_ivls);
 int cn_telo_hits_impl(cornetto_accel_t *h, const cornetto_asm_t *a, const char *motif, const cornetto_hit_t **d_hits, int64_t *n_hits);

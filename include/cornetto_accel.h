@@ -559,6 +559,16 @@ int cornetto_text_inflate(cornetto_accel_t *h, cornetto_text_t *comp, cornetto_t
  * (one copy; host memory of sum(len) bytes): how the record names of an inflated text reach the host. */
 int cornetto_text_gather(cornetto_accel_t *h, cornetto_text_t *t, const int64_t *at, const int32_t *len, int64_t n, char *dst);
 
+/* The other direction: bytes [at, at + n) of the device text `text` as BGZF members in the device text `out` from out_at on, back to back.
+ * The bytes are cut every 65280 (0xff00, what bgzip uses; the last member is shorter, n == 0 makes no member) and a wave makes a member
+ * (bgzf_deflate): one dynamic-Huffman block whose only matches are byte runs (a run of one value of 4 or more bytes is its first byte and
+ * distance-1 matches), or one stored block where that would not be smaller, so a member has at most 65280 + 5 + 26 = 65311 bytes; header
+ * with `BC`/BSIZE, CRC-32 and ISIZE as bgzip writes them.  The members' sizes are scanned (bgzf_scan) and the members packed (bgzf_pack).
+ * No end-of-file block is written.  `out` must have room for ceil(n / 65280) * 65536 bytes behind out_at: CORNETTO_E_ARG otherwise, and
+ * nothing runs.  Waits for the puts of `text`.  *n_out: bytes of the chain, *n_members: its members.  The bytes depend on the text alone. */
+int cornetto_text_deflate(cornetto_accel_t *h, cornetto_text_t *text, int64_t at, int64_t n, cornetto_text_t *out, int64_t out_at, int64_t *n_out,
+                          int64_t *n_members);
+
 /* Bedgraph text from a bgzip-compressed depth file (mosdepth writes *.per-base.bed.gz only): the next bytes of one file for the two bedgraph
  * readers, either plain bytes in host memory or the next BGZF blocks of the file, whose deflate streams are on the device.  The feed gives a
  * compressed source's blocks their places behind the bytes it carries over from the last feed IN THE READER'S OWN TEXT WORKSPACE, inflates
@@ -711,6 +721,12 @@ int cornetto_bamfq_feed(cornetto_accel_t *h, cornetto_bamfq_t *b, cornetto_text_
  * (the feed waits for all four slots). */
 int cornetto_bamfq_get(cornetto_accel_t *h, cornetto_bamfq_t *b, char *dst_pinned, int64_t at, int64_t n, int slot);
 int cornetto_bamfq_wait(cornetto_accel_t *h, cornetto_bamfq_t *b, int slot);
+/* The same range of the window's text as BGZF members (`seq --bam --bgzf`): the slab bamfq_text writes is deflated on the device under the
+ * rules of cornetto_text_deflate() and only the packed members reach `dst_pinned`, which must have dst_cap >= ceil(n / 65280) * 65536 bytes
+ * (CORNETTO_E_ARG otherwise, nothing runs).  The same four slots; a slot carries one get of either kind at a time.
+ * cornetto_bamfq_wait_bgzf(): the members of the slot's last such get are in its buffer, *n_bytes of them (0 after a get of no bytes). */
+int cornetto_bamfq_get_bgzf(cornetto_accel_t *h, cornetto_bamfq_t *b, char *dst_pinned, int64_t dst_cap, int64_t at, int64_t n, int slot);
+int cornetto_bamfq_wait_bgzf(cornetto_accel_t *h, cornetto_bamfq_t *b, int slot, int64_t *n_bytes);
 /* After the last feed: a file that ends inside a record is kind 2. */
 int cornetto_bamfq_finish(cornetto_accel_t *h, cornetto_bamfq_t *b);
 /* stats[0 .. 5): reads and bases of `total reads`, reads and bases of `reads >= min_len`, then the records taken (the passed-over ones
