@@ -103,16 +103,28 @@ _ORDER = [16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15]
 
 def walk(payload):
     """-> dict: kinds (list of 'stored' / 'fixed' / 'dynamic', one per deflate block), max_code_len, code16 (the repeat code 16 was used),
-    max_len, max_dist, overlaps (matches with distance below length), matches, out (bytes produced)"""
+    max_len, max_dist, overlaps (matches with distance below length), matches, out (bytes produced); and what tells hand-assembled streams
+    (tests/deflate_asm.py) apart: dist_code_lens / len_code_lens (the code lengths of the distance codes and length symbols that matches
+    USED), len_syms / dist_syms (the symbols they used), max_token_bits (the most bits of one length + distance token, extra bits included),
+    run_over_hlit (the repeat codes whose run began in the literal/length lengths and ended in the distance lengths), hlit / hdist / hclen
+    and n_dist_codes / n_lit_codes (per dynamic block; the last two count the non-zero lengths), empty_stored (the bit offsets, modulo 8,
+    of the headers of stored blocks of no bytes), stored / stored_at (the sizes of the stored blocks and the offsets of their bytes), end (the bit the stream ends behind)"""
     b = _Bits(payload)
-    st = {"kinds": [], "max_code_len": 0, "code16": False, "max_len": 0, "max_dist": 0, "overlaps": 0, "matches": 0, "out": 0}
+    st = {"kinds": [], "max_code_len": 0, "code16": False, "max_len": 0, "max_dist": 0, "overlaps": 0, "matches": 0, "out": 0,
+          "dist_code_lens": set(), "len_code_lens": set(), "len_syms": set(), "dist_syms": set(), "max_token_bits": 0, "run_over_hlit": set(),
+          "hlit": [], "hdist": [], "hclen": [], "n_dist_codes": [], "n_lit_codes": [], "empty_stored": [], "stored": [], "stored_at": []}
     last = 0
     while not last:
+        head = b.pos
         last, kind = b.take(1), b.take(2)
         if kind == 0:
             b.pos = (b.pos + 7) & ~7
             n = b.take(16)
             assert b.take(16) == n ^ 0xFFFF
+            st["stored"].append(n)
+            st["stored_at"].append(b.pos >> 3)
+            if n == 0:
+                st["empty_stored"].append(head & 7)
             b.pos += 8 * n
             st["out"] += n
             st["kinds"].append("stored")
@@ -129,6 +141,7 @@ def walk(payload):
                 cl[_ORDER[i]] = b.take(3)
             ct, lens = _codes(cl), []
             while len(lens) < hlit + hdist:
+                before = len(lens)
                 s = _sym(b, ct)
                 if s < 16:
                     lens.append(s)
@@ -139,8 +152,12 @@ def walk(payload):
                     lens += [0] * (3 + b.take(3))
                 else:
                     lens += [0] * (11 + b.take(7))
+                if before < hlit < len(lens):
+                    st["run_over_hlit"].add(s)
             assert len(lens) == hlit + hdist
             ll, dl = lens[:hlit], lens[hlit:]
+            for key, v in (("hlit", hlit), ("hdist", hdist), ("hclen", hclen), ("n_lit_codes", sum(x > 0 for x in ll)), ("n_dist_codes", sum(x > 0 for x in dl))):
+                st[key].append(v)
             st["max_code_len"] = max(st["max_code_len"], max(lens))
             st["kinds"].append("dynamic")
         lt, dt = _codes(ll), _codes(dl)
@@ -152,13 +169,19 @@ def walk(payload):
                 break
             else:
                 n = _LBASE[s - 257] + b.take(_LEXT[s - 257])
-                d = _sym(b, dt)
-                d = _DBASE[d] + b.take(_DEXT[d])
+                ds = _sym(b, dt)
+                d = _DBASE[ds] + b.take(_DEXT[ds])
+                st["len_syms"].add(s)
+                st["dist_syms"].add(ds)
+                st["len_code_lens"].add(ll[s])
+                st["dist_code_lens"].add(dl[ds])
+                st["max_token_bits"] = max(st["max_token_bits"], ll[s] + _LEXT[s - 257] + dl[ds] + _DEXT[ds])
                 st["matches"] += 1
                 st["max_len"] = max(st["max_len"], n)
                 st["max_dist"] = max(st["max_dist"], d)
                 st["overlaps"] += d < n
                 st["out"] += n
+    st["end"] = b.pos
     return st
 
 

@@ -2,12 +2,13 @@
 // The same statements as in bgzf_inflate / bgzf_crc32 with the 64 lanes run one after the other; input and output live in heap blocks
 // of exactly n_src and n_dst bytes, so that the host sanitizers see every byte read or written outside them:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined tools/sim/inflate_sim.cc -lz -o inflate_sim
-//   inflate_sim [--mut N] [--seed S] file.gz ...
+//   inflate_sim [--mut N] [--seed S] [--status] file.gz ...
 // For every BGZF member of every file: the member as it is, N seeded single-bit and single-byte changes of its deflate stream, the
 // stream cut short (n_src smaller by 1, 2, 3, 4, 8, to a half, to nothing) and n_dst one lower and one higher.  The rule of every trial:
 // where zlib's raw inflate ends the stream with exactly n_dst bytes whose CRC-32 is the footer's, the decoder returns the same bytes and
 // the CRC agrees; in every other case the decoder reports the block bad.  The chain walk is run over every file cut into two pieces at
-// seeded offsets.  Exit 0 and no sanitizer report: the argument for the bounds of the kernels.
+// seeded offsets.  Exit 0 and no sanitizer report: the argument for the bounds of the kernels.  --status: one line `status <file> <member> <code>`
+// for every member's as-it-is trial, the CNI_* code the decoder and the CRC check gave it (the tests pin the reason of every bad stream).
 #include <stdio.h>
 #include <stdlib.h>
 #include <zlib.h>
@@ -37,8 +38,8 @@ static uint32_t rnd()
 
 static long g_trials, g_good, g_fail;
 
-// one trial -> 0 when the rule holds
-static int trial(const uint8_t *payload, int32_t n_src, int32_t n_dst, uint32_t crc, const char *what)
+// one trial -> 0 when the rule holds; *status: the CNI_* code of the trial
+static int trial(const uint8_t *payload, int32_t n_src, int32_t n_dst, uint32_t crc, const char *what, int *status = nullptr)
 {
     uint8_t *src = (uint8_t *)malloc(n_src > 0 ? (size_t)n_src : 1);     // exact sizes: the sanitizer's red zones begin at the last byte
     if (n_src > 0) memcpy(src, payload, (size_t)n_src);
@@ -55,6 +56,7 @@ static int trial(const uint8_t *payload, int32_t n_src, int32_t n_dst, uint32_t 
         }
         if (got_crc != crc) st = CNI_BAD_CRC;
     }
+    if (status) *status = st;
     // zlib's raw inflate on the same bytes, with room for one byte more than n_dst
     std::vector<uint8_t> ref((size_t)n_dst + 1);
     z_stream z;
@@ -87,14 +89,16 @@ static int trial(const uint8_t *payload, int32_t n_src, int32_t n_dst, uint32_t 
 int main(int argc, char **argv)
 {
     long n_mut = 200;
+    bool print_status = false;
     std::vector<const char *> files;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--mut") && i + 1 < argc) n_mut = atol(argv[++i]);
         else if (!strcmp(argv[i], "--seed") && i + 1 < argc) g_rng = strtoull(argv[++i], NULL, 10) * 2 + 1;
+        else if (!strcmp(argv[i], "--status")) print_status = true;
         else files.push_back(argv[i]);
     }
     if (files.empty()) {
-        fprintf(stderr, "usage: inflate_sim [--mut N] [--seed S] file.gz ...\n");
+        fprintf(stderr, "usage: inflate_sim [--mut N] [--seed S] [--status] file.gz ...\n");
         return 2;
     }
     long n_members = 0;
@@ -144,7 +148,10 @@ int main(int argc, char **argv)
             const uint8_t *p = exact + B.src;
             char what[512];
             snprintf(what, sizeof(what), "%s member %lld as it is", path, (long long)i);
-            if (trial(p, B.n_src, B.n_dst, B.crc, what)) continue;
+            int st = -1;
+            const int failed = trial(p, B.n_src, B.n_dst, B.crc, what, &st);
+            if (print_status) printf("status %s %lld %d\n", path, (long long)i, st);
+            if (failed) continue;
             static const int cuts[] = {1, 2, 3, 4, 8};
             for (int c : cuts)
                 if (B.n_src >= c) {
