@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-__all__ = ["lib", "Accel", "bgzf_scan", "bam_header", "BGZF_DT", "BAMREC_DT", "BAMFQREC_DT", "BAM_SCAN_TILE", "BamFormatError", "AccelError", "HIT_DT", "WIN_DT", "IVL_DT", "TELROW_DT", "HAP_ROW_DT", "khash_str_order", "panel_boring", "REG_DT", "REGREC_DT", "build",
+__all__ = ["lib", "Accel", "bgzf_scan", "bam_header", "BGZF_DT", "BAMREC_DT", "BAMFQREC_DT", "BAM_SCAN_TILE", "FQSEQ_TILE", "FQREC_DT", "Bgzf", "FastqBlockError", "BamFormatError", "AccelError", "HIT_DT", "WIN_DT", "IVL_DT", "TELROW_DT", "HAP_ROW_DT", "khash_str_order", "panel_boring", "REG_DT", "REGREC_DT", "build",
            "LIB_PATH", "CLI_PATH"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -83,6 +83,12 @@ class BamFqOpt(C.Structure):
     _fields_ = [("min_len", C.c_int32), ("duplex", C.c_int32), ("window", C.c_int64), ("n_ref", C.c_int32), ("records", C.c_int32)]
 
 
+class FqSeqOpt(C.Structure):
+    """cornetto_fqseq_opt_t (include/cornetto_accel.h)"""
+    _fields_ = [("min_len", C.c_int32), ("records", C.c_int32), ("window", C.c_int64)]
+
+
+FQSEQ_TILE = 16384  # CORNETTO_FQSEQ_TILE: output bytes per workgroup of fqseq_text (checked against the library when it is loaded)
 BAMFQREC_DT = np.dtype([("offset", "<i8"), ("l_seq", "<i4"), ("flag", "<i4"), ("name_len", "<i4"), ("kept", "<i4")])
 BAMREC_DT = np.dtype([("offset", "<i8"), ("ref_id", "<i4"), ("pos", "<i4"), ("mapq", "<i4"), ("flag", "<i4"), ("counted", "<i4"), ("n_ops", "<i4"), ("span", "<i8"),
                       ("bases", "<i8")])
@@ -119,6 +125,15 @@ class BamFormatError(ValueError):
     def __init__(self, kind, record, a, b):
         super().__init__("BAM check %d failed at record %d (%d, %d)" % (kind, record, a, b))
         self.kind, self.record, self.a, self.b = kind, record, a, b
+
+
+class FastqBlockError(ValueError):
+    """a BGZF block of the FASTQ file handed to Accel.fastq_seq() is not what its footer says: block = its index in the file; text, stats,
+    records and rest cover the records that lie wholly in front of it; refeed = the status of one more feed (refused)"""
+
+    def __init__(self, block):
+        super().__init__("BGZF block %d is not what its footer says" % block)
+        self.block = block
 
 
 class AccelError(RuntimeError):
@@ -262,6 +277,20 @@ def lib(dev=False):
         "cornetto_bamfq_stats": (None, [vp, C.POINTER(i64)]),
         "cornetto_bamfq_error": (C.POINTER(BamErr), [vp]),
         "cornetto_bamfq_records": (C.c_int, [vp, vp, pp, C.POINTER(i64)]),
+        "cornetto_fqseq_tile": (i32, []),
+        "cornetto_fqseq_defaults": (None, [C.POINTER(FqSeqOpt)]),
+        "cornetto_fqseq_open": (C.c_int, [vp, C.POINTER(FqSeqOpt), pp]),
+        "cornetto_fqseq_close": (None, [vp, vp]),
+        "cornetto_fqseq_feed": (C.c_int, [vp, vp, C.POINTER(BgSrc), C.c_int, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]),
+        "cornetto_fqseq_rest": (i64, [vp]),
+        "cornetto_fqseq_error": (i64, [vp]),
+        "cornetto_fqseq_get": (C.c_int, [vp, vp, vp, i64, i64, C.c_int]),
+        "cornetto_fqseq_wait": (C.c_int, [vp, vp, C.c_int]),
+        "cornetto_fqseq_get_bgzf": (C.c_int, [vp, vp, vp, i64, i64, i64, C.c_int]),
+        "cornetto_fqseq_wait_bgzf": (C.c_int, [vp, vp, C.c_int, C.POINTER(i64)]),
+        "cornetto_fqseq_stats": (None, [vp, C.POINTER(i64)]),
+        "cornetto_fqseq_records": (C.c_int, [vp, vp, pp, C.POINTER(i64)]),
+        "cornetto_fqseq_text_time": (C.c_int, [vp, vp, C.POINTER(C.c_double), C.POINTER(i64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError if the library does not export a declared symbol
@@ -269,6 +298,7 @@ def lib(dev=False):
         fn.argtypes = args
     assert L.cornetto_bgrun_tile() == BGRUN_TILE
     assert L.cornetto_bam_scan_tile() == BAM_SCAN_TILE
+    assert L.cornetto_fqseq_tile() == FQSEQ_TILE
     L._declared = sorted(sig)
     _libs[path] = L
     return L
@@ -1075,6 +1105,135 @@ class Accel:
             if fq is not None and fq.value:
                 L.cornetto_bamfq_close(self.h, fq)
             L.cornetto_text_free(self.h, comp)
+
+    def fastq_seq(self, data, min_len, window=None, slab=None, feeds=1, bgzf_in=False, bgzf_out=False):
+        """FASTQ text through the feed / get loop of cornetto_fqseq_*: what `seq -m min_len` prints -> (text, stats, recs, rest_offset, plain).
+        data: the text (bytes), or with bgzf_in the file as a BGZF blob (inflated on the device), or a list of parts of the stream, each
+        bytes or a Bgzf (the kind may change between feeds); the bytes / blocks of every part are handed over in `feeds` parts.  text: the
+        printed text — with bgzf_out the list of what every get returned (a chain of BGZF members each); stats = [reads, bases of `total
+        reads`, reads, bases of `reads >= min_len`]; recs: the record table (FQREC_DT, offsets into the stream); rest_offset: the offset
+        in the plain / inflated stream of the first byte the device did not consume; plain: False when the sequential reader has to go
+        on from there.  window: bytes of text on the device at once; slab: bytes per get (the whole text of a window by default), the gets
+        take turns on the four copy slots.  Neither changes a result.  Raises FastqBlockError for a damaged block; a record larger than the
+        window raises AccelError (status -4, .taken = 0).  Kernel times of the feeds: self.fq_timing; of fqseq_text: self.fq_text_time =
+        (ms, bytes written) when the handle times every launch."""
+        L = self.L
+        parts = data if isinstance(data, (list, tuple)) else [Bgzf(data) if bgzf_in else data]
+        fq = None
+        pins, cap = [None] * 4, [0] * 4
+        out, texts = [], []
+        self.fq_timing = []
+
+        def result():
+            st = (C.c_int64 * 5)()
+            L.cornetto_fqseq_stats(fq, st)
+            p, n = C.c_void_p(), C.c_int64()
+            self._chk(L.cornetto_fqseq_records(self.h, fq, C.byref(p), C.byref(n)))
+            ms, nb = C.c_double(), C.c_int64()
+            self._chk(L.cornetto_fqseq_text_time(self.h, fq, C.byref(ms), C.byref(nb)))
+            self.fq_text_time = (ms.value, nb.value)
+            return out if bgzf_out else b"".join(out), list(st)[:4], _take(L, p, n.value, FQREC_DT), int(L.cornetto_fqseq_rest(fq))
+
+        def pull(n_text):
+            pend, at, k = [0] * 4, 0, 0
+            while at < n_text or any(pend):
+                s = k & 3
+                k += 1
+                if pend[s]:
+                    if bgzf_out:
+                        nz = C.c_int64()
+                        self._chk(L.cornetto_fqseq_wait_bgzf(self.h, fq, s, C.byref(nz)))
+                        out.append(C.string_at(pins[s], nz.value))
+                    else:
+                        self._chk(L.cornetto_fqseq_wait(self.h, fq, s))
+                        out.append(C.string_at(pins[s], pend[s]))
+                    pend[s] = 0
+                if at < n_text:
+                    n = min(slab or n_text, n_text - at)
+                    need = (n + 65279) // 65280 * 65536 if bgzf_out else n
+                    if cap[s] < need:
+                        if pins[s]:
+                            L.cornetto_pinned_free(pins[s])
+                        pins[s] = L.cornetto_pinned_alloc(need)
+                        cap[s] = need
+                        if not pins[s]:
+                            raise MemoryError("cornetto_pinned_alloc(%d)" % need)
+                    if bgzf_out:
+                        self._chk(L.cornetto_fqseq_get_bgzf(self.h, fq, pins[s], cap[s], at, n, s))
+                    else:
+                        self._chk(L.cornetto_fqseq_get(self.h, fq, pins[s], at, n, s))
+                    pend[s] = n
+                    at += n
+
+        def sources():
+            """(BgSrc with what it points to, units in it, is it the stream's last) for every feed group"""
+            groups = []
+            for part in parts:
+                if isinstance(part, Bgzf):
+                    blocks, resume, broken = bgzf_scan(part.blob)
+                    if broken or resume != len(part.blob):
+                        raise ValueError("not a chain of BGZF members")
+                    comp = self._text_from(part.blob)
+                    texts.append(comp)
+                    cuts = [len(blocks) * i // feeds for i in range(feeds + 1)]
+                    groups += [("z", comp, np.ascontiguousarray(blocks[cuts[i]:cuts[i + 1]])) for i in range(feeds)]
+                else:
+                    t = bytes(part)
+                    cuts = [len(t) * i // feeds for i in range(feeds + 1)]
+                    groups += [("t", None, t[cuts[i]:cuts[i + 1]]) for i in range(feeds)]
+            return groups
+        try:
+            opt = FqSeqOpt()
+            L.cornetto_fqseq_defaults(C.byref(opt))
+            opt.min_len, opt.records = min_len, 1
+            if window is not None:
+                opt.window = window
+            fq = C.c_void_p()
+            self._chk(L.cornetto_fqseq_open(self.h, C.byref(opt), C.byref(fq)))
+            groups = sources()
+            plain = True
+            for gi, (kind, comp, body) in enumerate(groups):
+                last = gi == len(groups) - 1
+                at, n_all, first = 0, len(body), True
+                while plain and (at < n_all or (first and last)):
+                    first = False
+                    if kind == "z":
+                        keep = np.ascontiguousarray(body[at:])
+                        src = BgSrc(None, 0, comp, keep.ctypes.data if keep.size else None, keep.size)
+                    else:
+                        keep = body[at:]
+                        src = BgSrc(keep, len(keep), None, None, 0)
+                    taken, n_text, pl = C.c_int64(), C.c_int64(), C.c_int32()
+                    rc = L.cornetto_fqseq_feed(self.h, fq, C.byref(src), 1 if last else 0, C.byref(taken), C.byref(n_text), C.byref(pl))
+                    self.fq_timing += self.last_timing()
+                    if rc == -4:
+                        try:
+                            self._chk(rc)
+                        except AccelError as e:
+                            e.taken = taken.value
+                            raise
+                    if rc not in (0, -6):
+                        self._chk(rc)
+                    pull(n_text.value)
+                    if rc == -6:
+                        err = FastqBlockError(int(L.cornetto_fqseq_error(fq)))
+                        err.text, err.stats, err.records, err.rest = result()
+                        none = BgSrc(None, 0, None, None, 0)
+                        err.refeed = L.cornetto_fqseq_feed(self.h, fq, C.byref(none), 1, C.byref(taken), C.byref(n_text), C.byref(pl))
+                        raise err
+                    at += taken.value
+                    plain = bool(pl.value)
+                if not plain:
+                    break
+            return result() + (plain,)
+        finally:
+            for p in pins:
+                if p:
+                    L.cornetto_pinned_free(p)
+            if fq is not None and fq.value:
+                L.cornetto_fqseq_close(self.h, fq)
+            for t in texts:
+                L.cornetto_text_free(self.h, t)
 
     def bedgraph_runs_ingest(self, tot_pieces, mq_pieces, alternate=True):
         """stream two RUN-LENGTH bedgraphs (iterables of bytes pieces, any split points) through cornetto_bgrun_*; returns what

@@ -253,6 +253,14 @@ void cli_host_bam_fastq(const char *path, int min_len, int duplex, int64_t skip_
  * $CORNETTO_EMIT_SLAB bytes.  -> 0; non-zero when a record is larger than the window (a CLI_WARNING says so): *n_done records are printed and
  * counted in stats, the caller reads the rest on the host */
 int cli_bam_fastq(cornetto_accel_t *h, const char *path, int min_len, int duplex, uint64_t stats[4], int64_t *n_done);
+/* cli/fasta_cmds.c: the loop of `seq` over the records the sequential reader still has (src/seq.c:116-129): prints the kept ones — through
+ * cli_bgzf_out_text() between cli_bgzf_out_begin() and _end() — and adds to stats (reads and bases of both summary lines) */
+void cli_seq_records(cli_fastx_t *fx, int min_len, uint64_t stats[4]);
+/* cli/fqseq.c: `seq --fastq FILE` (not in the reference): the same text written on the device (cornetto_fqseq_*) from a FASTQ file that is plain,
+ * BGZF (inflated on the device) or another gzip; a window of $CORNETTO_FASTQ_WINDOW bytes at a time, its text pulled in slabs of
+ * $CORNETTO_EMIT_SLAB bytes.  Where the text stops being plain records, or a record is larger than the window (a CLI_WARNING says so), the
+ * sequential reader prints the rest.  stats: added to.  A BGZF file that is not one to its end: cli_bgz_fail(), the text in front printed */
+void cli_fastq_seq(cornetto_accel_t *h, const char *path, int min_len, uint64_t stats[4]);
 /* cli/bgzf_out.c: `seq --bam --bgzf` (an extension): between _begin() and _end() the text of both readers above leaves as a BGZF stream on stdout.
  * _text(): text, collected into members of 65280 bytes through zlib; _members(): members the device made (cornetto_bamfq_get_bgzf), behind the
  * pending text; _flush(): the pending text as a member — cli_bam_fail() calls it, so a malformed file leaves the members of the records in front

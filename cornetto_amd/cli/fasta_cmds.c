@@ -1,5 +1,6 @@
-/* fasta_cmds.c — the FASTA/FASTQ driven sub-commands: telofind, sdust (device scans), fa2bed, seq (host
- * only).  Reference: src/find_telomere.c:83-111, src/sdust/sdust.c:179-207, src/assbed.c:50-107,
+/* fasta_cmds.c — the FASTA/FASTQ driven sub-commands: telofind, sdust (device scans), fa2bed, seq (on the host with a positional
+ * file, as the reference; `seq --fastq` and `seq --bam` write the same text on the device: cli/fqseq.c, cli/bam.c).
+ * Reference: src/find_telomere.c:83-111, src/sdust/sdust.c:179-207, src/assbed.c:50-107,
  * src/seq.c:53-138.  One device: the records come from the streamer (cli/stream.c), one scan per batch, printed in
  * input order.  CORNETTO_DEVICES: the sequential reader's batches are dealt to the devices.  CORNETTO_ACCEL=no: the host path. */
 #include <getopt.h>
@@ -351,15 +352,66 @@ static int seq_bam(const char *bam, int min_len, int duplex, int bgzf)
     return 0;
 }
 
+void cli_seq_records(cli_fastx_t *fx, int min_len, uint64_t stats[4])
+{
+    const int bgzf = cli_bgzf_out_active();
+    cli_rec_t *r;
+    while ((r = cli_fastx_next(fx)) != NULL) {
+        const int64_t l = (int64_t)r->seq.l;
+        stats[1] += (uint64_t)l;
+        stats[0]++;
+        if (l < min_len) continue;
+        stats[3] += (uint64_t)l;
+        stats[2]++;
+        if (!bgzf) { /* src/seq.c:120-129: name, TAB, comment */
+            printf("@%s", r->name.s);
+            if (r->comment.l) printf("\t%s", r->comment.s);
+            printf("\n%s\n+\n%s\n", r->seq.s, r->qual.s);
+            continue;
+        }
+        /* the same bytes ("%s" ends at a byte 0) */
+        cli_bgzf_out_text("@", 1);
+        cli_bgzf_out_text(r->name.s, strlen(r->name.s));
+        if (r->comment.l) {
+            cli_bgzf_out_text("\t", 1);
+            cli_bgzf_out_text(r->comment.s, strlen(r->comment.s));
+        }
+        cli_bgzf_out_text("\n", 1);
+        cli_bgzf_out_text(r->seq.s, strlen(r->seq.s));
+        cli_bgzf_out_text("\n+\n", 3);
+        cli_bgzf_out_text(r->qual.s, strlen(r->qual.s));
+        cli_bgzf_out_text("\n", 1);
+    }
+}
+
+/* `seq --fastq FILE [--bgzf]` (not in the reference): the text `seq FILE` prints, written on the device; --accel=no: the host loop on FILE */
+static int seq_fastq(const char *fastq, int min_len, int bgzf)
+{
+    uint64_t stats[4] = {0, 0, 0, 0};
+    if (bgzf) cli_bgzf_out_begin();      /* a BGZF file that is not one to its end exits without the end-of-file block */
+    if (!cli_host_mode()) {
+        cornetto_accel_t *h = cli_accel_open();
+        cli_fastq_seq(h, fastq, min_len, stats);
+        cornetto_accel_close(h);
+    } else {
+        cli_fastx_t *fx = cli_fastx_open(fastq, 1);
+        cli_seq_records(fx, min_len, stats);
+        cli_fastx_close(fx);
+    }
+    if (bgzf) cli_bgzf_out_end();
+    seq_summary(min_len, stats[0], stats[1], stats[2], stats[3]);
+    return 0;
+}
+
 int seq_main(int argc, char *argv[])
 {
     static const struct option lo[] = {{"verbose", required_argument, 0, 'v'}, {"min-len", required_argument, 0, 'm'}, {"help", no_argument, 0, 'h'},
                                        {"bam", required_argument, 0, 0}, {"duplex", no_argument, 0, 0}, {"accel", required_argument, 0, 0}, {"bgzf", no_argument, 0, 0},
-                                       {0, 0, 0, 0}};
+                                       {"fastq", required_argument, 0, 0}, {0, 0, 0, 0}};
     FILE *fp_help = stderr;
     int min_len = 30000; /* src/seq.c:63 */
     int c, li = 0, duplex = 0, bgzf = 0;
-    const char *bam = NULL;
+    const char *bam = NULL, *fastq = NULL;
     optind = 1;
     while ((c = getopt_long(argc, argv, "hm:", lo, &li)) >= 0) {
         if (c == 'h') {
@@ -376,6 +428,8 @@ int seq_main(int argc, char *argv[])
             duplex = 1;
         } else if (c == 0 && li == 6) {
             bgzf = 1;
+        } else if (c == 0 && li == 7) {
+            fastq = optarg;
         } else if (c == 0 && li == 5) {
             if (strcmp(optarg, "no") == 0 || strcmp(optarg, "n") == 0) {
                 cli_host_set(1);
@@ -393,40 +447,38 @@ int seq_main(int argc, char *argv[])
         CLI_ERROR("%s", "--bam takes the place of the FASTQ file: no positional file with it");
         exit(EXIT_FAILURE);
     }
+    if (fp_help != stdout && fastq && bam) {
+        CLI_ERROR("%s", "--fastq and --bam each take the place of the FASTQ file: one of them");
+        exit(EXIT_FAILURE);
+    }
+    if (fp_help != stdout && fastq && argc - optind != 0) {
+        CLI_ERROR("%s", "--fastq takes the place of the FASTQ file: no positional file with it");
+        exit(EXIT_FAILURE);
+    }
     if (fp_help != stdout && duplex && !bam) {
         CLI_ERROR("%s", "--duplex: only with --bam (the dx tag is a field of a BAM record)");
         exit(EXIT_FAILURE);
     }
-    if (fp_help != stdout && bgzf && !bam) {
-        CLI_ERROR("%s", "--bgzf: only with --bam (the text of a FASTQ file is printed as it is)");
+    if (fp_help != stdout && bgzf && !bam && !fastq) {
+        CLI_ERROR("%s", "--bgzf: only with --bam or --fastq (the text of a positional FASTQ file is printed as it is)");
         exit(EXIT_FAILURE);
     }
-    if ((!bam && argc - optind != 1) || fp_help == stdout) {
+    if ((!bam && !fastq && argc - optind != 1) || fp_help == stdout) {
         fprintf(fp_help, "Usage: cornetto seq <reads.fastq> \n");
         fprintf(fp_help, "   -m INT                     min length [%d]\n", 30000);
         fprintf(fp_help, "   -h                         help\n");
         fprintf(fp_help, "   --bam FILE                 (extension) the reads of a basecaller's BAM in place of <reads.fastq>, decoded on the device\n");
         fprintf(fp_help, "   --duplex                   (extension) with --bam: only the reads with the tag dx:i:1\n");
         fprintf(fp_help, "   --bgzf                     (not in the reference) with --bam: the text leaves as BGZF, deflated on the device (as bgzip writes it)\n");
+        fprintf(fp_help, "   --fastq FILE               (not in the reference) <reads.fastq>, plain or bgzip-compressed, filtered and written on the device\n");
         exit(fp_help == stdout ? EXIT_SUCCESS : EXIT_FAILURE);
     }
     if (bam) return seq_bam(bam, min_len, duplex, bgzf);
+    if (fastq) return seq_fastq(fastq, min_len, bgzf);
     cli_fastx_t *fx = cli_fastx_open(argv[optind], 1);
-    cli_rec_t *r;
-    uint64_t before = 0, after = 0, before_n = 0, after_n = 0;
-    while ((r = cli_fastx_next(fx)) != NULL) {
-        const int64_t l = (int64_t)r->seq.l;
-        before += (uint64_t)l;
-        before_n++;
-        if (l >= min_len) { /* src/seq.c:120-129: name, TAB, comment */
-            after += (uint64_t)l;
-            after_n++;
-            printf("@%s", r->name.s);
-            if (r->comment.l) printf("\t%s", r->comment.s);
-            printf("\n%s\n+\n%s\n", r->seq.s, r->qual.s);
-        }
-    }
-    seq_summary(min_len, before_n, before, after_n, after);
+    uint64_t stats[4] = {0, 0, 0, 0};
+    cli_seq_records(fx, min_len, stats);
+    seq_summary(min_len, stats[0], stats[1], stats[2], stats[3]);
     cli_fastx_close(fx);
     return 0;
 }

@@ -737,6 +737,58 @@ const cornetto_bamerr_t *cornetto_bamfq_error(const cornetto_bamfq_t *b);
 int cornetto_bamfq_records(cornetto_accel_t *h, cornetto_bamfq_t *b, cornetto_bamfqrec_t **recs, int64_t *n_recs);
 
 /* ---------------------------------------------------------------------------------------------------
+ * FASTQ to FASTQ: the length-filtered text `cornetto seq -m` prints (src/seq.c:116-129), written on the device from FASTQ text that is plain
+ * bytes or BGZF blocks: `seq --fastq`.  The object, its window, its four copy slots and its two kinds of get are those of cornetto_bamfq_*;
+ * the records and what makes one plain are those of cornetto_fastq_split() (the same kernel).  A kept record (len >= min_len) prints as
+ *   '@' name [TAB comment] '\n' bases "\n+\n" qualities '\n'
+ * the TAB in place of whatever white-space byte stood between name and comment, none when the comment is empty; a trailing '\r' of the three
+ * payload lines, whatever follows '+' on the third line and the separator itself are not copied.  A record that holds a byte 0 is not plain
+ * for this stage (the reference prints with "%s"): it and everything behind it are the caller's sequential reader's.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct {
+    int32_t min_len;     /* keep len >= this (30000: src/seq.c:63) */
+    int32_t records;     /* non-zero: keep the record table (cornetto_fqseq_records) */
+    int64_t window;      /* bytes of FASTQ text held on the device at once, at most 2^32-256 (the newline table is uint32), 256 MiB by default: an
+                            operating parameter, never changes a result.  It must hold the largest record, and for BGZF blocks one block more */
+} cornetto_fqseq_opt_t;
+void cornetto_fqseq_defaults(cornetto_fqseq_opt_t *opt);
+
+/* output bytes per workgroup of the text kernel (tests plant every part of a record at its multiples) */
+#define CORNETTO_FQSEQ_TILE 16384
+int32_t cornetto_fqseq_tile(void);
+
+typedef struct cornetto_fqseq cornetto_fqseq_t;
+int cornetto_fqseq_open(cornetto_accel_t *h, const cornetto_fqseq_opt_t *opt, cornetto_fqseq_t **out);
+void cornetto_fqseq_close(cornetto_accel_t *h, cornetto_fqseq_t *q);
+/* ONE window.  src: the next bytes of the stream, plain or BGZF blocks, under the contract of cornetto_bgin_feed_src() (NULL or empty: nothing
+ * new).  *taken: the leading bytes (plain) or blocks (BGZF) that fit the window behind the tail the last window left; hand the others over
+ * again.  final: nothing follows `src` (it counts once all of src is taken: the last line then need not end in a newline).  The text is
+ * indexed, framed, sized and scanned; *n_text: bytes of the window's text, ready for cornetto_fqseq_get() until the next feed.  What follows
+ * the last whole record stays on the device in front of the next window.  *plain = 0: the first group of four lines that is not a plain
+ * record (or, with `final`, whatever follows the last one) ends the device's part: the window's text and the counts cover the records in
+ * front of it, cornetto_fqseq_rest() says where the sequential reader continues, and no further feed is taken (CORNETTO_E_ARG).
+ * CORNETTO_E_FORMAT: a damaged BGZF block (cornetto_fqseq_error(): its index in the file, counted over all feeds); the window's text is that of
+ * the records that lie wholly in front of the block and may be fetched; no further feed is taken.  CORNETTO_E_NOMEM with *taken == 0: not one
+ * more byte (or block) fits behind the carried bytes: a record larger than the window.  Synchronous: `src` may be overwritten on return. */
+int cornetto_fqseq_feed(cornetto_accel_t *h, cornetto_fqseq_t *q, const cornetto_bgsrc_t *src, int final, int64_t *taken, int64_t *n_text, int32_t *plain);
+/* offset in the plain or inflated stream of the first byte that no record of the feeds so far holds */
+int64_t cornetto_fqseq_rest(const cornetto_fqseq_t *q);
+/* -1, or the index of the damaged block */
+int64_t cornetto_fqseq_error(const cornetto_fqseq_t *q);
+/* The two kinds of get, with the contracts (slots, dst_cap, waits) of cornetto_bamfq_get() / _wait() and cornetto_bamfq_get_bgzf() / _wait_bgzf():
+ * fqseq_text writes the slab, a workgroup a tile of CORNETTO_FQSEQ_TILE bytes, a thread 16 bytes. */
+int cornetto_fqseq_get(cornetto_accel_t *h, cornetto_fqseq_t *q, char *dst_pinned, int64_t at, int64_t n, int slot);
+int cornetto_fqseq_wait(cornetto_accel_t *h, cornetto_fqseq_t *q, int slot);
+int cornetto_fqseq_get_bgzf(cornetto_accel_t *h, cornetto_fqseq_t *q, char *dst_pinned, int64_t dst_cap, int64_t at, int64_t n, int slot);
+int cornetto_fqseq_wait_bgzf(cornetto_accel_t *h, cornetto_fqseq_t *q, int slot, int64_t *n_bytes);
+/* stats[0 .. 5): reads and bases of `total reads`, reads and bases of `reads >= min_len`, then the records taken, over the feeds so far */
+void cornetto_fqseq_stats(const cornetto_fqseq_t *q, int64_t *stats);
+/* The record table of the feeds so far (opt.records), in input order, offsets into the stream: cornetto_free(). */
+int cornetto_fqseq_records(cornetto_accel_t *h, cornetto_fqseq_t *q, cornetto_fqrec_t **recs, int64_t *n_recs);
+/* Waits for every get; *ms: the time of the fqseq_text launches so far that ran under cornetto_accel_set_timing(2), *n_bytes: what they wrote. */
+int cornetto_fqseq_text_time(cornetto_accel_t *h, cornetto_fqseq_t *q, double *ms, int64_t *n_bytes);
+
+/* ---------------------------------------------------------------------------------------------------
  * fixasm output text: the records of a resident assembly, renamed and reoriented
  * ------------------------------------------------------------------------------------------------- */
 
