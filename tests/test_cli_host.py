@@ -10,6 +10,7 @@ import pytest
 
 import cornetto_amd
 from helpers import golden
+from telowin_cases import stderr_line
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -165,6 +166,24 @@ def test_text_parsers_in_front_of_the_device_calls(cli, golden_dir, tmp_path):
     for sub in (["seq", "-m", "3"], ["fa2bed"]):
         rc, out, err = run(cli, sub + ["-"], stdin=fq.read_bytes())
         assert rc == 1 and out == b"" and b"Could not to open file -: No such file or directory" in err
+
+
+@pytest.mark.parametrize("identity,thr,exp", [
+    ("100", "0", "hits_craft.i100t0.telowin.exp"),
+    ("100", "0.5", "hits_craft.i100t05.telowin.exp"),
+    ("99.9", "0.4", "hits_craft.telowin.exp"),
+    ("90", "0.1", "hits_craft.i90t01.telowin.exp"),
+])
+def test_telowin_on_a_crafted_hit_list_on_the_host(cli, golden_dir, monkeypatch, identity, thr, exp):
+    """CORNETTO_ACCEL=no: the parser and the host windows (cli/host_backend.c) on hits that telofind never writes (tests/telowin_cases.py:
+    overlapping, repeated, unsorted, `start >= end`; a contig of length 0, a name that comes back) print what the unmodified reference
+    prints (tests/golden/make_golden_telowin_hits.py) — with threshold 0 every window it visits"""
+    for k, v in (("CORNETTO_ACCEL", "no"), ("HIP_VISIBLE_DEVICES", ""), ("ROCR_VISIBLE_DEVICES", "")):
+        monkeypatch.setenv(k, v)
+    rc, out, err = run(cli, ["telowin", os.path.join(golden_dir, "hits_craft.telomere"), identity, thr])
+    assert rc == 0, err.decode()
+    assert out == golden(golden_dir, exp)
+    assert stderr_line(identity, thr) in err
 
 
 def _bedgraph_pair(tmp_path, lens, seed, digits_t=(10_000, 60_000), digits_q=(0, 10)):

@@ -75,6 +75,10 @@ def _win_text(names, lens, wins):
     ("probe.telomere", 95.0, 0.4, "probe.i95.telowin.exp"),
     ("mix.telofind.exp", 99.9, 0.4, "mix.telowin.exp"),
     ("mix.telofind.exp", 99.9, 0.1, "mix.t01.telowin.exp"),
+    ("hits_craft.telomere", 100.0, 0.0, "hits_craft.i100t0.telowin.exp"),      # (not telofind output: tests/golden/make_golden_telowin_hits.py)
+    ("hits_craft.telomere", 100.0, 0.5, "hits_craft.i100t05.telowin.exp"),
+    ("hits_craft.telomere", 99.9, 0.4, "hits_craft.telowin.exp"),
+    ("hits_craft.telomere", 90.0, 0.1, "hits_craft.i90t01.telowin.exp"),
 ])
 def test_telowin_golden(acc, golden_dir, tsv, identity, thr, exp):
     names, lens, hits = _parse_tsv(golden(golden_dir, tsv))

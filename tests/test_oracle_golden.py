@@ -66,6 +66,12 @@ def _telowin_text(tsv, identity, thr):
     ("probe.telomere", 95.0, 0.4, "probe.i95.telowin.exp"),
     ("mix.telofind.exp", 99.9, 0.4, "mix.telowin.exp"),
     ("mix.telofind.exp", 99.9, 0.1, "mix.t01.telowin.exp"),
+    # a hit list that is not telofind output (tests/golden/make_golden_telowin_hits.py): overlapping, repeated, unsorted and empty hits, a
+    # contig of length 0, a name that comes back; threshold 0 prints every window the reference visits
+    ("hits_craft.telomere", 100.0, 0.0, "hits_craft.i100t0.telowin.exp"),
+    ("hits_craft.telomere", 100.0, 0.5, "hits_craft.i100t05.telowin.exp"),
+    ("hits_craft.telomere", 99.9, 0.4, "hits_craft.telowin.exp"),
+    ("hits_craft.telomere", 90.0, 0.1, "hits_craft.i90t01.telowin.exp"),
 ])
 def test_telowin_golden(golden_dir, tsv, identity, thr, exp):
     assert _telowin_text(golden(golden_dir, tsv), identity, thr) == golden(golden_dir, exp)
