@@ -11,6 +11,8 @@
 //               r = w % inc elements ("head").  A workgroup-wide inclusive scan (u32, wrapping like the
 //               reference's int accumulators) turns block sums into tile-local prefix sums; the tile total
 //               is kept exactly in u64 for the mean.
+//  cov_blocks_scan  the same prefixes for inc = 50 and w a multiple of it (the default -w 2500 -i 50) without the transpose: wave
+//               scans over the 16-byte vectors in load order, the block ends picked out by a fixed lane pattern.
 //  cov_tilescan one workgroup: exclusive scan of tile totals (u32 offsets for the prefix, u64 grand totals).
 //  cov_windows  one thread per window j: sum = G[a+q-1] - G[a-1] + head[a+q] with G = local prefix +
 //               tile offset, q = w / inc; integer division by (end-st) truncating toward zero (:360-361);
@@ -257,6 +259,157 @@ __global__ __launch_bounds__(CB_THREADS) void cov_blocks(CbArgs A)
         A.tile_tot64[tix] = x;
     }
   }
+}
+
+// cov_blocks_scan: the same prefixes for r = 0 and a compile-time even INC >= 8, without the transpose through LDS.  Wave wv owns the
+// values [64 INC wv, 64 INC (wv + 1)) of the tile — the 64 blocks whose prefixes threads 64 wv ... write in cov_blocks — as 8 INC vectors
+// of 8 values in load order, vector lane + 64 k in round k.  The tile-local prefix at the end of a block is the wave-exclusive scan of
+// the vector sums at the lane that holds the block's end, plus that lane's leading 2, 4, 6 or 8 values (INC is even, so never an odd
+// count; INC >= 8, so at most one end per vector), plus the rounds and the waves in front.  u32 sums regrouped: no bit changes.
+//
+// Where the block ends lie is the same for every wave and tile (INC = 50: the pattern repeats every 25 vectors), so it is a table:
+// per round two lane masks that say how many values lie behind the end (kernel arguments: scalar registers, loaded with the others),
+// and per lane and round the byte offset of the prefix within the wave's 64 — or an offset behind the 512 bytes of the wave's
+// output buffer, for a lane that holds no block end: the buffer store drops it.
+struct CbsMasks {
+    uint64_t odd[8], hi[8];      // the end lies behind an odd number of dwords (2 or 6 values) / in the vector's upper half (6 or 8 values)
+};
+template <int INC>
+struct CbsPattern {
+    static constexpr int NVEC = 64 * INC / 8, NR = (NVEC + 63) / 64;
+    uint32_t off[64][8];
+    uint64_t odd[8], hi[8];
+    constexpr CbsMasks masks() const
+    {
+        CbsMasks m{};
+        for (int k = 0; k < 8; ++k) { m.odd[k] = odd[k]; m.hi[k] = hi[k]; }
+        return m;
+    }
+    constexpr CbsPattern() : off{}, odd{}, hi{}
+    {
+        for (int k = 0; k < 8; ++k)
+            for (int l = 0; l < 64; ++l) {
+                const int v = l + 64 * k, j = (8 * v + 8) / INC, m = j * INC - 8 * v;     // block j ends after m of the vector's values
+                const bool has = k < NR && v < NVEC && j >= 1 && m >= 2;
+                off[l][k] = has ? (uint32_t)(j - 1) * 8u : 0xFFFFFF00u;
+                if (has && (m == 2 || m == 6)) odd[k] |= 1ull << l;
+                if (has && m >= 6) hi[k] |= 1ull << l;
+            }
+    }
+};
+template <int INC>
+__constant__ const CbsPattern<INC> cbs_pattern{};
+typedef unsigned int cb_u2 __attribute__((ext_vector_type(2)));
+
+// the values of a vector from the nv-th on are behind the contig's end (the buffer ends with the vector, not with the contig)
+__device__ __forceinline__ void cbs_clip(cb_u4 &d, int nv)
+{
+#pragma unroll
+    for (int i = 0; i < 4; ++i) d[i] &= nv >= 2 * i + 2 ? 0xFFFFFFFFu : nv == 2 * i + 1 ? 0x0000FFFFu : 0u;
+}
+
+// one vector of one array: the prefix at the block end this lane may hold, within the round — the inclusive scan of the vector sums
+// less the values behind the block end — and the round's total
+__device__ __forceinline__ uint32_t cbs_round(const cb_u4 d, uint32_t &carry, uint64_t m_odd, uint64_t m_hi)
+{
+    const uint32_t t1 = add_u16x2(0, d[3]), t2 = add_u16x2(t1, d[2]), t3 = add_u16x2(t2, d[1]), s = add_u16x2(t3, d[0]);
+    const uint32_t incl = cnwave::wave_incl_dpp(s);
+    const bool odd = __builtin_amdgcn_inverse_ballot_w64(m_odd), hi = __builtin_amdgcn_inverse_ballot_w64(m_hi);
+    const uint32_t tail = hi ? (odd ? t1 : 0u) : (odd ? t3 : t2);
+    carry = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    return incl - tail;
+}
+
+template <int INC>
+__global__ __launch_bounds__(CB_THREADS) void cov_blocks_scan(CbArgs A, CbsMasks M)
+{
+    static_assert(INC >= 8 && INC % 2 == 0 && INC <= 64, "cov_blocks_scan: an even block size, at most one block end per vector, at most 8 rounds");
+    constexpr uint32_t WVALS = 64 * INC;
+    constexpr int NR = CbsPattern<INC>::NR;
+    const int64_t tix = blockIdx.x;
+    const int4 m0 = A.tmeta[2 * tix], m1 = A.tmeta[2 * tix + 1];        // (ahead of s_setprio: the compiler takes that for a store, and what follows one is no scalar load)
+    // No s_setprio here, unlike the staging kernel: its waves stall at eight barriers and at the LDS port and need the priority to get
+    // through beside the resident sdust waves.  These waves issue ~400 instructions back to back once their loads have landed; ahead of
+    // the sdust waves (priority 1 or 3) that costs sd_sift more than the shorter cov_prepare gives back (step 6.62-6.81 ms against the
+    // staging kernel's 6.41-6.61), at the same priority the step is 6.13-6.35 ms.
+    __shared__ uint32_t wsum[2][CB_THREADS / 64];
+
+    const int lane = threadIdx.x & 63;
+    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t off = (int64_t)(((unsigned long long)(uint32_t)m1.y << 32) | (uint32_t)m1.x);
+    // first element of the wave's share within the contig, and how many of its values the contig still has (a tile starts at most
+    // 256 blocks + a window behind the contig's end: below 2^32 for every int length)
+    const uint32_t w0 = (uint32_t)m0.y * INC + wv * WVALS, len = (uint32_t)m0.z;
+    const uint32_t rem = w0 >= len ? 0u : len - w0 < WVALS ? len - w0 : WVALS;
+    // The share as a raw buffer that ends with the contig (rounded up to a whole vector): loads past it return zeros, so the lanes
+    // of the last round that have no vector, and blocks behind the contig's end, need no test.
+    const uint32_t nrec = (rem * 2 + 15) & ~15u;
+    const int64_t eo = off + w0;
+    const __amdgpu_buffer_rsrc_t rsd = __builtin_amdgcn_make_buffer_rsrc((void *)(A.depth + eo), 0, (int)nrec, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsq = __builtin_amdgcn_make_buffer_rsrc((void *)(A.mq + eo), 0, (int)nrec, 0x00020000);
+    cb_u4 vd[NR], vq[NR];
+#pragma unroll
+    for (int k = 0; k < NR; ++k) vd[k] = __builtin_amdgcn_raw_buffer_load_b128(rsd, (lane + 64 * k) * 16, 0, 0);
+#pragma unroll
+    for (int k = 0; k < NR; ++k) vq[k] = __builtin_amdgcn_raw_buffer_load_b128(rsq, (lane + 64 * k) * 16, 0, 0);
+    const CbsPattern<INC> &P = cbs_pattern<INC>;
+    const uint4 o0 = *reinterpret_cast<const uint4 *>(&P.off[lane][0]), o1 = *reinterpret_cast<const uint4 *>(&P.off[lane][4]);
+    const uint32_t ooff[8] = {o0.x, o0.y, o0.z, o0.w, o1.x, o1.y, o1.z, o1.w};
+
+    if (rem < WVALS) {                                                    // the contig ends inside the share, or before it
+        const int nv = (int)rem - 8 * lane;
+#pragma unroll
+        for (int k = 0; k < NR; ++k) {
+            cbs_clip(vd[k], nv - 512 * k);
+            cbs_clip(vq[k], nv - 512 * k);
+        }
+    }
+
+    // in load order, a few rounds at a time (their scans interleave): the first rounds run while the later ones are still in flight
+    uint32_t cd[NR + 1], cq[NR + 1], od[NR], oq[NR];                      // c[k]: the rounds in front of round k
+    cd[0] = cq[0] = 0;
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+        uint32_t tot;
+        od[k] = cbs_round(vd[k], tot, M.odd[k], M.hi[k]);
+        cd[k + 1] = cd[k] + tot;
+        if (k % 3 == 2 && k + 1 < NR) __builtin_amdgcn_sched_barrier(0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+        uint32_t tot;
+        oq[k] = cbs_round(vq[k], tot, M.odd[k], M.hi[k]);
+        cq[k + 1] = cq[k] + tot;
+        if (k % 3 == 2 && k + 1 < NR) __builtin_amdgcn_sched_barrier(0);
+    }
+
+    if (lane == 0) {
+        wsum[0][wv] = cd[NR];
+        wsum[1][wv] = cq[NR];
+    }
+    __syncthreads();
+    // the waves in front: lane l takes the total of wave l % 4 if that is one of them, and each quad adds its four up
+    const bool front = (uint32_t)(lane & 3) < wv;
+    const uint32_t wd = wsum[0][lane & 3], wq = wsum[1][lane & 3];
+    uint32_t fd = front ? wd : 0u, fq = front ? wq : 0u;
+    fd += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)fd, 0xB1, 0xF, 0xF, true);       // quad_perm:[1,0,3,2]
+    fq += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)fq, 0xB1, 0xF, 0xF, true);
+    fd += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)fd, 0x4E, 0xF, 0xF, true);       // quad_perm:[2,3,0,1]
+    fq += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)fq, 0x4E, 0xF, 0xF, true);
+    const __amdgpu_buffer_rsrc_t rso = __builtin_amdgcn_make_buffer_rsrc((void *)(A.pre + (size_t)tix * CB_THREADS + wv * 64), 0, 64 * (int)sizeof(uint2), 0x00020000);
+#pragma unroll
+    for (int k = 0; k < NR; ++k) {
+        const cb_u2 o = {od[k] + fd + cd[k], oq[k] + fq + cq[k]};
+        __builtin_amdgcn_raw_buffer_store_b64(o, rso, (int)ooff[k], 0, 0);
+    }
+    if (wv == CB_THREADS / 64 - 1 && lane == 0) {                         // the last wave's last carry ends the tile: below 2^32, so exact
+        A.tile_tot32[tix] = make_uint2(cd[NR] + fd, cq[NR] + fq);
+        ulonglong2 x;
+        x.x = cd[NR] + fd;
+        x.y = cq[NR] + fq;
+        A.tile_tot64[tix] = x;
+    }
 }
 
 // exact grand totals of depth / mq for the mean: one 64-bit atomic pair per workgroup
@@ -577,7 +730,9 @@ int cn_cov_prepare_impl(cornetto_accel_t *h, cornetto_cov_t *c, int32_t w, int32
     if (inc <= CB_MAX_INC_LDS) {
         const size_t lds = (size_t)CB_THREADS / CB_PARTS * inc * sizeof(uint16_t);
         static_assert(CB_THREADS / CB_PARTS * 50 / 8 <= 4 * CB_THREADS, "cov_blocks<true, INC>: at most 4 vectors per thread and part");
-        if (A.inc == 50) {                               // the default step (-i 50)
+        if (A.inc == 50 && r == 0 && A.tmeta && !CN_DEV_INT("CORNETTO_COV_BLOCKS_STAGE", 0)) {   // -i 50 and w a multiple of it (-w 2500): no heads, no staging (the switch, read per call: the tests compare both kernels in one process)
+            CN_LAUNCH(h, "cov_blocks", cov_blocks_scan<50><<<dim3((unsigned)nt), dim3(CB_THREADS), 0, h->stream>>>(A, CbsPattern<50>{}.masks()));
+        } else if (A.inc == 50) {                        // the default step (-i 50)
             static const int cb_nt = CN_DEV_INT("CORNETTO_COV_TILES", 1);   // (2: two tiles per workgroup, all loads up front — 138 registers: does not fit beside the resident sdust waves, 8.4 instead of 3.9 ms in the step)
             if (cb_nt == 2) {
                 CN_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void *>(&cov_blocks<true, 50, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
