@@ -277,6 +277,13 @@ def lib(dev=False):
         "cornetto_bamfq_stats": (None, [vp, C.POINTER(i64)]),
         "cornetto_bamfq_error": (C.POINTER(BamErr), [vp]),
         "cornetto_bamfq_records": (C.c_int, [vp, vp, pp, C.POINTER(i64)]),
+        "cornetto_bamfq_set_max_err": (C.c_int, [vp, vp, i64]),
+        "cornetto_bamfq_qstats": (None, [vp, C.POINTER(i64)]),
+        "cornetto_bamfq_qsums": (C.c_int, [vp, vp, pp, C.POINTER(i64)]),
+        "cornetto_qual_weight": (C.c_uint32, [C.c_int]),
+        "cornetto_fqseq_set_max_err": (C.c_int, [vp, vp, i64]),
+        "cornetto_fqseq_qstats": (None, [vp, C.POINTER(i64)]),
+        "cornetto_fqseq_qsums": (C.c_int, [vp, vp, pp, C.POINTER(i64)]),
         "cornetto_fqseq_tile": (i32, []),
         "cornetto_fqseq_defaults": (None, [C.POINTER(FqSeqOpt)]),
         "cornetto_fqseq_open": (C.c_int, [vp, C.POINTER(FqSeqOpt), pp]),
@@ -1017,13 +1024,15 @@ class Accel:
             raise BamFormatError(2, -1, 0, -1)
         return (blocks,) + tuple(hdr)
 
-    def bam_fastq(self, blob, min_len=0, duplex=False, window=None, slab=None, feeds=1):
+    def bam_fastq(self, blob, min_len=0, duplex=False, window=None, slab=None, feeds=1, max_err=None):
         """the BAM file `blob` (bytes) through the feed / get loop of cornetto_bamfq_*: the FASTQ text `seq --bam` prints -> (text, stats,
         records): stats = [reads, bases of `total reads`, reads, bases of `reads >= min_len`], records = the record table (BAMFQREC_DT).
         window: bytes of inflated BAM on the device at once; slab: bytes per get (the whole text of a window by default), the gets take
         turns on the four copy slots; feeds: the blocks are handed over in that many parts.  Neither changes a result.  Raises
         BamFormatError, which carries text, stats and records of the records in front of the failing one; a record larger than the window
-        raises AccelError (status -4).  The kernel times of the feeds are kept in self.bam_timing."""
+        raises AccelError (status -4).  The kernel times of the feeds are kept in self.bam_timing.  max_err: P of `seq -q` (an integer
+        0 .. 10^9, None: off; cornetto_bamfq_set_max_err): `kept` of the records is then 1 for the printed ones, self.bam_qstats = [reads,
+        bases printed] and self.bam_qsums = the records' sums of quality weights (uint64; None without max_err)."""
         L = self.L
         blocks, _names, lens, skip = self._bam_head(blob)
         comp = self._text_from(blob)
@@ -1037,6 +1046,13 @@ class Accel:
             L.cornetto_bamfq_stats(fq, st)
             p, n = C.c_void_p(), C.c_int64()
             self._chk(L.cornetto_bamfq_records(self.h, fq, C.byref(p), C.byref(n)))
+            qs = (C.c_int64 * 2)()
+            L.cornetto_bamfq_qstats(fq, qs)
+            self.bam_qstats, self.bam_qsums = list(qs), None
+            if max_err is not None:
+                ps, ns = C.c_void_p(), C.c_int64()
+                self._chk(L.cornetto_bamfq_qsums(self.h, fq, C.byref(ps), C.byref(ns)))
+                self.bam_qsums = _take(L, ps, ns.value, np.dtype(np.uint64))
             return b"".join(out), list(st)[:4], _take(L, p, n.value, BAMFQREC_DT)
 
         def fail():
@@ -1074,6 +1090,8 @@ class Accel:
                 opt.window = window
             fq = C.c_void_p()
             self._chk(L.cornetto_bamfq_open(self.h, C.byref(opt), C.byref(fq)))
+            if max_err is not None:
+                self._chk(L.cornetto_bamfq_set_max_err(self.h, fq, max_err))
             cuts = [len(blocks) * i // feeds for i in range(feeds + 1)]
             for i in range(feeds):
                 part = np.ascontiguousarray(blocks[cuts[i]:cuts[i + 1]])
@@ -1106,7 +1124,7 @@ class Accel:
                 L.cornetto_bamfq_close(self.h, fq)
             L.cornetto_text_free(self.h, comp)
 
-    def fastq_seq(self, data, min_len, window=None, slab=None, feeds=1, bgzf_in=False, bgzf_out=False):
+    def fastq_seq(self, data, min_len, window=None, slab=None, feeds=1, bgzf_in=False, bgzf_out=False, max_err=None):
         """FASTQ text through the feed / get loop of cornetto_fqseq_*: what `seq -m min_len` prints -> (text, stats, recs, rest_offset, plain).
         data: the text (bytes), or with bgzf_in the file as a BGZF blob (inflated on the device), or a list of parts of the stream, each
         bytes or a Bgzf (the kind may change between feeds); the bytes / blocks of every part are handed over in `feeds` parts.  text: the
@@ -1116,7 +1134,9 @@ class Accel:
         on from there.  window: bytes of text on the device at once; slab: bytes per get (the whole text of a window by default), the gets
         take turns on the four copy slots.  Neither changes a result.  Raises FastqBlockError for a damaged block; a record larger than the
         window raises AccelError (status -4, .taken = 0).  Kernel times of the feeds: self.fq_timing; of fqseq_text: self.fq_text_time =
-        (ms, bytes written) when the handle times every launch."""
+        (ms, bytes written) when the handle times every launch.  max_err: P of `seq -q` (an integer 0 .. 10^9, None: off;
+        cornetto_fqseq_set_max_err): `keep` of the records is then 1 for the printed ones, self.fq_qstats = [reads, bases printed] and
+        self.fq_qsums = the records' sums of quality weights (uint64; None without max_err)."""
         L = self.L
         parts = data if isinstance(data, (list, tuple)) else [Bgzf(data) if bgzf_in else data]
         fq = None
@@ -1132,6 +1152,13 @@ class Accel:
             ms, nb = C.c_double(), C.c_int64()
             self._chk(L.cornetto_fqseq_text_time(self.h, fq, C.byref(ms), C.byref(nb)))
             self.fq_text_time = (ms.value, nb.value)
+            qs = (C.c_int64 * 2)()
+            L.cornetto_fqseq_qstats(fq, qs)
+            self.fq_qstats, self.fq_qsums = list(qs), None
+            if max_err is not None:
+                ps, ns = C.c_void_p(), C.c_int64()
+                self._chk(L.cornetto_fqseq_qsums(self.h, fq, C.byref(ps), C.byref(ns)))
+                self.fq_qsums = _take(L, ps, ns.value, np.dtype(np.uint64))
             return out if bgzf_out else b"".join(out), list(st)[:4], _take(L, p, n.value, FQREC_DT), int(L.cornetto_fqseq_rest(fq))
 
         def pull(n_text):
@@ -1190,6 +1217,8 @@ class Accel:
                 opt.window = window
             fq = C.c_void_p()
             self._chk(L.cornetto_fqseq_open(self.h, C.byref(opt), C.byref(fq)))
+            if max_err is not None:
+                self._chk(L.cornetto_fqseq_set_max_err(self.h, fq, max_err))
             groups = sources()
             plain = True
             for gi, (kind, comp, body) in enumerate(groups):

@@ -284,6 +284,7 @@ int cli_bam_fastq(cornetto_accel_t *h, const char *path, int min_len, int duplex
         if (!b) {
             opt.n_ref = R.n_ref;
             cli_accel_check(h, cornetto_bamfq_open(h, &opt, &b), "BAM to FASTQ");
+            if (cli_qmean_max_err() >= 0) cli_accel_check(h, cornetto_bamfq_set_max_err(h, b, cli_qmean_max_err()), "BAM to FASTQ");
         }
         for (int64_t i = 0; (i < nb || skip > 0) && !nomem && failed == CORNETTO_OK;) {
             int64_t taken = 0, n_text = 0;
@@ -338,6 +339,9 @@ int cli_bam_fastq(cornetto_accel_t *h, const char *path, int min_len, int duplex
     memset(&err, 0, sizeof(err));
     if (b) {
         cornetto_bamfq_stats(b, st);
+        int64_t qst[2] = {0, 0};
+        cornetto_bamfq_qstats(b, qst);      /* (what the device printed; the host reader counts what it prints behind it) */
+        cli_qmean_add(qst[0], qst[1]);
         err = *cornetto_bamfq_error(b);
     }
     for (int k = 0; k < 4; ++k) stats[k] = (uint64_t)st[k];

@@ -261,6 +261,17 @@ void cli_seq_records(cli_fastx_t *fx, int min_len, uint64_t stats[4]);
  * $CORNETTO_EMIT_SLAB bytes.  Where the text stops being plain records, or a record is larger than the window (a CLI_WARNING says so), the
  * sequential reader prints the rest.  stats: added to.  A BGZF file that is not one to its end: cli_bgz_fail(), the text in front printed */
 void cli_fastq_seq(cornetto_accel_t *h, const char *path, int min_len, uint64_t stats[4]);
+/* cli/qmean.c: `seq -q` (not in the reference; include/cornetto_accel.h states the rule).  seq_main() sets P once (_set; -1: off, the default);
+ * every reader of `seq` asks cli_qmean_max_err() for it — the device objects take it through cornetto_*_set_max_err() — and every host loop
+ * asks cli_qmean_pass() about the record it is about to print: the n_qual printed quality characters and the n_bases printed bases (true
+ * without -q, and for an empty quality line), and counts what it prints with cli_qmean_count(); cli_qmean_add(): what a device object
+ * printed.  cli_qmean_printed(): reads and bases of the third summary line. */
+void cli_qmean_set(int64_t max_err);
+int64_t cli_qmean_max_err(void);
+int cli_qmean_pass(const char *qual, size_t n_qual, int64_t n_bases);
+void cli_qmean_count(int64_t n_bases);
+void cli_qmean_add(int64_t reads, int64_t bases);
+void cli_qmean_printed(uint64_t printed[2]);
 /* cli/bgzf_out.c: `seq --bam --bgzf` (an extension): between _begin() and _end() the text of both readers above leaves as a BGZF stream on stdout.
  * _text(): text, collected into members of 65280 bytes through zlib; _members(): members the device made (cornetto_bamfq_get_bgzf), behind the
  * pending text; _flush(): the pending text as a member — cli_bam_fail() calls it, so a malformed file leaves the members of the records in front

@@ -4,6 +4,7 @@
  * src/seq.c:53-138.  One device: the records come from the streamer (cli/stream.c), one scan per batch, printed in
  * input order.  CORNETTO_DEVICES: the sequential reader's batches are dealt to the devices.  CORNETTO_ACCEL=no: the host path. */
 #include <getopt.h>
+#include <math.h>
 #include <stdlib.h>
 #include <pthread.h>
 #include <string.h>
@@ -327,10 +328,17 @@ int assbed_main(int argc, char *argv[])
 }
 
 /* ---------------------------------------------------------------- seq */
+static double seq_min_qscore = 0.0;      /* -q, as it was given: for the third summary line */
+
 static void seq_summary(int min_len, uint64_t before_n, uint64_t before, uint64_t after_n, uint64_t after)
 {
     fprintf(stderr, "total reads: %lu\t%lu bases\t%.2f Gbases\n", (unsigned long)before_n, (unsigned long)before, before / 1e9);
     fprintf(stderr, "reads >= %d: %lu\t%lu bases\t%.2f Gbases\n", min_len, (unsigned long)after_n, (unsigned long)after, after / 1e9);
+    if (cli_qmean_max_err() >= 0) {      /* -q (not in the reference): the reads that were printed */
+        uint64_t p[2];
+        cli_qmean_printed(p);
+        fprintf(stderr, "mean qscore >= %g: %lu\t%lu bases\t%.2f Gbases\n", seq_min_qscore, (unsigned long)p[0], (unsigned long)p[1], p[1] / 1e9);
+    }
 }
 
 /* `seq --bam FILE [--duplex] [--bgzf]` (an extension; include/cornetto_accel.h states the rules): a basecaller's BAM to the text `seq` prints */
@@ -363,6 +371,9 @@ void cli_seq_records(cli_fastx_t *fx, int min_len, uint64_t stats[4])
         if (l < min_len) continue;
         stats[3] += (uint64_t)l;
         stats[2]++;
+        /* -q: the characters "%s" prints (they end at a byte 0) */
+        if (!cli_qmean_pass(r->qual.s, r->qual.l ? strlen(r->qual.s) : 0, (int64_t)strlen(r->seq.s))) continue;
+        cli_qmean_count(l);
         if (!bgzf) { /* src/seq.c:120-129: name, TAB, comment */
             printf("@%s", r->name.s);
             if (r->comment.l) printf("\t%s", r->comment.s);
@@ -407,13 +418,13 @@ int seq_main(int argc, char *argv[])
 {
     static const struct option lo[] = {{"verbose", required_argument, 0, 'v'}, {"min-len", required_argument, 0, 'm'}, {"help", no_argument, 0, 'h'},
                                        {"bam", required_argument, 0, 0}, {"duplex", no_argument, 0, 0}, {"accel", required_argument, 0, 0}, {"bgzf", no_argument, 0, 0},
-                                       {"fastq", required_argument, 0, 0}, {0, 0, 0, 0}};
+                                       {"fastq", required_argument, 0, 0}, {"min-qscore", required_argument, 0, 'q'}, {0, 0, 0, 0}};
     FILE *fp_help = stderr;
     int min_len = 30000; /* src/seq.c:63 */
     int c, li = 0, duplex = 0, bgzf = 0;
     const char *bam = NULL, *fastq = NULL;
     optind = 1;
-    while ((c = getopt_long(argc, argv, "hm:", lo, &li)) >= 0) {
+    while ((c = getopt_long(argc, argv, "hm:q:", lo, &li)) >= 0) {
         if (c == 'h') {
             fp_help = stdout;
         } else if (c == 'm') {
@@ -422,6 +433,16 @@ int seq_main(int argc, char *argv[])
                 fprintf(stderr, "Error: min-len must be a positive integer\n");
                 exit(EXIT_FAILURE);
             }
+        } else if (c == 'q') {
+            char *end = NULL;
+            const double t = strtod(optarg, &end);
+            if (end == optarg || *end || !(t >= 0.0 && t <= (double)CORNETTO_QUAL_MAX)) {
+                fprintf(stderr, "Error: min-qscore must be a number from 0 to %d\n", CORNETTO_QUAL_MAX);
+                exit(EXIT_FAILURE);
+            }
+            seq_min_qscore = t;
+            /* the largest mean error probability in units of 10^-9, once, for every path */
+            cli_qmean_set((int64_t)floor(1e9 * pow(10.0, -t / 10.0) + 0.5));
         } else if (c == 0 && li == 3) {
             bam = optarg;
         } else if (c == 0 && li == 4) {
@@ -467,6 +488,7 @@ int seq_main(int argc, char *argv[])
         fprintf(fp_help, "Usage: cornetto seq <reads.fastq> \n");
         fprintf(fp_help, "   -m INT                     min length [%d]\n", 30000);
         fprintf(fp_help, "   -h                         help\n");
+        fprintf(fp_help, "   -q FLOAT                   (not in the reference) --min-qscore: only the reads whose mean error probability is at most 10^(-FLOAT/10)\n");
         fprintf(fp_help, "   --bam FILE                 (extension) the reads of a basecaller's BAM in place of <reads.fastq>, decoded on the device\n");
         fprintf(fp_help, "   --duplex                   (extension) with --bam: only the reads with the tag dx:i:1\n");
         fprintf(fp_help, "   --bgzf                     (not in the reference) with --bam: the text leaves as BGZF, deflated on the device (as bgzip writes it)\n");

@@ -114,6 +114,7 @@ void cli_fastq_seq(cornetto_accel_t *h, const char *path, int min_len, uint64_t 
     o.pin_bytes = o.bgzf ? (o.slab_bytes + 65279) / 65280 * 65536 : o.slab_bytes;
     (void)cornetto_accel_set_timing(h, 0);      /* (nobody reads the kernel times here: no event packets beside the kernels) */
     cli_accel_check(h, cornetto_fqseq_open(h, &opt, &o.q), "FASTQ text");
+    if (cli_qmean_max_err() >= 0) cli_accel_check(h, cornetto_fqseq_set_max_err(h, o.q, cli_qmean_max_err()), "FASTQ text");
     double t_read = 0, t_feed = 0;
     int32_t plain = 1;
     int nomem = 0;
@@ -213,6 +214,9 @@ void cli_fastq_seq(cornetto_accel_t *h, const char *path, int min_len, uint64_t 
     int64_t st[5] = {0, 0, 0, 0, 0};
     cornetto_fqseq_stats(o.q, st);
     for (int k = 0; k < 4; ++k) stats[k] += (uint64_t)st[k];
+    int64_t qst[2] = {0, 0};
+    cornetto_fqseq_qstats(o.q, qst);      /* (what the device printed; the sequential reader below counts its own) */
+    cli_qmean_add(qst[0], qst[1]);
     if (fx) {
         if (nomem)
             CLI_WARNING("%s: a record does not fit the window of %lld bytes%s (CORNETTO_FASTQ_WINDOW): reading the rest of the file on the host, one thread", path,

@@ -1011,6 +1011,8 @@ void cli_host_bam_fastq(const char *path, int min_len, int duplex, int64_t skip_
             *o++ = no_qual ? '"' : (char)((q > 93 ? 93 : q) + 33);
         }
         *o++ = '\n';
+        if (!cli_qmean_pass(o - 1 - l_seq, (size_t)l_seq, l_seq)) continue;      /* -q: decided on the quality line as it is printed */
+        cli_qmean_count(l_seq);
         if (cli_bgzf_out_active()) cli_bgzf_out_text(line, need);
         else fwrite(line, 1, need, stdout);
     }

@@ -5,6 +5,12 @@
 //   bam_frame     (bamwin.hpp) the offsets of the records that lie wholly in the window
 //   bamfq_size    a thread per record: the checks and the flag, length and dx rules of bamfq.hpp -> the bytes of the record's text (0: not
 //                 printed), the counts of the two summary lines (a 64-bit atomic per wave), the error with the lowest record index
+//   with cornetto_bamfq_set_max_err() (`seq -q`; nothing of it runs or is allocated otherwise)
+//     bamfq_qrange  a thread per record: the quality array of a record that bamfq_size kept as a range of qmean_sum (length 0: not kept, or the
+//                   qualities are absent)
+//     qmean_sum     (qmean.hip) the sums of quality weights, into a table the window zeroes itself
+//     bamfq_qkeep   a thread per record: l_seq * E[1] in place of the sum where the qualities are absent; sum > P * l_seq clears the record's
+//                   size and its `kept`; the reads and bases that stay are counted
 //   bamfq_scan    the exclusive scan of the sizes (the look-back of scan.hpp): every record's offset in the window's text, and its length
 // and per get of bytes [at, at + n) of that text
 //   bamfq_text    emit.hip's decomposition: a workgroup writes a tile of consecutive output bytes, a thread 16 bytes with one aligned vector
@@ -20,6 +26,7 @@
 #include "common.hpp"
 #include "deflate.hpp"
 #include "internal.hpp"
+#include "qmean.hpp"
 #include "scan.hpp"
 
 namespace {
@@ -31,8 +38,8 @@ constexpr int FQ_PER_THREAD = 4;                                          // 16-
 constexpr int64_t FQ_TILE = (int64_t)FQ_THREADS * 16 * FQ_PER_THREAD;     // 16 KiB of output per block
 
 // words of the small device block behind the window's own
-enum { SM_TOTAL_N = BW_OWN, SM_TOTAL_B = 6, SM_KEPT_N = 7, SM_KEPT_B = 8, SM_TEXT = 9, SM_DET = 10 };
-static_assert(SM_DET + 2 <= BW_WORDS, "the small block");
+enum { SM_TOTAL_N = BW_OWN, SM_TOTAL_B = 6, SM_KEPT_N = 7, SM_KEPT_B = 8, SM_TEXT = 9, SM_DET = 10, SM_Q_N = 12, SM_Q_B = 13 };
+static_assert(SM_DET + 2 <= SM_Q_N && SM_Q_B < BW_WORDS, "the small block");
 
 struct FsArgs {
     const uint8_t *text;
@@ -97,6 +104,47 @@ __global__ void __launch_bounds__(64) bamfq_detail(FsArgs A, int64_t r)
     A.sm[SM_DET + 1] = (unsigned long long)(long long)e.b;
 }
 
+__global__ void __launch_bounds__(256) bamfq_qrange(const uint8_t *__restrict__ text, const uint32_t *__restrict__ off, const uint32_t *__restrict__ size, int64_t n_rec,
+                                                    uint32_t *__restrict__ start, uint32_t *__restrict__ len)
+{
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= n_rec) return;
+    uint32_t s = off[r], l = 0u;         // (a record without text: any place inside it keeps the starts ascending)
+    if (size[r]) {                       // (it has passed the checks of cnq_size: its fields lie inside it)
+        const CnqRec x = cnq_rec(text + off[r]);
+        s = (uint32_t)(x.qual - text);
+        l = x.no_qual ? 0u : (uint32_t)x.S;
+    }
+    start[r] = s;
+    len[r] = l;
+}
+
+__global__ void __launch_bounds__(256) bamfq_qkeep(const uint8_t *__restrict__ text, const uint32_t *__restrict__ off, uint32_t *__restrict__ size, int64_t n_rec,
+                                                   unsigned long long *__restrict__ sum, int64_t max_err, cornetto_bamfqrec_t *recs, unsigned long long *sm)
+{
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    unsigned long long pn = 0, pb = 0;
+    if (r < n_rec && size[r]) {
+        const CnqRec x = cnq_rec(text + off[r]);
+        const unsigned long long L = (unsigned long long)x.S;
+        unsigned long long s = sum[r];
+        if (x.no_qual) sum[r] = s = L * qm_e(1);      // every quality prints as '"'
+        if (s > (unsigned long long)max_err * L) {
+            size[r] = 0u;
+            if (recs) recs[r].kept = 0;
+        } else {
+            pn = 1;
+            pb = L;
+        }
+    }
+    pn = fq_wave_sum(pn);
+    pb = fq_wave_sum(pb);
+    if ((threadIdx.x & 63) == 0 && pn) {
+        atomicAdd(sm + SM_Q_N, pn);
+        atomicAdd(sm + SM_Q_B, pb);
+    }
+}
+
 struct FtArgs {
     CnqSrc S;
     int64_t at, nbytes;
@@ -132,6 +180,14 @@ struct cornetto_bamfq {
     int64_t stats[4] = {0, 0, 0, 0};
     std::vector<cornetto_bamfqrec_t> recs;
     cornetto_bamerr_t err{0, 0, 0, 0, 0};
+    // cornetto_bamfq_set_max_err(): the ranges and sums of qmean_sum ([q_cap] each, grown by the window that needs them), what passed, the sums kept
+    int64_t max_err = -1;
+    bool fed = false;
+    uint32_t *d_qstart = nullptr, *d_qlen = nullptr;
+    unsigned long long *d_qsum = nullptr;
+    int64_t q_cap = 0;
+    int64_t qstats[2] = {0, 0};
+    std::vector<uint64_t> qsums;
     uint8_t *slab[4] = {nullptr, nullptr, nullptr, nullptr};
     int64_t slab_cap[4] = {0, 0, 0, 0};
     hipStream_t q[4] = {nullptr, nullptr, nullptr, nullptr};   // kernel + copy of slot s, in order
@@ -209,6 +265,33 @@ int fq_launch_size(cornetto_accel_t *h, const FsArgs &A)
     return CORNETTO_OK;
 }
 
+// `seq -q` for the window's first n records, between their sizes and the scan: the sums of this window's records alone (the table is zeroed
+// here, whatever it held), then the decision
+int fq_qmean(cornetto_accel_t *h, cornetto_bamfq_t *b, int64_t n, int64_t n_text)
+{
+    if (n > b->q_cap) {
+        void *old[] = {b->d_qstart, b->d_qlen, b->d_qsum};
+        for (void *p : old)
+            if (p) (void)hipFree(p);
+        b->d_qstart = b->d_qlen = nullptr;
+        b->d_qsum = nullptr;
+        b->q_cap = 0;
+        const int64_t cap = std::min(n + n / 8 + 1024, b->w.rec_cap);
+        if (hipMalloc((void **)&b->d_qstart, (size_t)cap * 4) != hipSuccess || hipMalloc((void **)&b->d_qlen, (size_t)cap * 4) != hipSuccess ||
+            hipMalloc((void **)&b->d_qsum, (size_t)cap * 8) != hipSuccess)
+            return cn_fail(h, CORNETTO_E_NOMEM, "bamfq_feed: device allocation of the quality sums of %lld records failed", (long long)cap);
+        b->q_cap = cap;
+    }
+    const dim3 grid((unsigned)((n + 255) / 256));
+    const uint8_t *text = b->w.win->d;
+    CN_HIP(h, hipMemsetAsync(b->d_qsum, 0, (size_t)n * 8, h->stream));
+    CN_HIP(h, hipMemsetAsync(b->w.d_sm + SM_Q_N, 0, 2 * 8, h->stream));
+    CN_LAUNCH(h, "bamfq_qrange", bamfq_qrange<<<grid, dim3(256), 0, h->stream>>>(text, b->w.d_recoff, b->d_size, n, b->d_qstart, b->d_qlen));
+    CN_TRY(cn_qmean_sum(h, text, n_text, b->d_qstart, b->d_qlen, n, 1, b->d_qsum));
+    CN_LAUNCH(h, "bamfq_qkeep", bamfq_qkeep<<<grid, dim3(256), 0, h->stream>>>(text, b->w.d_recoff, b->d_size, n, b->d_qsum, b->max_err, b->d_recs, b->w.d_sm));
+    return CORNETTO_OK;
+}
+
 // the records of window bytes [0, n_text): frame, size, scan; the tail stays where it is until the gets are through
 int fq_window(cornetto_accel_t *h, cornetto_bamfq_t *b, int64_t n_text, int64_t *n_out)
 {
@@ -242,6 +325,7 @@ int fq_window(cornetto_accel_t *h, cornetto_bamfq_t *b, int64_t n_text, int64_t 
     }
     int64_t text = 0;
     if (n_ok > 0) {
+        if (b->max_err >= 0) CN_TRY(fq_qmean(h, b, n_ok, n_text));
         CN_TRY(cnscan::exclusive_u32(h, "bamfq_scan", b->d_size, n_ok, 1, b->d_out, b->w.d_sm + SM_TEXT));
         CN_HIP(h, hipMemcpyAsync(b->d_out + n_ok, b->w.d_sm + SM_TEXT, 4, hipMemcpyDeviceToDevice, h->stream));      // out[n]: the text's length (below 2^32)
         CN_HIP(h, hipMemcpyAsync(p_sm + SM_TOTAL_N, b->w.d_sm + SM_TOTAL_N, 5 * 8, hipMemcpyDeviceToHost, h->stream));
@@ -249,6 +333,17 @@ int fq_window(cornetto_accel_t *h, cornetto_bamfq_t *b, int64_t n_text, int64_t 
         text = (int64_t)p_sm[SM_TEXT];
         if (text < 0 || text > 0xFFFFFFFFll) return cn_fail(h, CORNETTO_E_HIP, "bamfq_feed: a window's text of %lld bytes", (long long)text);
         for (int k = 0; k < 4; ++k) b->stats[k] += (int64_t)p_sm[SM_TOTAL_N + k];
+        if (b->max_err >= 0) {
+            CN_HIP(h, hipMemcpyAsync(p_sm + SM_Q_N, b->w.d_sm + SM_Q_N, 2 * 8, hipMemcpyDeviceToHost, h->stream));
+            if (b->d_recs) {
+                const size_t at = b->qsums.size();
+                b->qsums.resize(at + (size_t)n_ok);
+                CN_HIP(h, hipMemcpyAsync(b->qsums.data() + at, b->d_qsum, (size_t)n_ok * 8, hipMemcpyDeviceToHost, h->stream));
+            }
+            CN_HIP(h, hipStreamSynchronize(h->stream));
+            b->qstats[0] += (int64_t)p_sm[SM_Q_N];
+            b->qstats[1] += (int64_t)p_sm[SM_Q_B];
+        }
         if (b->d_recs) {
             const size_t at = b->recs.size();
             b->recs.resize(at + (size_t)n_ok);
@@ -303,7 +398,7 @@ void cornetto_bamfq_close(cornetto_accel_t *h, cornetto_bamfq_t *b)
     if (b->d_ztot) (void)hipFree(b->d_ztot);
     if (b->p_ztot) (void)hipHostFree(b->p_ztot);
     cnbw::win_close(h, b->w);
-    void *blocks[] = {b->d_size, b->d_out, b->d_recs};
+    void *blocks[] = {b->d_size, b->d_out, b->d_recs, b->d_qstart, b->d_qlen, b->d_qsum};
     for (void *p : blocks)
         if (p) (void)hipFree(p);
     delete b;
@@ -339,6 +434,32 @@ int cornetto_bamfq_open(cornetto_accel_t *h, const cornetto_bamfq_opt_t *opt, co
 
 const cornetto_bamerr_t *cornetto_bamfq_error(const cornetto_bamfq_t *b) { return b ? &b->err : nullptr; }
 
+int cornetto_bamfq_set_max_err(cornetto_accel_t *h, cornetto_bamfq_t *b, int64_t P)
+{
+    if (!h || !b || b->fed || P < -1 || P > CORNETTO_QUAL_ONE) return cn_fail(h, CORNETTO_E_ARG, "bamfq_set_max_err: -1 or 0 .. 10^9, before the first feed");
+    b->max_err = P;
+    return CORNETTO_OK;
+}
+
+void cornetto_bamfq_qstats(const cornetto_bamfq_t *b, int64_t *qstats)
+{
+    if (!b || !qstats) return;
+    for (int k = 0; k < 2; ++k) qstats[k] = b->max_err >= 0 ? b->qstats[k] : b->stats[2 + k];
+}
+
+int cornetto_bamfq_qsums(cornetto_accel_t *h, cornetto_bamfq_t *b, uint64_t **sums, int64_t *n_sums)
+{
+    if (!h || !b || !sums || !n_sums) return cn_fail(h, CORNETTO_E_ARG, "bamfq_qsums: bad argument");
+    if (!b->opt.records || b->max_err < 0) return cn_fail(h, CORNETTO_E_ARG, "bamfq_qsums: the object keeps no sums (opt.records, cornetto_bamfq_set_max_err)");
+    *sums = nullptr;
+    *n_sums = (int64_t)b->qsums.size();
+    if (b->qsums.empty()) return CORNETTO_OK;
+    *sums = (uint64_t *)cn_result_alloc(b->qsums.size() * 8);
+    if (!*sums) return cn_fail(h, CORNETTO_E_NOMEM, "bamfq_qsums: host allocation failed");
+    memcpy(*sums, b->qsums.data(), b->qsums.size() * 8);
+    return CORNETTO_OK;
+}
+
 void cornetto_bamfq_stats(const cornetto_bamfq_t *b, int64_t *stats)
 {
     if (!b || !stats) return;
@@ -353,6 +474,7 @@ int cornetto_bamfq_feed(cornetto_accel_t *h, cornetto_bamfq_t *b, cornetto_text_
     *taken = 0;
     *n_text = 0;
     if (b->err.kind) return CORNETTO_E_FORMAT;
+    b->fed = true;
     for (int64_t i = 0; i < n_blocks; ++i)
         if (blocks[i].n_dst < 0 || blocks[i].n_dst > 65536) return cn_fail(h, CORNETTO_E_ARG, "bamfq_feed: block %lld has no BGZF size", (long long)i);
     CN_HIP(h, hipSetDevice(h->device));

@@ -6,6 +6,11 @@
 //                 is not a plain record
 //   fqseq_zero    the first byte 0 of the window (16 bytes per thread); fqseq_fold: its record joins "the first group that is not plain" — the
 //                 reference prints with printf("%s"), so a record with a byte 0 is the sequential reader's
+//   with cornetto_fqseq_set_max_err() (`seq -q`; nothing of it runs or is allocated otherwise)
+//     fqseq_qrange  a thread per record: its quality line as a range of qmean_sum, of length 0 where -m has dropped it
+//     qmean_sum     (qmean.hip) the sums of quality weights, into a table the window zeroes itself
+//     fqseq_qkeep   a thread per record: sum > P * len clears `keep`; the reads and bases that stay are counted, the ones that go are added
+//                   to the counts of `reads >= min_len` here, since fqseq_size below counts what is still kept
 //   fqseq_size    a thread per record: the bytes of its text (0: dropped by -m), the counts of the two summary lines (a 64-bit atomic per wave)
 //   fqseq_scan    the exclusive scan of the sizes (the look-back of scan.hpp): every record's offset in the window's text
 // and per get of bytes [at, at + n) of that text
@@ -34,7 +39,7 @@ constexpr int64_t FX_TILE = (int64_t)FX_THREADS * 16 * FX_PER_THREAD;     // 16 
 static_assert(FX_TILE == CORNETTO_FQSEQ_TILE, "the tile the tests plant their seams at");
 
 // words of the small device block
-enum { SM_BAD = 0 /* u32 first group not plain, u32 first byte 0 */, SM_TOTAL_N = 1, SM_TOTAL_B = 2, SM_KEPT_N = 3, SM_KEPT_B = 4, SM_TEXT = 5, SM_WORDS = 8 };
+enum { SM_BAD = 0 /* u32 first group not plain, u32 first byte 0 */, SM_TOTAL_N = 1, SM_TOTAL_B = 2, SM_KEPT_N = 3, SM_KEPT_B = 4, SM_TEXT = 5, SM_Q_N = 6, SM_Q_B = 7, SM_WORDS = 8 };
 
 __global__ void __launch_bounds__(cnmarks::MK_THREADS) fqseq_zero(const uint8_t *__restrict__ text, int64_t n, uint32_t *first_zero)
 {
@@ -94,6 +99,47 @@ __global__ void __launch_bounds__(256) fqseq_size(const cornetto_fqrec_t *__rest
     }
 }
 
+__global__ void __launch_bounds__(256) fqseq_qrange(const cornetto_fqrec_t *__restrict__ recs, int64_t n_rec, uint32_t *__restrict__ start, uint32_t *__restrict__ len)
+{
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= n_rec) return;
+    const cornetto_fqrec_t x = recs[r];
+    start[r] = (uint32_t)x.qual;
+    len[r] = x.keep ? (uint32_t)x.len : 0u;
+}
+
+__global__ void __launch_bounds__(256) fqseq_qkeep(cornetto_fqrec_t *__restrict__ recs, int64_t n_rec, const unsigned long long *__restrict__ sum, int64_t max_err,
+                                                   unsigned long long *sm)
+{
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    unsigned long long dn = 0, db = 0, pn = 0, pb = 0;
+    if (r < n_rec && recs[r].keep) {
+        const unsigned long long len = (unsigned long long)recs[r].len;
+        if (sum[r] > (unsigned long long)max_err * len) {
+            recs[r].keep = 0;
+            dn = 1;
+            db = len;
+        } else {
+            pn = 1;
+            pb = len;
+        }
+    }
+    dn = fx_wave_sum(dn);
+    db = fx_wave_sum(db);
+    pn = fx_wave_sum(pn);
+    pb = fx_wave_sum(pb);
+    if ((threadIdx.x & 63) == 0) {
+        if (dn) {
+            atomicAdd(sm + SM_KEPT_N, dn);
+            atomicAdd(sm + SM_KEPT_B, db);
+        }
+        if (pn) {
+            atomicAdd(sm + SM_Q_N, pn);
+            atomicAdd(sm + SM_Q_B, pb);
+        }
+    }
+}
+
 __global__ void __launch_bounds__(FX_THREADS) fqseq_text(FxArgs A)
 {
     const int64_t tile = (int64_t)blockIdx.x * FX_TILE;
@@ -121,6 +167,13 @@ struct cornetto_fqseq {
     uint32_t *d_size = nullptr, *d_out = nullptr;      // [rec_cap], [rec_cap + 1]
     int64_t rec_cap = 0;
     unsigned long long *d_sm = nullptr;
+    // cornetto_fqseq_set_max_err(): the ranges and sums of qmean_sum ([rec_cap] each, allocated with the tables), what passed, the sums kept
+    int64_t max_err = -1;
+    bool fed = false;
+    uint32_t *d_qstart = nullptr, *d_qlen = nullptr;
+    unsigned long long *d_qsum = nullptr;
+    int64_t qstats[2] = {0, 0};
+    std::vector<uint64_t> qsums;
     int64_t carry = 0, text_off = 0;                   // bytes at the front of the window from the last one; the stream offset of the window's first byte
     int64_t n_cur = 0, text_cur = 0;                   // the window the gets read: records with offsets, bytes of text
     int64_t pend_text = -1, pend_end = 0;              // the tail of that window is moved when its gets are through: at the next feed
@@ -202,16 +255,20 @@ int fx_settle(cornetto_accel_t *h, cornetto_fqseq_t *b)
 int fx_tables(cornetto_accel_t *h, cornetto_fqseq_t *b, int64_t n)
 {
     if (n <= b->rec_cap) return CORNETTO_OK;
-    void *old[] = {b->d_recs, b->d_size, b->d_out};
+    void *old[] = {b->d_recs, b->d_size, b->d_out, b->d_qstart, b->d_qlen, b->d_qsum};
     for (void *p : old)
         if (p) (void)hipFree(p);
     b->d_recs = nullptr;
-    b->d_size = b->d_out = nullptr;
+    b->d_size = b->d_out = b->d_qstart = b->d_qlen = nullptr;
+    b->d_qsum = nullptr;
     b->rec_cap = 0;
     const int64_t cap = n + n / 8 + 1024;
     if (hipMalloc((void **)&b->d_recs, (size_t)cap * sizeof(cornetto_fqrec_t)) != hipSuccess || hipMalloc((void **)&b->d_size, (size_t)cap * 4) != hipSuccess ||
         hipMalloc((void **)&b->d_out, ((size_t)cap + 1) * 4) != hipSuccess)
         return cn_fail(h, CORNETTO_E_NOMEM, "fqseq_feed: device allocation of the tables of %lld records failed", (long long)cap);
+    if (b->max_err >= 0 && (hipMalloc((void **)&b->d_qstart, (size_t)cap * 4) != hipSuccess || hipMalloc((void **)&b->d_qlen, (size_t)cap * 4) != hipSuccess ||
+                            hipMalloc((void **)&b->d_qsum, (size_t)cap * 8) != hipSuccess))
+        return cn_fail(h, CORNETTO_E_NOMEM, "fqseq_feed: device allocation of the quality sums of %lld records failed", (long long)cap);
     b->rec_cap = cap;
     return CORNETTO_OK;
 }
@@ -254,15 +311,32 @@ int fx_window(cornetto_accel_t *h, cornetto_fqseq_t *b, int64_t n, bool final, i
         if (n_use > 0) {
             uint32_t *p_end = reinterpret_cast<uint32_t *>(p_sm + 8);
             CN_HIP(h, hipMemcpyAsync(p_end, d_ends + (n_use - 1), 4, hipMemcpyDeviceToHost, h->stream));
+            if (b->max_err >= 0) {      // the sums of this window's records alone: the table is zeroed here, whatever it held
+                const dim3 grid((unsigned)((n_use + 255) / 256));
+                CN_HIP(h, hipMemsetAsync(b->d_qsum, 0, (size_t)n_use * 8, h->stream));
+                CN_LAUNCH(h, "fqseq_qrange", fqseq_qrange<<<grid, dim3(256), 0, h->stream>>>(b->d_recs, n_use, b->d_qstart, b->d_qlen));
+                CN_TRY(cn_qmean_sum(h, b->d_win, n, b->d_qstart, b->d_qlen, n_use, 0, b->d_qsum));
+                CN_LAUNCH(h, "fqseq_qkeep", fqseq_qkeep<<<grid, dim3(256), 0, h->stream>>>(b->d_recs, n_use, b->d_qsum, b->max_err, b->d_sm));
+            }
             CN_LAUNCH(h, "fqseq_size", fqseq_size<<<dim3((unsigned)((n_use + 255) / 256)), dim3(256), 0, h->stream>>>(b->d_recs, n_use, b->d_size, b->d_sm));
             CN_TRY(cnscan::exclusive_u32(h, "fqseq_scan", b->d_size, n_use, 1, b->d_out, b->d_sm + SM_TEXT));
             CN_HIP(h, hipMemcpyAsync(b->d_out + n_use, b->d_sm + SM_TEXT, 4, hipMemcpyDeviceToDevice, h->stream));      // out[n]: the text's length (below 2^32)
-            CN_HIP(h, hipMemcpyAsync(p_sm + SM_TOTAL_N, b->d_sm + SM_TOTAL_N, 5 * 8, hipMemcpyDeviceToHost, h->stream));
+            CN_HIP(h, hipMemcpyAsync(p_sm + SM_TOTAL_N, b->d_sm + SM_TOTAL_N, (b->max_err >= 0 ? 7 : 5) * 8, hipMemcpyDeviceToHost, h->stream));
             CN_HIP(h, hipStreamSynchronize(h->stream));
             end = (int64_t)p_end[0];
             text = (int64_t)p_sm[SM_TEXT];
             if (end < 1 || end > n || text < 0 || text > 0xFFFFFFFFll) return cn_fail(h, CORNETTO_E_HIP, "fqseq_feed: a window's text of %lld bytes, its records end at %lld", (long long)text, (long long)end);
             for (int k = 0; k < 4; ++k) b->stats[k] += (int64_t)p_sm[SM_TOTAL_N + k];
+            if (b->max_err >= 0) {
+                b->qstats[0] += (int64_t)p_sm[SM_Q_N];
+                b->qstats[1] += (int64_t)p_sm[SM_Q_B];
+            }
+            if (b->opt.records && b->max_err >= 0) {
+                const size_t at = b->qsums.size();
+                b->qsums.resize(at + (size_t)n_use);
+                CN_HIP(h, hipMemcpyAsync(b->qsums.data() + at, b->d_qsum, (size_t)n_use * 8, hipMemcpyDeviceToHost, h->stream));
+                CN_HIP(h, hipStreamSynchronize(h->stream));
+            }
             if (b->opt.records) {
                 const size_t at = b->recs.size();
                 b->recs.resize(at + (size_t)n_use);
@@ -318,7 +392,7 @@ void cornetto_fqseq_close(cornetto_accel_t *h, cornetto_fqseq_t *b)
     }
     if (b->d_ztot) (void)hipFree(b->d_ztot);
     if (b->p_ztot) (void)hipHostFree(b->p_ztot);
-    void *blocks[] = {b->d_win, b->d_tail, b->d_recs, b->d_size, b->d_out, b->d_sm};
+    void *blocks[] = {b->d_win, b->d_tail, b->d_recs, b->d_size, b->d_out, b->d_sm, b->d_qstart, b->d_qlen, b->d_qsum};
     for (void *p : blocks)
         if (p) (void)hipFree(p);
     delete b;
@@ -344,6 +418,32 @@ int cornetto_fqseq_open(cornetto_accel_t *h, const cornetto_fqseq_opt_t *opt, co
     return CORNETTO_OK;
 }
 
+int cornetto_fqseq_set_max_err(cornetto_accel_t *h, cornetto_fqseq_t *b, int64_t P)
+{
+    if (!h || !b || b->fed || P < -1 || P > CORNETTO_QUAL_ONE) return cn_fail(h, CORNETTO_E_ARG, "fqseq_set_max_err: -1 or 0 .. 10^9, before the first feed");
+    b->max_err = P;
+    return CORNETTO_OK;
+}
+
+void cornetto_fqseq_qstats(const cornetto_fqseq_t *b, int64_t *qstats)
+{
+    if (!b || !qstats) return;
+    for (int k = 0; k < 2; ++k) qstats[k] = b->max_err >= 0 ? b->qstats[k] : b->stats[2 + k];
+}
+
+int cornetto_fqseq_qsums(cornetto_accel_t *h, cornetto_fqseq_t *b, uint64_t **sums, int64_t *n_sums)
+{
+    if (!h || !b || !sums || !n_sums) return cn_fail(h, CORNETTO_E_ARG, "fqseq_qsums: bad argument");
+    if (!b->opt.records || b->max_err < 0) return cn_fail(h, CORNETTO_E_ARG, "fqseq_qsums: the object keeps no sums (opt.records, cornetto_fqseq_set_max_err)");
+    *sums = nullptr;
+    *n_sums = (int64_t)b->qsums.size();
+    if (b->qsums.empty()) return CORNETTO_OK;
+    *sums = (uint64_t *)cn_result_alloc(b->qsums.size() * 8);
+    if (!*sums) return cn_fail(h, CORNETTO_E_NOMEM, "fqseq_qsums: host allocation failed");
+    memcpy(*sums, b->qsums.data(), b->qsums.size() * 8);
+    return CORNETTO_OK;
+}
+
 int64_t cornetto_fqseq_error(const cornetto_fqseq_t *b) { return b ? b->err_block : -1; }
 
 int64_t cornetto_fqseq_rest(const cornetto_fqseq_t *b) { return b ? b->rest : 0; }
@@ -365,6 +465,7 @@ int cornetto_fqseq_feed(cornetto_accel_t *h, cornetto_fqseq_t *b, const cornetto
     if (!bgsrc_size(src, &n_new)) return cn_fail(h, CORNETTO_E_ARG, "fqseq_feed: bad source");
     if (b->err_block >= 0) return CORNETTO_E_FORMAT;
     if (b->stopped) return cn_fail(h, CORNETTO_E_ARG, "fqseq_feed: the device's part of the text has ended (cornetto_fqseq_rest)");
+    b->fed = true;
     CN_HIP(h, hipSetDevice(h->device));
     CN_TRY(fx_settle(h, b));
     const bool comp = bgsrc_compressed(src);

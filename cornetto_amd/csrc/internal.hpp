@@ -67,5 +67,9 @@ int cn_bgzf_inflate_raw(cornetto_accel_t *h, const uint8_t *d_comp, uint8_t *d_o
 // d_out on (room for 65536 bytes a member), the chain's length to the device word *d_total.  Queued on the handle's stream: nothing is waited for,
 // staging and sizes live in the handle's workspaces (calls follow each other on that stream).
 int cn_bgzf_deflate_queue(cornetto_accel_t *h, const uint8_t *d_src, int64_t n, uint8_t *d_out, unsigned long long *d_total);
+// qmean_sum (qmean.hip) queued on the handle's stream: d_sum[r] += the weights of the bytes d_text[d_start[r] .. + d_len[r]) for r < n, out of
+// the table of printed FASTQ characters (bam == 0) or of raw BAM qualities.  The ranges ascend and do not overlap; the caller has zeroed d_sum
+// on the same stream; d_text is readable to the next multiple of 16 behind n_text.  Nothing is waited for.
+int cn_qmean_sum(cornetto_accel_t *h, const uint8_t *d_text, int64_t n_text, const uint32_t *d_start, const uint32_t *d_len, int64_t n, int bam, unsigned long long *d_sum);
 int cn_sdust_list_impl(cornetto_accel_t *h, const cornetto_asm_t *a, int32_t T, int32_t W, const cornetto_ivl_t **d_ivls, int64_t *n_ivls);
 int cn_telo_hits_impl(cornetto_accel_t *h, const cornetto_asm_t *a, const char *motif, const cornetto_hit_t **d_hits, int64_t *n_hits);

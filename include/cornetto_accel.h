@@ -789,6 +789,57 @@ int cornetto_fqseq_records(cornetto_accel_t *h, cornetto_fqseq_t *q, cornetto_fq
 int cornetto_fqseq_text_time(cornetto_accel_t *h, cornetto_fqseq_t *q, double *ms, int64_t *n_bytes);
 
 /* ---------------------------------------------------------------------------------------------------
+ * The mean-quality filter of `seq -q` (not in the reference), for cornetto_fqseq_* and cornetto_bamfq_* and every host loop.  THE RULE:
+ *   - weights: E[q] = round(10^9 * 10^(-q/10)) for q = 0 .. 93, the literal table below (no entry is a rounding tie: 10^(-q/10) is irrational
+ *     unless q is a multiple of 10, and then the value is an integer);
+ *   - a character c of a printed FASTQ quality line has q = clamp(c - 33, 0, 93): bytes below '!' give 0, bytes above '~' give 93;
+ *   - with S = the sum of E[q] over the PRINTED quality characters and L = the number of printed bases, a read passes iff S <= P * L.
+ *     P, an integer in [0, 10^9], is the largest mean error probability allowed in units of 10^-9; L < 2^31, so both sides fit 64 bits.
+ *     64-bit integers only, no floating point on any path; the sum does not depend on the order, so device, host and tests agree bit for bit;
+ *   - a read is printed iff it passes the length filter, and --duplex where given, and this.  L = 0 passes; a record printed with an empty
+ *     quality line (a FASTA record through `seq FILE`) passes;
+ *   - BAM: the characters are the ones `seq --bam` prints: q = min(raw, 93); absent qualities (first byte 0xFF) print as '"' each, so
+ *     S = l_seq * E[1]; reversing the qualities does not change the sum.  `seq --bam F -q T` prints what
+ *     `seq --bam F -m .. | seq --fastq - -m 0 -q T` prints.
+ * NOT replicated: dorado's --min-qscore skips the first 60 bases and has its qs tag; neither is copied.  Parity with dorado, chopper or
+ * samtools is unpinned, like every other extension here.
+ * On the device (qmean_sum, csrc/qmean.hpp): a wave owns 1 KiB of the window, finds the quality ranges that reach into it and adds every
+ * range's weights to its 64-bit sum; a pass per record then clears the keep decision where S > P * L, in front of the size scan.
+ * ------------------------------------------------------------------------------------------------- */
+#define CORNETTO_QUAL_MAX 93
+#define CORNETTO_QUAL_ONE 1000000000ll /* E[0]: the unit of P */
+#define CORNETTO_QUAL_WEIGHTS                                                                                   \
+    {                                                                                                           \
+        1000000000u, 794328235u, 630957344u, 501187234u, 398107171u, 316227766u, 251188643u, 199526231u,        \
+        158489319u, 125892541u, 100000000u, 79432823u, 63095734u, 50118723u, 39810717u, 31622777u,              \
+        25118864u, 19952623u, 15848932u, 12589254u, 10000000u, 7943282u, 6309573u, 5011872u,                    \
+        3981072u, 3162278u, 2511886u, 1995262u, 1584893u, 1258925u, 1000000u, 794328u,                          \
+        630957u, 501187u, 398107u, 316228u, 251189u, 199526u, 158489u, 125893u,                                 \
+        100000u, 79433u, 63096u, 50119u, 39811u, 31623u, 25119u, 19953u,                                        \
+        15849u, 12589u, 10000u, 7943u, 6310u, 5012u, 3981u, 3162u,                                              \
+        2512u, 1995u, 1585u, 1259u, 1000u, 794u, 631u, 501u,                                                    \
+        398u, 316u, 251u, 200u, 158u, 126u, 100u, 79u,                                                          \
+        63u, 50u, 40u, 32u, 25u, 20u, 16u, 13u,                                                                 \
+        10u, 8u, 6u, 5u, 4u, 3u, 3u, 2u,                                                                        \
+        2u, 1u, 1u, 1u, 1u, 1u                                                                                  \
+    }
+/* E[clamp(q, 0, 93)] */
+uint32_t cornetto_qual_weight(int q);
+/* Between open and the first feed: P = -1 turns the filter off (the default: nothing of it is launched or allocated), 0 .. 10^9 sets it.
+ * CORNETTO_E_ARG after a feed or out of range. */
+int cornetto_fqseq_set_max_err(cornetto_accel_t *h, cornetto_fqseq_t *q, int64_t P);
+int cornetto_bamfq_set_max_err(cornetto_accel_t *h, cornetto_bamfq_t *b, int64_t P);
+/* qstats[0 .. 2): reads and bases printed, over the feeds so far (with the filter off: those of `reads >= min_len`).  With the filter on
+ * the `keep` / `kept` column of the record tables is 1 exactly for the printed records; the counts of cornetto_*_stats() keep their
+ * meaning (length, and dx for a BAM). */
+void cornetto_fqseq_qstats(const cornetto_fqseq_t *q, int64_t *qstats);
+void cornetto_bamfq_qstats(const cornetto_bamfq_t *b, int64_t *qstats);
+/* The sums S of the feeds so far, a uint64_t per record in the order of the record table (opt.records and the filter on; CORNETTO_E_ARG
+ * otherwise); a record dropped before the sum (length, dx, passed over) reports 0: cornetto_free(). */
+int cornetto_fqseq_qsums(cornetto_accel_t *h, cornetto_fqseq_t *q, uint64_t **sums, int64_t *n_sums);
+int cornetto_bamfq_qsums(cornetto_accel_t *h, cornetto_bamfq_t *b, uint64_t **sums, int64_t *n_sums);
+
+/* ---------------------------------------------------------------------------------------------------
  * fixasm output text: the records of a resident assembly, renamed and reoriented
  * ------------------------------------------------------------------------------------------------- */
 

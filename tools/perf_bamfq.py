@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """development aid: `seq --bam` on a synthetic unaligned BAM of long reads — --mb million bytes of records, reads of about --read bases with
-bases and qualities drawn at random (they do not compress: the decoder's worst case), a dx:i:1 tag on a share of them,
+bases and qualities drawn at random (they do not compress: the decoder's worst case; the qualities of three reads in ten
+are halved, so that `-q 10` drops a visible share), a dx:i:1 tag on a share of them,
 half of them on the reverse strand, BGZF blocks of 65280 bytes (zlib level 1) — on the device and under --accel=no, against `seq -m N` on the
 FASTQ text of the same reads (written here too: what a user has today once something else has made the text), with the parent commit's
 binary (`_old/cornetto` beside `_old/libcornetto_hip.so`) when it is there and this build's otherwise — the code of that path is the same.
    python tools/perf_bamfq.py --dir /tmp/bamfq [--mb 500] [--runs 5] [--old _old/cornetto] [--kernels] [--sweep 64,256,1024]
-prints: the stdout of the commands is the same; wall times of the process, alternating runs, files in the page cache; with --kernels the event
-times of one pass through the binding (bgzf_inflate, bgzf_crc32, bam_frame, bamfq_size, bamfq_scan, bamfq_text); with --sweep the wall time over
+prints: the stdout of the commands is the same; wall times of the process, alternating runs, files in the page cache; then `seq --bam` on the device
+without and with -q 10, alternating, with --accel=no -q 10 and this build's seq -q 10 on the FASTQ text, whose text must be the same; with --kernels
+the event times of one pass through the binding (bgzf_inflate, bgzf_crc32, bam_frame, bamfq_size, bamfq_scan, bamfq_text) without and with the filter,
+and qmean_sum's time over the bytes of its windows and over the quality bytes it sums; with --sweep the wall time over
 $CORNETTO_BAM_WINDOW (MiB).  `samtools fastq` is timed if it is on the box; nothing depends on it."""
 import argparse
 import os
@@ -46,12 +49,15 @@ def synthesize(d, mb, read_len, duplex_share, seed):
     if all(os.path.exists(p) for p in paths):
         return paths
     rng = np.random.default_rng(seed)
+    low = np.random.default_rng(seed + 1)          # (a generator of its own: lengths, bases and tags are those of the files without -q)
     parts, n_reads, n_bytes = [b"BAM\1" + struct.pack("<ii", 0, 0)], 0, 0
     with open(paths[1], "wb") as f_all, open(paths[2], "wb") as f_dx:
         while n_bytes < mb * 1_000_000:
             l_seq = int(max(200, rng.normal(read_len, read_len / 3)))
             nib = (1 << rng.integers(0, 4, l_seq + (l_seq & 1))).astype(np.uint8)
-            qual = rng.integers(0, 51, l_seq).astype(np.uint8)
+            qual = rng.integers(0, 51, l_seq).astype(np.uint8)          # a mean error of 0.095: above Q10; halved, 0.18: below it
+            if low.random() < 0.3:
+                qual >>= 1
             rev = bool(rng.random() < 0.5)
             dx = bool(rng.random() < duplex_share)
             name = b"%08x-4c1d-4f7a-9c3e-%012d" % (n_reads * 2654435761 & 0xFFFFFFFF, n_reads)
@@ -139,6 +145,21 @@ def main():
         print("%s, -m %s: stdout %s (%d bytes)" % (label, m, "the same" if len(set(ours)) == 1 else "DIFFERS %r" % (outs,), ours[0][0]), flush=True)
         for k in cmds:
             print("  %-24s %s" % (k, stats(times[k])), flush=True)
+    # -q 10 beside the same command without it, alternating
+    pairs = {"seq --bam, device": [new, "seq", "-m", m, "--bam", bam], "seq --bam, --accel=no": [new, "seq", "-m", m, "--accel=no", "--bam", bam],
+             "seq on the FASTQ text (this build)": [new, "seq", "-m", m, fastq]}
+    tq, outq = {(k, q): [] for k in pairs for q in (0, 1)}, {}
+    for i in range(a.runs + 1):          # (the first round unmeasured)
+        for k, argv in pairs.items():
+            for q in (0, 1):
+                dt, n, crc = wall(argv + (["-q", "10"] if q else []))
+                if i:
+                    tq[(k, q)].append(dt)
+                outq[(k, q)] = (n, crc)
+    same = len(set(outq[(k, 1)] for k in pairs)) == 1
+    print("-m %s -q 10: stdout %s (%d of %d bytes)" % (m, "the same from all three" if same else "DIFFERS %r" % (outq,), outq[("seq --bam, device", 1)][0], outq[("seq --bam, device", 0)][0]), flush=True)
+    for k in pairs:
+        print("  %-36s %s   with -q 10: %s" % (k, stats(tq[(k, 0)]), stats(tq[(k, 1)])), flush=True)
     for mib in [int(x) for x in a.sweep.split(",") if x]:
         ts = [wall([new, "seq", "-m", m, "--bam", bam], {"CORNETTO_BAM_WINDOW": str(mib << 20)})[0] for _ in range(3)]
         print("window %4d MiB: %s" % (mib, stats(ts)), flush=True)
@@ -146,13 +167,18 @@ def main():
         acc = cornetto_amd.Accel(0)
         with open(bam, "rb") as f:
             blob = f.read()
-        for rep in range(2):
-            text, st, _ = acc.bam_fastq(blob, a.min_len, False, window=256 << 20, slab=32 << 20)
-        tm = {}
-        for name, ms in acc.bam_timing:
-            tm.setdefault(name, []).append(ms)
-        print("kernels of one pass (window 256 MiB, slabs of 32 MiB, %d bytes of text): %s" % (
-            len(text), "; ".join("%s %d x, %.2f ms in all, %.2f ms the longest" % (k, len(v), sum(v), max(v)) for k, v in tm.items())), flush=True)
+        for max_err in (None, 10 ** 8):
+            for rep in range(2):
+                text, st, _ = acc.bam_fastq(blob, a.min_len, False, window=256 << 20, slab=32 << 20, max_err=max_err)
+            tm = {}
+            for name, ms in acc.bam_timing:
+                tm.setdefault(name, []).append(ms)
+            print("kernels of one pass%s (window 256 MiB, slabs of 32 MiB, %d bytes of text): %s" % (
+                "" if max_err is None else " with -q 10", len(text), "; ".join("%s %d x, %.2f ms in all, %.2f ms the longest" % (k, len(v), sum(v), max(v)) for k, v in tm.items())), flush=True)
+            if max_err is not None:
+                ms, n_win = sum(tm.get("qmean_sum", [0.0])), a.mb * 1_000_000
+                print("qmean_sum: %d x, %.3f ms over windows of about %d bytes in all: %.0f GB/s of window, %.0f GB/s of the %d quality bytes it sums; %d of %d reads >= %d printed" % (
+                    len(tm.get("qmean_sum", [])), ms, n_win, n_win / ms / 1e6 if ms > 0 else 0, st[3] / ms / 1e6 if ms > 0 else 0, st[3], acc.bam_qstats[0], st[2], a.min_len), flush=True)
         acc.close()
 
 
