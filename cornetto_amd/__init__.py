@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-__all__ = ["lib", "Accel", "bgzf_scan", "bam_header", "BGZF_DT", "BAMREC_DT", "BAMFQREC_DT", "BAM_SCAN_TILE", "FQSEQ_TILE", "FQREC_DT", "Bgzf", "FastqBlockError", "BamFormatError", "AccelError", "HIT_DT", "WIN_DT", "IVL_DT", "TELROW_DT", "HAP_ROW_DT", "khash_str_order", "panel_boring", "REG_DT", "REGREC_DT", "build",
+__all__ = ["lib", "Accel", "bgzf_scan", "bam_header", "BGZF_DT", "BAMREC_DT", "BAMFQREC_DT", "BAM_SCAN_TILE", "FQSEQ_TILE", "KQV_TILE", "Kset", "FQREC_DT", "Bgzf", "FastqBlockError", "BamFormatError", "AccelError", "HIT_DT", "WIN_DT", "IVL_DT", "TELROW_DT", "HAP_ROW_DT", "khash_str_order", "panel_boring", "REG_DT", "REGREC_DT", "build",
            "LIB_PATH", "CLI_PATH"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -88,6 +88,7 @@ class FqSeqOpt(C.Structure):
     _fields_ = [("min_len", C.c_int32), ("records", C.c_int32), ("window", C.c_int64)]
 
 
+KQV_TILE = 4096  # CORNETTO_KQV_TILE: bases per workgroup of kq_insert / kq_query (tests plant seams at its multiples)
 FQSEQ_TILE = 16384  # CORNETTO_FQSEQ_TILE: output bytes per workgroup of fqseq_text (checked against the library when it is loaded)
 BAMFQREC_DT = np.dtype([("offset", "<i8"), ("l_seq", "<i4"), ("flag", "<i4"), ("name_len", "<i4"), ("kept", "<i4")])
 BAMREC_DT = np.dtype([("offset", "<i8"), ("ref_id", "<i4"), ("pos", "<i4"), ("mapq", "<i4"), ("flag", "<i4"), ("counted", "<i4"), ("n_ops", "<i4"), ("span", "<i8"),
@@ -298,6 +299,11 @@ def lib(dev=False):
         "cornetto_fqseq_stats": (None, [vp, C.POINTER(i64)]),
         "cornetto_fqseq_records": (C.c_int, [vp, vp, pp, C.POINTER(i64)]),
         "cornetto_fqseq_text_time": (C.c_int, [vp, vp, C.POINTER(C.c_double), C.POINTER(i64)]),
+        "cornetto_kset_open": (C.c_int, [vp, i32, i64, pp]),
+        "cornetto_kset_add": (C.c_int, [vp, vp, vp]),
+        "cornetto_kset_stats": (None, [vp, C.POINTER(i64)]),
+        "cornetto_kset_query": (C.c_int, [vp, vp, vp, C.POINTER(i64), C.POINTER(i64), pp, C.POINTER(i64)]),
+        "cornetto_kset_free": (None, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError if the library does not export a declared symbol
@@ -392,6 +398,46 @@ class _Resident:
             pass
 
 
+class Kset:
+    """a set of canonical k-mers resident in HBM (cornetto_kset_*): Accel.kset(k, slots)"""
+
+    def __init__(self, acc, ptr, k, slots):
+        self.acc, self.ptr, self.k, self.slots = acc, ptr, k, slots
+
+    def add(self, asm):
+        """the k-mers of every contig of the resident assembly into the set; AccelError with status -4 when the table overflowed"""
+        self.acc._chk(self.acc.L.cornetto_kset_add(self.acc.h, self.ptr, asm.ptr))
+
+    @property
+    def stats(self):
+        """(positions inserted, distinct k-mers, slots)"""
+        st = (C.c_int64 * 3)()
+        self.acc.L.cornetto_kset_stats(self.ptr, st)
+        return tuple(int(x) for x in st)
+
+    def query(self, asm, runs=False):
+        """-> (kmers, missing) int64 per contig of `asm`; with runs also the merged spans of the missing positions (IVL_DT)"""
+        n = len(asm.lens)
+        km, ms = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(n, 1), dtype=np.int64)
+        p, nr = C.c_void_p(), C.c_int64()
+        self.acc._chk(self.acc.L.cornetto_kset_query(self.acc.h, self.ptr, asm.ptr, km.ctypes.data_as(C.POINTER(C.c_int64)), ms.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                     C.byref(p) if runs else None, C.byref(nr) if runs else None))
+        if runs:
+            return km[:n], ms[:n], _take(self.acc.L, p, nr.value, IVL_DT)
+        return km[:n], ms[:n]
+
+    def close(self):
+        if self.ptr is not None:
+            self.acc.L.cornetto_kset_free(self.acc.h, self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Accel:
     """one device + stream; mirrors the handle of include/cornetto_accel.h"""
 
@@ -459,6 +505,12 @@ class Accel:
         out = C.c_void_p()
         self._chk(self.L.cornetto_asm_upload(self.h, ptrs, lens.ctypes.data, n, C.byref(out)))
         return _Resident(self, out, self.L.cornetto_asm_free, lens)
+
+    def kset(self, k=21, slots=1):
+        """an empty k-mer set with `slots` slots of 8 bytes: cornetto_kset_open()"""
+        out = C.c_void_p()
+        self._chk(self.L.cornetto_kset_open(self.h, k, slots, C.byref(out)))
+        return Kset(self, out, k, slots)
 
     def asm_wrap(self, dev_ptr, offsets, lens):
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)

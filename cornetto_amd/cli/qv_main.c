@@ -1,0 +1,355 @@
+/* qv_main.c — `cornetto qv [-k INT] [-t FILE]... [-c FILE] [-b FILE] [--slots INT] [--accel=no] <truth.fa> <asm.fa> [asm2.fa ...]`: the k-mer
+ * consensus quality of assemblies against a truth assembly.  Not in the reference: its protocol (docs/protocol.md:292-303) runs `yak count`
+ * and `yak qv` against the HG002 Q100 assembly for asm-1 .. asm-n, primary and hap1+hap2.  The rule is stated once in include/cornetto_accel.h
+ * (Merqury's QV from the share of an assembly's k-mers that the truth does not hold; yak's histogram error model is not replicated).
+ *
+ * The truth files are read once (stream.c) and every batch of their records goes into one set of canonical k-mers that stays resident in HBM
+ * (cornetto_kset_add); every assembly is then read the same way and probed against it (cornetto_kset_query).  One device handle serves all files.
+ * --accel=no / CORNETTO_ACCEL=no: the same rule on the host, a single-threaded open-addressing set and the sequential reader; the same bytes. */
+#include <errno.h>
+#include <getopt.h>
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include "cli.h"
+
+typedef struct {
+    int k;
+    int64_t slots;
+    /* the truth */
+    int64_t t_recs, t_bases;
+    cornetto_kset_t *set;                 /* device path */
+    uint64_t *tab;                        /* host path: open addressing, linear probing, ~0 = empty */
+    int64_t h_pos, h_distinct;
+    /* the assembly being read */
+    int64_t contigs, bases, kmers, missing;
+    FILE *fc, *fb;
+} qv_t;
+
+static void qv_overflow(const qv_t *Q)
+{
+    CLI_ERROR("the k-mer table of %lld slots overflowed: the truth holds more distinct %d-mers; give a larger table with --slots", (long long)Q->slots, Q->k);
+    exit(EXIT_FAILURE);
+}
+
+/* error and qv as the tables print them (the rule: include/cornetto_accel.h) */
+static void qv_format(int64_t kmers, int64_t missing, int k, char *e_out, char *q_out, size_t cap)
+{
+    if (kmers == 0) {
+        snprintf(e_out, cap, "NA");
+        snprintf(q_out, cap, "NA");
+    } else if (missing == 0) {
+        snprintf(e_out, cap, "0");
+        snprintf(q_out, cap, "inf");
+    } else {
+        const double p = (double)(kmers - missing) / (double)kmers;
+        const double e = 1 - pow(p, 1.0 / k);
+        snprintf(e_out, cap, "%.3e", e);
+        snprintf(q_out, cap, "%.2f", -10 * log10(e));
+    }
+}
+
+static void contig_row(qv_t *Q, const char *name, size_t name_len, int64_t len, int64_t kmers, int64_t missing)
+{
+    Q->contigs++;
+    Q->bases += len;
+    Q->kmers += kmers;
+    Q->missing += missing;
+    if (!Q->fc) return;
+    char e[48], q[48];
+    qv_format(kmers, missing, Q->k, e, q, sizeof(e));
+    fwrite(name, 1, name_len, Q->fc);
+    fprintf(Q->fc, "\t%lld\t%lld\t%lld\t%s\t%s\n", (long long)len, (long long)kmers, (long long)missing, e, q);
+}
+
+static void bed_row(qv_t *Q, const char *name, size_t name_len, int64_t start, int64_t finish)
+{
+    fwrite(name, 1, name_len, Q->fb);
+    fprintf(Q->fb, "\t%lld\t%lld\n", (long long)start, (long long)finish);
+}
+
+/* ---------------------------------------------------------------- the device path */
+static void truth_scan(cornetto_accel_t *h, const cli_recname_t *r, int64_t n, const cornetto_asm_t *a, void *arg)
+{
+    qv_t *Q = (qv_t *)arg;
+    Q->t_recs += n;
+    for (int64_t i = 0; i < n; ++i) Q->t_bases += r[i].len;
+    const int rc = cornetto_kset_add(h, Q->set, a);
+    if (rc == CORNETTO_E_NOMEM) qv_overflow(Q);
+    cli_accel_check(h, rc, "qv: inserting the truth's k-mers");
+}
+
+static void asm_scan(cornetto_accel_t *h, const cli_recname_t *r, int64_t n, const cornetto_asm_t *a, void *arg)
+{
+    qv_t *Q = (qv_t *)arg;
+    int64_t *km = (int64_t *)cli_xmalloc(((size_t)n + 1) * 2 * sizeof(int64_t)), *ms = km + n + 1;
+    cornetto_ivl_t *rows = NULL;
+    int64_t n_rows = 0;
+    cli_accel_check(h, cornetto_kset_query(h, Q->set, a, km, ms, Q->fb ? &rows : NULL, Q->fb ? &n_rows : NULL), "qv: probing the assembly's k-mers");
+    for (int64_t i = 0; i < n; ++i) contig_row(Q, r[i].name, (size_t)r[i].name_len, r[i].len, km[i], ms[i]);
+    for (int64_t i = 0; i < n_rows; ++i) bed_row(Q, r[rows[i].ctg].name, (size_t)r[rows[i].ctg].name_len, rows[i].start, rows[i].finish);
+    cornetto_free(rows);
+    free(km);
+}
+
+/* ---------------------------------------------------------------- the host path: the same rule, one record at a time */
+static inline int base_code(unsigned char c)
+{
+    switch (c) {
+    case 'A': case 'a': return 0;
+    case 'C': case 'c': return 1;
+    case 'G': case 'g': return 2;
+    case 'T': case 't': return 3;
+    default: return 4;
+    }
+}
+
+static inline uint64_t host_mix(uint64_t x)
+{
+    x ^= x >> 33;
+    x *= 0xff51afd7ed558ccdULL;
+    x ^= x >> 33;
+    x *= 0xc4ceb9fe1a85ec53ULL;
+    x ^= x >> 33;
+    return x;
+}
+
+/* 1 new, 0 present, -1 no room */
+static int host_insert(qv_t *Q, uint64_t key)
+{
+    const uint64_t slots = (uint64_t)Q->slots;
+    uint64_t s = host_mix(key) % slots;
+    for (uint64_t step = 0; step < slots; ++step) {
+        if (Q->tab[s] == key) return 0;
+        if (Q->tab[s] == ~(uint64_t)0) {
+            Q->tab[s] = key;
+            return 1;
+        }
+        s = s + 1 == slots ? 0 : s + 1;
+    }
+    return -1;
+}
+
+static int host_has(const qv_t *Q, uint64_t key)
+{
+    const uint64_t slots = (uint64_t)Q->slots;
+    uint64_t s = host_mix(key) % slots;
+    for (uint64_t step = 0; step < slots; ++step) {
+        if (Q->tab[s] == key) return 1;
+        if (Q->tab[s] == ~(uint64_t)0) return 0;
+        s = s + 1 == slots ? 0 : s + 1;
+    }
+    return 0;
+}
+
+/* every position of the record that holds a k-mer: truth != 0 inserts it, else it is counted, looked up and its span joins the rows */
+static void host_record(qv_t *Q, const cli_rec_t *rec, int truth)
+{
+    const int k = Q->k;
+    const uint64_t mask = ((uint64_t)1 << (2 * k)) - 1;
+    const unsigned char *s = (const unsigned char *)rec->seq.s;
+    const int64_t len = (int64_t)rec->seq.l;
+    uint64_t fwd = 0, rc = 0;
+    int valid = 0;
+    int64_t kmers = 0, missing = 0, open_start = -1, open_finish = -1;
+    for (int64_t e = 0; e < len; ++e) {
+        const int c = base_code(s[e]);
+        if (c > 3) {
+            valid = 0;
+            continue;
+        }
+        fwd = ((fwd << 2) | (uint64_t)c) & mask;
+        rc = (rc >> 2) | ((uint64_t)(3 - c) << (2 * (k - 1)));
+        if (valid < k) ++valid;
+        if (valid < k) continue;
+        const uint64_t key = fwd < rc ? fwd : rc;
+        const int64_t pos = e - (k - 1);
+        if (truth) {
+            const int r = host_insert(Q, key);
+            if (r < 0) qv_overflow(Q);
+            Q->h_pos++;
+            Q->h_distinct += r;
+            continue;
+        }
+        ++kmers;
+        if (host_has(Q, key)) continue;
+        ++missing;
+        if (!Q->fb) continue;
+        if (open_start >= 0 && pos <= open_finish) {           /* overlapping or book-ended */
+            open_finish = pos + k;
+        } else {
+            if (open_start >= 0) bed_row(Q, rec->name.s, rec->name.l, open_start, open_finish);
+            open_start = pos;
+            open_finish = pos + k;
+        }
+    }
+    if (truth) {
+        Q->t_recs++;
+        Q->t_bases += len;
+        return;
+    }
+    /* (the table of contigs is written before the rows of later contigs, the rows of a contig in one piece: both files are in file order) */
+    if (open_start >= 0) bed_row(Q, rec->name.s, rec->name.l, open_start, open_finish);
+    contig_row(Q, rec->name.s, rec->name.l, len, kmers, missing);
+}
+
+static void host_file(qv_t *Q, const char *path, int truth)
+{
+    cli_fastx_t *fx = cli_fastx_open(path, 1);
+    cli_rec_t *r;
+    while ((r = cli_fastx_next_checked(fx)) != NULL) host_record(Q, r, truth);
+    cli_fastx_close(fx);
+}
+
+/* ---------------------------------------------------------------- sizing */
+static void sum_lengths(cornetto_accel_t *h, const cli_recname_t *r, int64_t n, const cornetto_asm_t *a, void *arg)
+{
+    (void)h;
+    (void)a;
+    for (int64_t i = 0; i < n; ++i) *(int64_t *)arg += r[i].len;
+}
+
+/* an upper bound of the positions of a truth file: the bytes of a plain regular file, else the sum of the record lengths of one pass over it;
+ * -1: a FIFO or `-`, which can be read only once */
+static int64_t truth_bound(const char *path)
+{
+    struct stat st;
+    if (!strcmp(path, "-")) return -1;
+    if (stat(path, &st) != 0) (void)cli_gz_open(path, 1);      /* the reference's open error; exit 1 */
+    if (!S_ISREG(st.st_mode)) return -1;
+    FILE *fp = cli_fopen_chk(path, "rb");
+    const int c0 = fgetc(fp), c1 = fgetc(fp);
+    fclose(fp);
+    if (!(c0 == 0x1f && c1 == 0x8b)) return (int64_t)st.st_size;
+    int64_t sum = 0;
+    stream_names(path, 1, sum_lengths, &sum);
+    return sum;
+}
+
+static void usage(FILE *fp)
+{
+    fprintf(fp, "Usage: cornetto qv [options] <truth.fasta> <assembly.fasta> [assembly2.fasta ...]\n");
+    fprintf(fp, "k-mer consensus quality of assemblies against a truth assembly: the share of every assembly's k-mers that the truth\n");
+    fprintf(fp, "does not hold, as error rate and QV (Merqury's rule).  FASTA or FASTQ, plain, gzip or BGZF.\n");
+    fprintf(fp, "   -k INT                     k-mer length, odd, 11 to 31 [21]\n");
+    fprintf(fp, "   -t FILE                    a further truth file, e.g. the other haplotype (may be repeated)\n");
+    fprintf(fp, "   -c FILE                    write the per-contig table to FILE (one assembly only)\n");
+    fprintf(fp, "   -b FILE                    write the merged spans of the missing k-mers to FILE as BED (one assembly only)\n");
+    fprintf(fp, "   --slots INT                slots of the k-mer table, 8 bytes each [twice the bases of the truth]\n");
+    fprintf(fp, "   --accel=no                 run on the host\n");
+    fprintf(fp, "   -h                         help\n");
+}
+
+static void usage_fail(const char *msg)
+{
+    CLI_ERROR("%s", msg);
+    usage(stderr);
+    exit(EXIT_FAILURE);
+}
+
+int qv_main(int argc, char *argv[])
+{
+    static const struct option lo[] = {{"help", no_argument, 0, 'h'}, {"slots", required_argument, 0, 1000}, {"accel", required_argument, 0, 1001}, {0, 0, 0, 0}};
+    const char *k_arg = "21", *c_arg = NULL, *b_arg = NULL, *slots_arg = NULL;
+    const char **truth = (const char **)cli_xmalloc(((size_t)argc + 1) * sizeof(char *));
+    int n_truth = 1, c, li = 0;
+    FILE *fp_help = stderr;
+    optind = 1;
+    while ((c = getopt_long(argc, argv, "k:t:c:b:h", lo, &li)) >= 0) {
+        if (c == 'k') k_arg = optarg;
+        else if (c == 't') truth[n_truth++] = optarg;
+        else if (c == 'c') c_arg = optarg;
+        else if (c == 'b') b_arg = optarg;
+        else if (c == 1000) slots_arg = optarg;
+        else if (c == 1001) {
+            if (!strcmp(optarg, "no") || !strcmp(optarg, "n")) cli_host_set(1);
+            else if (!strcmp(optarg, "yes") || !strcmp(optarg, "y")) cli_host_set(0);
+            else usage_fail("option '--accel' only accepts 'yes' or 'no'");
+        } else if (c == 'h') fp_help = stdout;
+        else exit(EXIT_FAILURE);
+    }
+    if (fp_help == stdout) {
+        usage(stdout);
+        exit(EXIT_SUCCESS);
+    }
+    if (argc - optind < 2) {
+        usage(stderr);
+        exit(EXIT_FAILURE);
+    }
+    truth[0] = argv[optind];
+    char **asms = argv + optind + 1;
+    const int n_asm = argc - optind - 1;
+    char *end = NULL;
+    const long long k = strtoll(k_arg, &end, 10);
+    if (*end || end == k_arg || k < 11 || k > 31 || !(k & 1)) usage_fail("-k: k is an odd number from 11 to 31");
+    if ((c_arg || b_arg) && n_asm != 1) usage_fail("-c and -b take one assembly");
+    long long slots = 0;
+    if (slots_arg) {
+        errno = 0;
+        slots = strtoll(slots_arg, &end, 10);
+        if (*end || end == slots_arg || errno || slots < 1) usage_fail("--slots: a number of at least 1");
+    } else {
+        for (int i = 0; i < n_truth; ++i) {
+            const int64_t b = truth_bound(truth[i]);
+            if (b < 0) usage_fail("a truth that is a FIFO or `-` can be read only once: size the table with --slots");
+            slots += 2 * b;
+        }
+        if (slots < 1) slots = 1;
+    }
+
+    qv_t Q;
+    memset(&Q, 0, sizeof(Q));
+    Q.k = (int)k;
+    Q.slots = (int64_t)slots;
+    const int host = cli_host_mode();
+    cornetto_accel_t *h = NULL;
+    int64_t stats[3] = {0, 0, 0};
+    if (host) {
+        Q.tab = (size_t)slots > SIZE_MAX / 8 ? NULL : (uint64_t *)malloc((size_t)slots * 8);
+        if (!Q.tab) {
+            CLI_ERROR("a k-mer table of %lld slots wants %lld bytes: give a smaller one with --slots", slots, slots * 8);
+            exit(EXIT_FAILURE);
+        }
+        memset(Q.tab, 0xFF, (size_t)slots * 8);
+        for (int i = 0; i < n_truth; ++i) host_file(&Q, truth[i], 1);
+        stats[0] = Q.h_pos;
+        stats[1] = Q.h_distinct;
+    } else {
+        h = cli_accel_open();
+        const int rc = cornetto_kset_open(h, Q.k, Q.slots, &Q.set);
+        if (rc == CORNETTO_E_NOMEM) {
+            CLI_ERROR("%s: give a smaller one with --slots", cornetto_accel_last_error(h));
+            exit(EXIT_FAILURE);
+        }
+        cli_accel_check(h, rc, "qv: the k-mer table");
+        for (int i = 0; i < n_truth; ++i) stream_records_on(h, truth[i], 1, truth_scan, &Q);
+        cornetto_kset_stats(Q.set, stats);
+    }
+    fprintf(stderr, "[qv] truth: %lld records, %lld bases, %lld k-mers, %lld distinct, k=%d\n", (long long)Q.t_recs, (long long)Q.t_bases, (long long)stats[0],
+            (long long)stats[1], Q.k);
+
+    Q.fc = c_arg ? cli_fopen_chk(c_arg, "w") : NULL;
+    Q.fb = b_arg ? cli_fopen_chk(b_arg, "w") : NULL;
+    if (Q.fc) fprintf(Q.fc, "#contig\tlength\tkmers\tmissing\terror\tqv\n");
+    printf("#file\tcontigs\tbases\tkmers\tmissing\terror\tqv\n");
+    for (int i = 0; i < n_asm; ++i) {
+        Q.contigs = Q.bases = Q.kmers = Q.missing = 0;
+        if (host) host_file(&Q, asms[i], 0);
+        else stream_records_on(h, asms[i], 1, asm_scan, &Q);
+        char e[48], q[48];
+        qv_format(Q.kmers, Q.missing, Q.k, e, q, sizeof(e));
+        printf("%s\t%lld\t%lld\t%lld\t%lld\t%s\t%s\n", asms[i], (long long)Q.contigs, (long long)Q.bases, (long long)Q.kmers, (long long)Q.missing, e, q);
+        fflush(stdout);
+    }
+    if ((Q.fc && fclose(Q.fc) != 0) || (Q.fb && fclose(Q.fb) != 0)) {
+        CLI_ERROR("%s", "writing the -c / -b file failed");
+        exit(EXIT_FAILURE);
+    }
+    if (Q.set) cornetto_kset_free(h, Q.set);
+    free(Q.tab);
+    free(truth);
+    return EXIT_SUCCESS;
+}

@@ -27,6 +27,7 @@ typedef struct {
     scan_fn scan;
     void *arg;
     int names_only;          /* stream_names(): the framing gets seqs == NULL, the scan a == NULL, the sequential reader uploads nothing */
+    int release;             /* stream_records_on(): what the call allocated is released before it returns, as for stream_names() */
     int warm;                /* CORNETTO_WARM_* for a large assembly, or 0 */
     cornetto_accel_t *h;     /* NULL until the first device call needs it (cli_accel_open_end) */
     int trace;               /* CORNETTO_CLI_TRACE */
@@ -576,7 +577,7 @@ static int stream_bgzf_fasta(stream_t *s, int64_t csize, int64_t *resume, int64_
  * unpinning a 1 GB piece and closing the handle take about 0.1 s. */
 static void stream_release(stream_t *s)
 {
-    if (!s->names_only) return;
+    if (!s->names_only && !s->release) return;
     for (int i = 0; i < s->n_pinned; ++i) cornetto_pinned_free(s->pinned[i]);
     if (s->text) cornetto_text_free(s->h, s->text);
 }
@@ -642,6 +643,13 @@ static void stream_run(stream_t *s, int must_open)
 void stream_records(const char *path, int must_open, scan_fn scan, void *arg, int warm)
 {
     stream_t s = {.path = path, .scan = scan, .arg = arg, .warm = warm};
+    stream_run(&s, must_open);
+}
+
+/* for a sub-command that reads several files (qv): the caller's handle, and what the call allocated goes before it returns */
+void stream_records_on(cornetto_accel_t *h, const char *path, int must_open, scan_fn scan, void *arg)
+{
+    stream_t s = {.path = path, .scan = scan, .arg = arg, .release = 1, .h = h};
     stream_run(&s, must_open);
 }
 

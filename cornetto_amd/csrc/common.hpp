@@ -158,6 +158,7 @@ enum {   // device workspace slots
     WS_SORT, WS_HAP_ROWS, WS_HAP_BLOCKS, WS_HAP_FUN,
     WS_BZ_BLOCKS, WS_BZ_STATUS, WS_BZ_PACK,
     WS_DF_STAGE, WS_DF_SIZE, WS_DF_TOTAL,
+    WS_KQ_CNT, WS_KQ_MAP, WS_KQ_ROWS,
     WS_COUNT
 };
 static_assert(WS_COUNT <= 72, "cornetto_accel::dev has 72 slots");

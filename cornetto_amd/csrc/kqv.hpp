@@ -1,0 +1,177 @@
+// kqv.hpp — the arithmetic of `cornetto qv` (include/cornetto_accel.h states the rule): canonical k-mers of a contig by a rolling update, an
+// open-addressing set of them, and the bitmap of the positions a query misses.  Shared by the kernels of kqv.hip and, as a CPU program under the
+// host sanitizers, by tools/sim/kqv_sim.cc (tests/test_kqv_host.py), so everything here is a host/device function over plain pointers.
+//   kq_code()     a byte's base code 0..3, or 4 for every other byte;
+//   kq_roll()     one base into {fwd, rc, valid}: fwd and rc are the 2k-bit codes of the last k bases and of their reverse complement (first
+//                 base most significant), valid counts the valid bases behind the position, capped at k; an invalid byte sets it to 0;
+//   kq_run()      the decomposition: a contig is cut into tiles of KQ_TILE bases, thread `tid` of a tile owns the KQ_RUN consecutive bases
+//                 [b0, b1) and with them the k-mers that END there (position e - k + 1 for base e).  It rolls the k - 1 bases in front of b0
+//                 in first — the first run of a contig has nothing in front — and calls f(position, canonical k-mer) for every owned base
+//                 with valid == k.  It reads seq[max(b0 - k + 1, 0) .. b1), b1 <= len: never a byte outside the contig;
+//   kq_home()     the home slot mulhi64(mix(key), slots): slots need not be a power of two;
+//   kq_insert()   linear probing from the home slot through cas(slot, EMPTY, key) -> the old value: done when that is EMPTY (new) or the key
+//                 itself; at most `slots` steps, then KQ_FULL.  `stop()` lets the lanes of a kernel leave once one of them has overflowed;
+//   kq_lookup()   the same walk with plain loads; a key is missing at the first EMPTY slot or after `slots` steps;
+//   kq_bit()      word and mask of position `pos` of a contig whose first tile is `tile0` in the bitmap (KQ_TILE bits per tile).
+// The empty slot is ~0: no key, k <= 31 makes every key smaller than 2^62.
+#pragma once
+#include <cstdint>
+
+#include "../../include/cornetto_accel.h"
+
+#ifdef __HIPCC__
+#define KQ_HD __host__ __device__
+#else
+#define KQ_HD
+#endif
+
+namespace {   // internal linkage: every translation unit that includes this gets its own copy
+
+constexpr int KQ_THREADS = 256;                        // threads per workgroup = per tile
+constexpr int KQ_RUN = CORNETTO_KQV_TILE / KQ_THREADS; // consecutive bases per thread
+constexpr int KQ_TILE = CORNETTO_KQV_TILE;
+static_assert(KQ_RUN * KQ_THREADS == KQ_TILE && KQ_TILE % 64 == 0, "a tile is whole runs and whole bitmap words");
+constexpr uint64_t KQ_EMPTY = ~(uint64_t)0;
+constexpr int KQ_NEW = 1, KQ_PRESENT = 0, KQ_FULL = -1;
+
+KQ_HD static inline bool kq_k_ok(int k) { return k >= 11 && k <= 31 && (k & 1); }
+
+KQ_HD static inline int kq_code(uint8_t b)
+{
+    switch (b) {
+    case 'A': case 'a': return 0;
+    case 'C': case 'c': return 1;
+    case 'G': case 'g': return 2;
+    case 'T': case 't': return 3;
+    default: return 4;
+    }
+}
+
+struct KqRoll {
+    uint64_t fwd, rc;
+    int valid;
+};
+
+KQ_HD static inline void kq_roll(KqRoll &s, int code, int k)
+{
+    if (code > 3) {
+        s.valid = 0;
+        return;
+    }
+    const uint64_t mask = ((uint64_t)1 << (2 * k)) - 1;
+    s.fwd = ((s.fwd << 2) | (uint64_t)code) & mask;
+    s.rc = (s.rc >> 2) | ((uint64_t)(3 - code) << (2 * (k - 1)));
+    if (s.valid < k) ++s.valid;
+}
+
+KQ_HD static inline uint64_t kq_canon(const KqRoll &s) { return s.fwd < s.rc ? s.fwd : s.rc; }
+
+// the owned bases [b0, b1) of thread `tid` of the tile that begins at base `first` of a contig of `len` bases (b0 >= b1: none)
+KQ_HD static inline void kq_bounds(int64_t first, int tid, int64_t len, int64_t &b0, int64_t &b1)
+{
+    b0 = first + (int64_t)tid * KQ_RUN;
+    b1 = b0 + KQ_RUN < len ? b0 + KQ_RUN : len;
+}
+
+// the state in front of base b0: the up to k - 1 bases before it rolled in
+KQ_HD static inline KqRoll kq_lead(const uint8_t *seq, int64_t b0, int k)
+{
+    KqRoll s = {0, 0, 0};
+    for (int64_t i = b0 - (k - 1) > 0 ? b0 - (k - 1) : 0; i < b0; ++i) kq_roll(s, kq_code(seq[i]), k);
+    return s;
+}
+
+// base b0 + r of the run [b0, b1) rolled into s; true when a k-mer ends there: its position and its canonical code.  r >= b1 - b0: nothing is read
+KQ_HD static inline bool kq_step(const uint8_t *seq, int64_t b0, int64_t b1, int r, KqRoll &s, int k, int64_t &pos, uint64_t &key)
+{
+    const int64_t e = b0 + r;
+    if (e >= b1) return false;
+    kq_roll(s, kq_code(seq[e]), k);
+    if (s.valid != k) return false;
+    pos = e - (k - 1);
+    key = kq_canon(s);
+    return true;
+}
+
+// a thread of the kernels: bounds, lead, KQ_RUN steps (the kernels spell the same three calls out, with their ballots between the steps)
+template <class F>
+KQ_HD static inline void kq_run(const uint8_t *seq, int64_t len, int64_t first, int tid, int k, F f)
+{
+    int64_t b0, b1;
+    kq_bounds(first, tid, len, b0, b1);
+    KqRoll s = {0, 0, 0};
+    if (b0 < b1) s = kq_lead(seq, b0, k);
+    for (int r = 0; r < KQ_RUN; ++r) {
+        int64_t pos;
+        uint64_t key;
+        if (kq_step(seq, b0, b1, r, s, k, pos, key)) f(pos, key);
+    }
+}
+
+// the finaliser of MurmurHash3 (public domain): every input bit reaches every output bit
+KQ_HD static inline uint64_t kq_mix(uint64_t x)
+{
+    x ^= x >> 33;
+    x *= 0xff51afd7ed558ccdull;
+    x ^= x >> 33;
+    x *= 0xc4ceb9fe1a85ec53ull;
+    x ^= x >> 33;
+    return x;
+}
+
+KQ_HD static inline uint64_t kq_mulhi(uint64_t a, uint64_t b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umul64hi(a, b);
+#else
+    return (uint64_t)(((unsigned __int128)a * b) >> 64);
+#endif
+}
+
+KQ_HD static inline uint64_t kq_home(uint64_t key, uint64_t slots) { return kq_mulhi(kq_mix(key), slots); }   // < slots
+KQ_HD static inline uint64_t kq_next(uint64_t slot, uint64_t slots) { return slot + 1 == slots ? 0 : slot + 1; }
+
+template <class Cas, class Stop>
+KQ_HD static inline int kq_insert(uint64_t *tab, uint64_t slots, uint64_t key, Cas cas, Stop stop)
+{
+    uint64_t slot = kq_home(key, slots);
+    for (uint64_t step = 0; step < slots; ++step) {
+        const uint64_t old = cas(tab + slot, KQ_EMPTY, key);
+        if (old == KQ_EMPTY) return KQ_NEW;
+        if (old == key) return KQ_PRESENT;
+        if ((step & 1023) == 1023 && stop()) return KQ_FULL;
+        slot = kq_next(slot, slots);
+    }
+    return KQ_FULL;
+}
+
+KQ_HD static inline bool kq_lookup(const uint64_t *tab, uint64_t slots, uint64_t key)
+{
+    uint64_t slot = kq_home(key, slots);
+    for (uint64_t step = 0; step < slots; ++step) {
+        const uint64_t v = tab[slot];
+        if (v == key) return true;
+        if (v == KQ_EMPTY) return false;
+        slot = kq_next(slot, slots);
+    }
+    return false;
+}
+
+// position `pos` of a contig whose first tile is tile `tile0` of the table: bit `pos` behind the contig's first word
+KQ_HD static inline void kq_bit(int64_t tile0, int64_t pos, int64_t &word, uint64_t &mask)
+{
+    const int64_t g = tile0 * KQ_TILE + pos;
+    word = g >> 6;
+    mask = (uint64_t)1 << (g & 63);
+}
+
+// ---- the bitmap -> the runs of consecutive set bits.  Word w with the last bit of the word in front (`prev`, 0 for the first word) and the
+// first bit of the word behind (`next`, 0 for the last): a run starts at a set bit whose predecessor is clear and ends at a set bit whose
+// successor is clear.  No run spans two contigs: the last k - 1 positions of a contig hold no k-mer, so the bit in front of a contig's first
+// word is always clear.  The j-th start of the bitmap and its j-th end are the same run; with rank = starts in front of word w, the ends
+// in front of it are rank - (a run is open across the seam: prev && the word's first bit).
+KQ_HD static inline uint64_t kq_starts(uint64_t w, uint64_t prev) { return w & ~((w << 1) | (prev & 1)); }
+KQ_HD static inline uint64_t kq_ends(uint64_t w, uint64_t next) { return w & ~((w >> 1) | ((next & 1) << 63)); }
+KQ_HD static inline uint32_t kq_end_rank(uint32_t rank, uint64_t w, uint64_t prev) { return rank - (uint32_t)(prev & w & 1); }
+
+}  // namespace

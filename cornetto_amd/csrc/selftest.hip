@@ -116,6 +116,7 @@ constexpr WsRow ws_table[] = {
     WS_SCR(WS_SORT), WS_SCR(WS_HAP_ROWS), WS_SCR(WS_HAP_BLOCKS), WS_SCR(WS_HAP_FUN),
     WS_SCR(WS_BZ_BLOCKS), WS_SCR(WS_BZ_STATUS), WS_SCR(WS_BZ_PACK),
     WS_SCR(WS_DF_STAGE), WS_SCR(WS_DF_SIZE), WS_SCR(WS_DF_TOTAL),
+    WS_SCR(WS_KQ_CNT), WS_SCR(WS_KQ_MAP), WS_SCR(WS_KQ_ROWS),
 };
 #undef WS_ROW
 #undef WS_SCR

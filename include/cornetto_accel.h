@@ -840,6 +840,42 @@ int cornetto_fqseq_qsums(cornetto_accel_t *h, cornetto_fqseq_t *q, uint64_t **su
 int cornetto_bamfq_qsums(cornetto_accel_t *h, cornetto_bamfq_t *b, uint64_t **sums, int64_t *n_sums);
 
 /* ---------------------------------------------------------------------------------------------------
+ * k-mer QV of an assembly against a truth set: `cornetto qv`.  An EXTENSION (the reference's protocol runs `yak count` / `yak qv` against the
+ * HG002 Q100 assembly at this step, docs/protocol.md:292-303; yak's histogram error model is NOT replicated, the rule below is Merqury's;
+ * parity with either is unpinned).  THE RULE:
+ *   - k is odd, 11 <= k <= 31 (default 21): no k-mer is its own reverse complement;
+ *   - base codes: A a = 0, C c = 1, G g = 2, T t = 3; every other byte is invalid;
+ *   - position i of a contig of length L holds a k-mer iff i + k <= L and all of seq[i .. i + k) are valid;
+ *   - the k-mer is canonical: min(fwd, rc) of the two 2k-bit codes, first base most significant;
+ *   - the truth set S: the canonical k-mers of every position of every record of the truth file(s);
+ *   - per contig c of an assembly: kmers[c] = the positions that hold a k-mer, counted with multiplicity; missing[c] = those of them whose
+ *     canonical k-mer is not in S;
+ *   - per contig, on request: the union of the spans [i, i + k) of the missing positions; spans that overlap or are book-ended merge
+ *     (bedtools merge); rows cornetto_ivl_t {ctg, start, finish} by contig, then by start;
+ *   - QV, on the host in double from the two integers: p = (kmers - missing) / kmers, e = 1 - pow(p, 1.0 / k), qv = -10 log10(e); missing == 0
+ *     prints e as 0 and qv as inf, kmers == 0 prints both as NA, otherwise e with %.3e and qv with %.2f.
+ * Every count is an integer that does not depend on the order of insertion or of the probes.
+ * On the device (csrc/kqv.hip, kqv.hpp): an open-addressing table of uint64_t with linear probing, the empty slot ~0, the home slot
+ * mulhi64(mix(key), slots) — slots need not be a power of two; a contig is cut into tiles of CORNETTO_KQV_TILE bases, a workgroup a tile.
+ * ------------------------------------------------------------------------------------------------- */
+#define CORNETTO_KQV_TILE 4096
+typedef struct cornetto_kset cornetto_kset_t; /* a set of canonical k-mers resident in HBM */
+/* slots >= 1 (8 bytes each); a k outside the rule: CORNETTO_E_UNSUPPORTED; a table that cannot be allocated: CORNETTO_E_NOMEM, the message says
+ * how many bytes were wanted.  Every slot is set to empty on the handle's stream, whatever the memory held. */
+int cornetto_kset_open(cornetto_accel_t *h, int32_t k, int64_t slots, cornetto_kset_t **out);
+/* the k-mers of every contig of `truth` into the set (kq_insert); may be called repeatedly, once per batch of a streamer.  CORNETTO_E_NOMEM: the
+ * table overflowed (a probe found no room in `slots` steps), the set is unusable from then on.  Never a hang: no probe takes more steps. */
+int cornetto_kset_add(cornetto_accel_t *h, cornetto_kset_t *s, const cornetto_asm_t *truth);
+/* stats[0 .. 3): positions inserted (with multiplicity), distinct k-mers, slots */
+void cornetto_kset_stats(const cornetto_kset_t *s, int64_t *stats);
+/* kmers[c], missing[c] for the contigs of `a` (kq_query; arrays of the assembly's contig count).  runs / n_runs (both or neither): the rows of
+ * the rule, cornetto_free().  The rows are placed by 32-bit counts: with rows requested, an assembly with bases / 2 + contigs > 2^32 - 1 is
+ * refused by its size alone (CORNETTO_E_UNSUPPORTED).  One call at a time per set: the set keeps the call's tile table. */
+int cornetto_kset_query(cornetto_accel_t *h, const cornetto_kset_t *s, const cornetto_asm_t *a, int64_t *kmers, int64_t *missing, cornetto_ivl_t **runs,
+                        int64_t *n_runs);
+void cornetto_kset_free(cornetto_accel_t *h, cornetto_kset_t *s);
+
+/* ---------------------------------------------------------------------------------------------------
  * fixasm output text: the records of a resident assembly, renamed and reoriented
  * ------------------------------------------------------------------------------------------------- */
 
