@@ -304,6 +304,8 @@ def lib(dev=False):
         "cornetto_kset_stats": (None, [vp, C.POINTER(i64)]),
         "cornetto_kset_query": (C.c_int, [vp, vp, vp, C.POINTER(i64), C.POINTER(i64), pp, C.POINTER(i64)]),
         "cornetto_kset_free": (None, [vp, vp]),
+        "cornetto_kset_add_tag": (C.c_int, [vp, vp, vp, i32]),
+        "cornetto_kset_phase": (C.c_int, [vp, vp, vp, C.POINTER(i64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError if the library does not export a declared symbol
@@ -404,9 +406,13 @@ class Kset:
     def __init__(self, acc, ptr, k, slots):
         self.acc, self.ptr, self.k, self.slots = acc, ptr, k, slots
 
-    def add(self, asm):
-        """the k-mers of every contig of the resident assembly into the set; AccelError with status -4 when the table overflowed"""
-        self.acc._chk(self.acc.L.cornetto_kset_add(self.acc.h, self.ptr, asm.ptr))
+    def add(self, asm, tag=0):
+        """the k-mers of every contig of the resident assembly into the set; AccelError with status -4 when the table overflowed.  tag 1 (pat) or
+        2 (mat): into a tagged set (cornetto_kset_add_tag), the table of `cornetto trioeval`; a set is either plain or tagged"""
+        if tag:
+            self.acc._chk(self.acc.L.cornetto_kset_add_tag(self.acc.h, self.ptr, asm.ptr, tag))
+        else:
+            self.acc._chk(self.acc.L.cornetto_kset_add(self.acc.h, self.ptr, asm.ptr))
 
     @property
     def stats(self):
@@ -425,6 +431,13 @@ class Kset:
         if runs:
             return km[:n], ms[:n], _take(self.acc.L, p, nr.value, IVL_DT)
         return km[:n], ms[:n]
+
+    def phase(self, asm):
+        """-> (n, 7) int64 per contig of `asm` against a tagged set: kmers, pat, mat, pp, pm, mp, mm (cornetto_kset_phase)"""
+        n = len(asm.lens)
+        out = np.zeros((max(n, 1), 7), dtype=np.int64)
+        self.acc._chk(self.acc.L.cornetto_kset_phase(self.acc.h, self.ptr, asm.ptr, out.ctypes.data_as(C.POINTER(C.c_int64))))
+        return out[:n]
 
     def close(self):
         if self.ptr is not None:

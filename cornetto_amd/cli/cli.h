@@ -161,7 +161,7 @@ typedef void (*scan_fn)(cornetto_accel_t *h, const cli_recname_t *r, int64_t n, 
  * to `scan` in input order, a batch at a time; must_open: a file that cannot be opened is the reference's F_CHK error (exit 1).
  * warm: the entry points `scan` will call (CORNETTO_WARM_*, or 0), warmed up behind the device open when the input is a large assembly */
 void stream_records(const char *path, int must_open, scan_fn scan, void *arg, int warm);
-/* the same on the caller's open handle `h`, for a sub-command that reads several files in one process (qv): what a call allocates (device
+/* the same on the caller's open handle `h`, for a sub-command that reads several files in one process (qv, trioeval): what a call allocates (device
  * text, pinned slabs and pieces) is released before it returns */
 void stream_records_on(cornetto_accel_t *h, const char *path, int must_open, scan_fn scan, void *arg);
 /* the same for callers that need only every record's name and length: `names` is handed a == NULL.  No bases reach the device (the framing
@@ -333,5 +333,6 @@ int telocontigs_main(int argc, char *argv[]);
 int asmstats_main(int argc, char *argv[]);
 int telostats_main(int argc, char *argv[]);
 int qv_main(int argc, char *argv[]);
+int trioeval_main(int argc, char *argv[]);
 
 #endif

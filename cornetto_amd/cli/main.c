@@ -1,7 +1,8 @@
 /* main.c — `cornetto <command>` dispatcher; mirrors src/main.c:95-152 of the reference for the
  * panel-creation sub-commands (same names, same exit codes, same 3-line stderr footer), for fixasm
  * (fixasm_main.c), for the evaluation sub-commands asmstats, nx, report and telocontigs (eval_main.c) and for telostats, the reference's
- * scripts/telostats.sh as one sub-command (telostats_main.c), and for qv, the k-mer QV step of the protocol (qv_main.c).
+ * scripts/telostats.sh as one sub-command (telostats_main.c), and for qv and trioeval, the k-mer QV and the switch / Hamming error steps of
+ * the protocol (qv_main.c, trioeval_main.c).
  * minidot, the one sub-command of the reference outside this build, is not in the usage text and exits
  * with status 1 as unrecognised; telobreaks is built and dispatched below. */
 #include <stdlib.h>
@@ -33,6 +34,7 @@ static int print_usage(FILE *fp)
     fprintf(fp, "       qv              k-mer consensus quality of assemblies against a truth assembly\n");
     fprintf(fp, "       report          generate a report table for one or more assemblies\n");
     fprintf(fp, "       telocontigs     prints contigs from largest to smallest with number of telomeres\n");
+    fprintf(fp, "       trioeval        switch and Hamming error of phased assemblies against parental k-mers\n");
     fprintf(fp, "   misc:\n");
     fprintf(fp, "       fa2bed          create a bed file with assembly contig lengths\n");
     fprintf(fp, "       seq             extract reads equal or longer than a threshold from a fastq\n");
@@ -80,6 +82,8 @@ int main(int argc, char *argv[])
         ret = asmstats_main(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "qv") == 0) {
         ret = qv_main(argc - 1, argv + 1);
+    } else if (strcmp(argv[1], "trioeval") == 0) {
+        ret = trioeval_main(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "seq") == 0) {
         ret = seq_main(argc - 1, argv + 1);
     } else if (strcmp(argv[1], "--version") == 0 || strcmp(argv[1], "-V") == 0) {

@@ -15,6 +15,7 @@
 #include <unistd.h>
 
 #include "cli.h"
+#include "kmer.h"
 
 typedef struct {
     int k;
@@ -96,32 +97,11 @@ static void asm_scan(cornetto_accel_t *h, const cli_recname_t *r, int64_t n, con
 }
 
 /* ---------------------------------------------------------------- the host path: the same rule, one record at a time */
-static inline int base_code(unsigned char c)
-{
-    switch (c) {
-    case 'A': case 'a': return 0;
-    case 'C': case 'c': return 1;
-    case 'G': case 'g': return 2;
-    case 'T': case 't': return 3;
-    default: return 4;
-    }
-}
-
-static inline uint64_t host_mix(uint64_t x)
-{
-    x ^= x >> 33;
-    x *= 0xff51afd7ed558ccdULL;
-    x ^= x >> 33;
-    x *= 0xc4ceb9fe1a85ec53ULL;
-    x ^= x >> 33;
-    return x;
-}
-
 /* 1 new, 0 present, -1 no room */
 static int host_insert(qv_t *Q, uint64_t key)
 {
     const uint64_t slots = (uint64_t)Q->slots;
-    uint64_t s = host_mix(key) % slots;
+    uint64_t s = cli_kmer_mix(key) % slots;
     for (uint64_t step = 0; step < slots; ++step) {
         if (Q->tab[s] == key) return 0;
         if (Q->tab[s] == ~(uint64_t)0) {
@@ -136,7 +116,7 @@ static int host_insert(qv_t *Q, uint64_t key)
 static int host_has(const qv_t *Q, uint64_t key)
 {
     const uint64_t slots = (uint64_t)Q->slots;
-    uint64_t s = host_mix(key) % slots;
+    uint64_t s = cli_kmer_mix(key) % slots;
     for (uint64_t step = 0; step < slots; ++step) {
         if (Q->tab[s] == key) return 1;
         if (Q->tab[s] == ~(uint64_t)0) return 0;
@@ -149,23 +129,14 @@ static int host_has(const qv_t *Q, uint64_t key)
 static void host_record(qv_t *Q, const cli_rec_t *rec, int truth)
 {
     const int k = Q->k;
-    const uint64_t mask = ((uint64_t)1 << (2 * k)) - 1;
     const unsigned char *s = (const unsigned char *)rec->seq.s;
     const int64_t len = (int64_t)rec->seq.l;
-    uint64_t fwd = 0, rc = 0;
-    int valid = 0;
+    cli_kroll_t R;
+    cli_kroll_init(&R, k);
     int64_t kmers = 0, missing = 0, open_start = -1, open_finish = -1;
     for (int64_t e = 0; e < len; ++e) {
-        const int c = base_code(s[e]);
-        if (c > 3) {
-            valid = 0;
-            continue;
-        }
-        fwd = ((fwd << 2) | (uint64_t)c) & mask;
-        rc = (rc >> 2) | ((uint64_t)(3 - c) << (2 * (k - 1)));
-        if (valid < k) ++valid;
-        if (valid < k) continue;
-        const uint64_t key = fwd < rc ? fwd : rc;
+        uint64_t key;
+        if (!cli_kroll_push(&R, s[e], &key)) continue;
         const int64_t pos = e - (k - 1);
         if (truth) {
             const int r = host_insert(Q, key);
@@ -212,9 +183,8 @@ static void sum_lengths(cornetto_accel_t *h, const cli_recname_t *r, int64_t n, 
     for (int64_t i = 0; i < n; ++i) *(int64_t *)arg += r[i].len;
 }
 
-/* an upper bound of the positions of a truth file: the bytes of a plain regular file, else the sum of the record lengths of one pass over it;
- * -1: a FIFO or `-`, which can be read only once */
-static int64_t truth_bound(const char *path)
+/* kmer.h: an upper bound of the positions of a truth file */
+int64_t cli_kmer_file_bound(const char *path)
 {
     struct stat st;
     if (!strcmp(path, "-")) return -1;
@@ -293,7 +263,7 @@ int qv_main(int argc, char *argv[])
         if (*end || end == slots_arg || errno || slots < 1) usage_fail("--slots: a number of at least 1");
     } else {
         for (int i = 0; i < n_truth; ++i) {
-            const int64_t b = truth_bound(truth[i]);
+            const int64_t b = cli_kmer_file_bound(truth[i]);
             if (b < 0) usage_fail("a truth that is a FIFO or `-` can be read only once: size the table with --slots");
             slots += 2 * b;
         }

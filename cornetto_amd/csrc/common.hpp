@@ -50,7 +50,7 @@ struct cornetto_accel {
         void *p = nullptr;
         size_t bytes = 0;
     };
-    Ws dev[72];
+    Ws dev[80];
     Ws pin[32];
     int sd_slots = 0;   // sdust: waves the device holds at once (occupancy query, cached)
     int sd_cus = 0;
@@ -159,9 +159,10 @@ enum {   // device workspace slots
     WS_BZ_BLOCKS, WS_BZ_STATUS, WS_BZ_PACK,
     WS_DF_STAGE, WS_DF_SIZE, WS_DF_TOTAL,
     WS_KQ_CNT, WS_KQ_MAP, WS_KQ_ROWS,
+    WS_KT_CNT, WS_KT_MAP,
     WS_COUNT
 };
-static_assert(WS_COUNT <= 72, "cornetto_accel::dev has 72 slots");
+static_assert(WS_COUNT <= 80, "cornetto_accel::dev has 80 slots");
 enum {   // pinned host slots
     PIN_A, PIN_B, PIN_C, PIN_D, PIN_E, PIN_F, PIN_SMALL, PIN_TW, PIN_CW, PIN_STEP, PIN_TE,
     PIN_COUNT

@@ -19,28 +19,11 @@
 #include "common.hpp"
 #include "ivlmerge.hpp"
 #include "kqv.hpp"
+#include "kset.hpp"
 #include "scan.hpp"
 #include "tiles.hpp"
 
-struct cornetto_kset {
-    int32_t k = 0;
-    int64_t slots = 0;
-    uint64_t *d_tab = nullptr;
-    unsigned long long *d_stat = nullptr;   // [0] positions inserted, [1] distinct, [2] overflow
-    int64_t stats[3] = {0, 0, 0};           // host copy of [0], [1]; [2] = slots
-    bool dead = false;                      // the table overflowed
-    // the tile table of the last assembly seen (rebuilt per call: a function of the lengths alone)
-    CnPrefix pref;
-    int2 *d_tiles = nullptr;
-    size_t tiles_cap = 0;
-};
-
 namespace {
-
-struct KqTileFill {
-    int2 *out;
-    __device__ void operator()(int64_t t, int c, int64_t j) const { out[t] = make_int2(c, (int)(j * KQ_TILE)); }
-};
 
 __device__ __forceinline__ uint32_t kq_count(bool p) { return (uint32_t)__popcll(__ballot(p)); }
 
@@ -136,28 +119,6 @@ __global__ void __launch_bounds__(256) kq_run_emit(const unsigned long long *__r
     for (uint64_t m = kq_ends(v, next); m; m &= m - 1, ++r) rows[r].finish = p0 + (__ffsll((unsigned long long)m) - 1) + k;
 }
 
-// the tile table of `a` in the set's own buffers -> the number of tiles, or a negative status
-int64_t kq_tiles(cornetto_accel_t *h, cornetto_kset_t *s, const cornetto_asm_t *a)
-{
-    const int64_t nt = cntiles::prefix(h, s->pref, a->n, [&](int32_t c) { return ((int64_t)a->len[c] + KQ_TILE - 1) / KQ_TILE; });
-    if (nt < 0) return cn_fail(h, CORNETTO_E_NOMEM, "kset: device allocation failed");
-    if (nt > 0x7fffffffll) return cn_fail(h, CORNETTO_E_UNSUPPORTED, "kset: too many tiles");
-    if (nt == 0) return 0;
-    if (s->tiles_cap < (size_t)nt) {
-        if (s->d_tiles) (void)hipFree(s->d_tiles);
-        s->d_tiles = nullptr;
-        s->tiles_cap = 0;
-        if (cn_obj_malloc(h, (void **)&s->d_tiles, (size_t)nt * sizeof(int2)) != hipSuccess) {
-            (void)hipGetLastError();
-            return cn_fail(h, CORNETTO_E_NOMEM, "kset: device allocation failed");
-        }
-        s->tiles_cap = (size_t)nt;
-    }
-    cntiles::fill<<<dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, h->stream>>>(s->pref.dev, a->n, nt, KqTileFill{s->d_tiles});
-    if (hipGetLastError() != hipSuccess) return cn_fail(h, CORNETTO_E_HIP, "kset: the tile table could not be launched");
-    return nt;
-}
-
 }  // namespace
 
 extern "C" {
@@ -212,7 +173,9 @@ void cornetto_kset_stats(const cornetto_kset_t *s, int64_t *stats)
 int cornetto_kset_add(cornetto_accel_t *h, cornetto_kset_t *s, const cornetto_asm_t *truth)
 {
     if (!h || !s || !truth) return cn_fail(h, CORNETTO_E_ARG, "kset_add: bad argument");
+    if (s->mode == KSET_TAGGED) return cn_fail(h, CORNETTO_E_UNSUPPORTED, "kset_add: the set is tagged (kset_add_tag); a set is either plain or tagged");
     if (s->dead) return cn_fail(h, CORNETTO_E_NOMEM, "kset_add: the table of %lld slots has overflowed; the set is unusable", (long long)s->slots);
+    s->mode = KSET_PLAIN;
     CN_HIP(h, hipSetDevice(h->device));
     cn_timing_begin(h);
     const int64_t nt = kq_tiles(h, s, truth);
@@ -243,6 +206,7 @@ int cornetto_kset_query(cornetto_accel_t *h, const cornetto_kset_t *cs, const co
         *runs = nullptr;
         *n_runs = 0;
     }
+    if (s->mode == KSET_TAGGED) return cn_fail(h, CORNETTO_E_UNSUPPORTED, "kset_query: the set is tagged; its query is kset_phase");
     if (s->dead) return cn_fail(h, CORNETTO_E_ARG, "kset_query: the set is unusable, its table has overflowed");
     // the runs are placed by 32-bit ranks: at most one run per two positions and one more per contig
     if (runs && a->total / 2 + a->n > 0xFFFFFFFFll)

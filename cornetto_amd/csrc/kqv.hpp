@@ -13,6 +13,7 @@
 //                 itself; at most `slots` steps, then KQ_FULL.  `stop()` lets the lanes of a kernel leave once one of them has overflowed;
 //   kq_lookup()   the same walk with plain loads; a key is missing at the first EMPTY slot or after `slots` steps;
 //   kq_bit()      word and mask of position `pos` of a contig whose first tile is `tile0` in the bitmap (KQ_TILE bits per tile).
+//   kq_insert_tag(), kq_lookup_tag()   the same table with a 2-bit tag in bits 63:62 of a slot, for `cornetto trioeval` (ktrio.hip): below.
 // The empty slot is ~0: no key, k <= 31 makes every key smaller than 2^62.
 #pragma once
 #include <cstdint>
@@ -155,6 +156,48 @@ KQ_HD static inline bool kq_lookup(const uint64_t *tab, uint64_t slots, uint64_t
         slot = kq_next(slot, slots);
     }
     return false;
+}
+
+// ---- the tagged table of `cornetto trioeval`: a slot holds key | tag << 62, tag bit 0 = the key came from a paternal input, bit 1 = from a
+// maternal one; a table is either plain or tagged (cornetto_kset keeps which).  The empty slot stays ~0, and no tagged slot equals it: that
+// would take tag 3 and the key 2^62 - 1.  For k < 31 a key is below 2^(2k) <= 2^58.  For k = 31 the all-ones 62-bit code is T...T, whose
+// reverse complement A...A is 0 — the canonical code of that k-mer is 0, so 2^62 - 1 is never a key.
+//   kq_insert_tag()   old = cas(slot, EMPTY, key | tag << 62): new when old is EMPTY; when old holds the key under KQ_KEYMASK, the tag is OR-ed in
+//                     with fetch_or(slot, tag << 62) -> the old value — skipped when `old` carries it already (tags are only ever added, so a
+//                     value an atomic returned never overstates them) — and the key is present; otherwise the next slot.  The same `slots`-step
+//                     bound, KQ_FULL and stop() poll as kq_insert(); as there, only values returned by atomics decide anything;
+//   kq_lookup_tag()   plain loads (complete at the kernel boundary), compare under KQ_KEYMASK -> the tag, 0 for an absent key.
+constexpr uint64_t KQ_KEYMASK = ((uint64_t)1 << 62) - 1;
+constexpr int KQ_TAG_SHIFT = 62;
+
+template <class Cas, class FetchOr, class Stop>
+KQ_HD static inline int kq_insert_tag(uint64_t *tab, uint64_t slots, uint64_t key, uint64_t tag, Cas cas, FetchOr fetch_or, Stop stop)
+{
+    const uint64_t bits = tag << KQ_TAG_SHIFT;
+    uint64_t slot = kq_home(key, slots);
+    for (uint64_t step = 0; step < slots; ++step) {
+        const uint64_t old = cas(tab + slot, KQ_EMPTY, key | bits);
+        if (old == KQ_EMPTY) return KQ_NEW;
+        if ((old & KQ_KEYMASK) == key) {
+            if ((old & bits) != bits) (void)fetch_or(tab + slot, bits);
+            return KQ_PRESENT;
+        }
+        if ((step & 1023) == 1023 && stop()) return KQ_FULL;
+        slot = kq_next(slot, slots);
+    }
+    return KQ_FULL;
+}
+
+KQ_HD static inline int kq_lookup_tag(const uint64_t *tab, uint64_t slots, uint64_t key)
+{
+    uint64_t slot = kq_home(key, slots);
+    for (uint64_t step = 0; step < slots; ++step) {
+        const uint64_t v = tab[slot];
+        if (v == KQ_EMPTY) return 0;
+        if ((v & KQ_KEYMASK) == key) return (int)(v >> KQ_TAG_SHIFT);
+        slot = kq_next(slot, slots);
+    }
+    return 0;
 }
 
 // position `pos` of a contig whose first tile is tile `tile0` of the table: bit `pos` behind the contig's first word

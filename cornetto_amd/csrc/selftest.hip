@@ -117,6 +117,7 @@ constexpr WsRow ws_table[] = {
     WS_SCR(WS_BZ_BLOCKS), WS_SCR(WS_BZ_STATUS), WS_SCR(WS_BZ_PACK),
     WS_SCR(WS_DF_STAGE), WS_SCR(WS_DF_SIZE), WS_SCR(WS_DF_TOTAL),
     WS_SCR(WS_KQ_CNT), WS_SCR(WS_KQ_MAP), WS_SCR(WS_KQ_ROWS),
+    WS_SCR(WS_KT_CNT), WS_SCR(WS_KT_MAP),
 };
 #undef WS_ROW
 #undef WS_SCR

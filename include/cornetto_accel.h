@@ -876,6 +876,35 @@ int cornetto_kset_query(cornetto_accel_t *h, const cornetto_kset_t *s, const cor
 void cornetto_kset_free(cornetto_accel_t *h, cornetto_kset_t *s);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Switch and Hamming error of a phased assembly against parental k-mers: `cornetto trioeval`.  An EXTENSION (the reference's protocol runs
+ * `yak trioeval pat.yak mat.yak asm.fa` at this step, docs/protocol.md:292-308; yak works from read k-mer counts with thresholds, this works
+ * from parental or truth-haplotype ASSEMBLIES, as `cornetto qv hg002.mat.fa -t hg002.pat.fa` does; parity with yak is unpinned).  THE RULE:
+ *   - k, the valid bytes, the positions that hold a k-mer and the canonical code are those of `cornetto qv` above;
+ *   - P: the canonical k-mers of every position of every record of the paternal input; M: the same of the maternal input;
+ *   - a position of an assembly contig is a MARKER iff its k-mer is in exactly one of the two sets: of type pat when in P and not in M, of
+ *     type mat when in M and not in P; a k-mer in both sets or in neither is no marker;
+ *   - per contig: kmers = the positions that hold a k-mer, pat and mat = the markers of either type, all counted with multiplicity;
+ *   - per contig, the four PAIR counts pp, pm, mp, mm over every marker that has a marker in front of it in the same contig: the pair is
+ *     (type of the nearest marker at a smaller position, own type).  Invalid bytes between the two and their distance do not matter; no pair
+ *     spans two contigs; hence pp + pm + mp + mm = max(pat + mat - 1, 0);
+ *   - per assembly: switches = sum(pm + mp), pairs = sum(pp + pm + mp + mm), hamming = sum over the contigs of min(pat, mat), markers =
+ *     sum(pat + mat); switch_rate = switches / pairs and hamming_rate = hamming / markers, on the host in double from the integers, printed
+ *     with %.6f, or NA when the denominator is 0.
+ * Every integer is independent of the order of insertion and of the probes.
+ * On the device (csrc/ktrio.hip, ktrio.hpp, kqv.hpp): the table of `qv` with a 2-bit tag in bits 63:62 of a slot (bit 0 pat, bit 1 mat; every key
+ * is below 2^62); a set is either plain or tagged, decided by its first add, and the calls of the other family return CORNETTO_E_UNSUPPORTED.
+ * ------------------------------------------------------------------------------------------------- */
+#define CORNETTO_TRIO_PAT 1
+#define CORNETTO_TRIO_MAT 2
+#define CORNETTO_TRIO_COUNTS 7 /* per contig: kmers, pat, mat, pp, pm, mp, mm */
+/* cornetto_kset_add() with a tag: CORNETTO_TRIO_PAT or CORNETTO_TRIO_MAT, any other value is CORNETTO_E_ARG.  stats as for a plain set: the
+ * positions inserted and the distinct k-mers of the union.  Overflow as in cornetto_kset_add(): CORNETTO_E_NOMEM, the set is unusable, no hang. */
+int cornetto_kset_add_tag(cornetto_accel_t *h, cornetto_kset_t *s, const cornetto_asm_t *a, int32_t tag);
+/* counts[CORNETTO_TRIO_COUNTS * c + 0 .. 7) for the contigs of `a` (kt_mark, kt_tile, kt_seam).  0 contigs, contigs without a tile and contigs
+ * shorter than k are accepted (all counts 0).  One call at a time per set. */
+int cornetto_kset_phase(cornetto_accel_t *h, cornetto_kset_t *s, const cornetto_asm_t *a, int64_t *counts);
+
+/* ---------------------------------------------------------------------------------------------------
  * fixasm output text: the records of a resident assembly, renamed and reoriented
  * ------------------------------------------------------------------------------------------------- */
 
