@@ -88,6 +88,7 @@ class FqSeqOpt(C.Structure):
     _fields_ = [("min_len", C.c_int32), ("records", C.c_int32), ("window", C.c_int64)]
 
 
+KSET_COUNT_CAP, KSET_HIST_BINS = 65535, 1024  # CORNETTO_KSET_COUNT_CAP, CORNETTO_KSET_HIST_BINS: the counted sets of Accel.kset(channels=1 or 2)
 KQV_TILE = 4096  # CORNETTO_KQV_TILE: bases per workgroup of kq_insert / kq_query (tests plant seams at its multiples)
 FQSEQ_TILE = 16384  # CORNETTO_FQSEQ_TILE: output bytes per workgroup of fqseq_text (checked against the library when it is loaded)
 BAMFQREC_DT = np.dtype([("offset", "<i8"), ("l_seq", "<i4"), ("flag", "<i4"), ("name_len", "<i4"), ("kept", "<i4")])
@@ -306,6 +307,10 @@ def lib(dev=False):
         "cornetto_kset_free": (None, [vp, vp]),
         "cornetto_kset_add_tag": (C.c_int, [vp, vp, vp, i32]),
         "cornetto_kset_phase": (C.c_int, [vp, vp, vp, C.POINTER(i64)]),
+        "cornetto_kset_open_counted": (C.c_int, [vp, i32, i64, i32, pp]),
+        "cornetto_kset_count": (C.c_int, [vp, vp, vp, i32]),
+        "cornetto_kset_hist": (C.c_int, [vp, vp, i32, C.POINTER(i64)]),
+        "cornetto_kset_seal": (C.c_int, [vp, vp, C.POINTER(i32), C.POINTER(i64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError if the library does not export a declared symbol
@@ -401,10 +406,31 @@ class _Resident:
 
 
 class Kset:
-    """a set of canonical k-mers resident in HBM (cornetto_kset_*): Accel.kset(k, slots)"""
+    """a set of canonical k-mers resident in HBM (cornetto_kset_*): Accel.kset(k, slots); with channels = 1 or 2 a counted set, which takes
+    count() and hist() until seal() makes it the plain (1 channel) or the tagged (2) set that query() / phase() probe"""
 
-    def __init__(self, acc, ptr, k, slots):
-        self.acc, self.ptr, self.k, self.slots = acc, ptr, k, slots
+    def __init__(self, acc, ptr, k, slots, channels=0):
+        self.acc, self.ptr, self.k, self.slots, self.channels = acc, ptr, k, slots, channels
+
+    def count(self, asm, channel=0):
+        """the k-mers of every record of the resident batch counted into `channel` (cornetto_kset_count); status -4 when the table overflowed"""
+        self.acc._chk(self.acc.L.cornetto_kset_count(self.acc.h, self.ptr, asm.ptr, channel))
+
+    def hist(self, channel=0):
+        """-> int64[1024]: hist[c] = distinct k-mers of `channel` with min(count, 1023) == c; bin 0 stays 0 (cornetto_kset_hist)"""
+        out = np.zeros(KSET_HIST_BINS, dtype=np.int64)
+        self.acc._chk(self.acc.L.cornetto_kset_hist(self.acc.h, self.ptr, channel, out.ctypes.data_as(C.POINTER(C.c_int64))))
+        return out
+
+    def seal(self, min_count):
+        """min_count: an int, or one per channel -> the solid k-mers per channel; the set is plain or tagged from here on (cornetto_kset_seal)"""
+        n = max(self.channels, 1)
+        m = [int(min_count)] * n if np.isscalar(min_count) else [int(x) for x in min_count]
+        if len(m) != n:
+            raise ValueError("seal: %d thresholds for %d channels" % (len(m), n))
+        mc, solid = (C.c_int32 * 2)(*m), (C.c_int64 * 2)()
+        self.acc._chk(self.acc.L.cornetto_kset_seal(self.acc.h, self.ptr, mc, solid))
+        return tuple(int(solid[i]) for i in range(n))
 
     def add(self, asm, tag=0):
         """the k-mers of every contig of the resident assembly into the set; AccelError with status -4 when the table overflowed.  tag 1 (pat) or
@@ -519,11 +545,15 @@ class Accel:
         self._chk(self.L.cornetto_asm_upload(self.h, ptrs, lens.ctypes.data, n, C.byref(out)))
         return _Resident(self, out, self.L.cornetto_asm_free, lens)
 
-    def kset(self, k=21, slots=1):
-        """an empty k-mer set with `slots` slots of 8 bytes: cornetto_kset_open()"""
+    def kset(self, k=21, slots=1, channels=0):
+        """an empty k-mer set with `slots` slots of 8 bytes: cornetto_kset_open(); channels = 1 or 2: a counted set with 4 more bytes per slot
+        and channel (cornetto_kset_open_counted)"""
         out = C.c_void_p()
-        self._chk(self.L.cornetto_kset_open(self.h, k, slots, C.byref(out)))
-        return Kset(self, out, k, slots)
+        if channels:
+            self._chk(self.L.cornetto_kset_open_counted(self.h, k, slots, channels, C.byref(out)))
+        else:
+            self._chk(self.L.cornetto_kset_open(self.h, k, slots, C.byref(out)))
+        return Kset(self, out, k, slots, channels)
 
     def asm_wrap(self, dev_ptr, offsets, lens):
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)

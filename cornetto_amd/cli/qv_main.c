@@ -1,11 +1,16 @@
-/* qv_main.c — `cornetto qv [-k INT] [-t FILE]... [-c FILE] [-b FILE] [--slots INT] [--accel=no] <truth.fa> <asm.fa> [asm2.fa ...]`: the k-mer
- * consensus quality of assemblies against a truth assembly.  Not in the reference: its protocol (docs/protocol.md:292-303) runs `yak count`
+/* qv_main.c — `cornetto qv [-k INT] [-t FILE]... [-c FILE] [-b FILE] [--slots INT] [--accel=no] <truth.fa> <asm.fa> [asm2.fa ...]`, or from reads,
+ * `cornetto qv -r reads.fq [-r more.fq] [--min-count INT] [--hist FILE] [...] <asm.fa> [asm2.fa ...]`: the k-mer consensus quality of assemblies
+ * against a truth assembly, or against the k-mers that the sample's own accurate reads hold at least --min-count times.  Not in the reference: its
+ * protocol (docs/protocol.md:292-303) runs `yak count`
  * and `yak qv` against the HG002 Q100 assembly for asm-1 .. asm-n, primary and hap1+hap2.  The rule is stated once in include/cornetto_accel.h
  * (Merqury's QV from the share of an assembly's k-mers that the truth does not hold; yak's histogram error model is not replicated).
  *
  * The truth files are read once (stream.c) and every batch of their records goes into one set of canonical k-mers that stays resident in HBM
  * (cornetto_kset_add); every assembly is then read the same way and probed against it (cornetto_kset_query).  One device handle serves all files.
- * --accel=no / CORNETTO_ACCEL=no: the same rule on the host, a single-threaded open-addressing set and the sequential reader; the same bytes. */
+ * With -r the set is a counted one (cornetto_kset_open_counted, cornetto_kset_count per batch), its histogram goes to --hist, and the seal with
+ * --min-count (cornetto_kset_seal) leaves the plain set that the same probes walk.
+ * --accel=no / CORNETTO_ACCEL=no: the same rule on the host, a single-threaded open-addressing set (kmer.h has the counted one) and the sequential
+ * reader; the same bytes. */
 #include <errno.h>
 #include <getopt.h>
 #include <math.h>
@@ -25,6 +30,8 @@ typedef struct {
     cornetto_kset_t *set;                 /* device path */
     uint64_t *tab;                        /* host path: open addressing, linear probing, ~0 = empty */
     int64_t h_pos, h_distinct;
+    int reads;                            /* -r: the truth is counted, not inserted */
+    cli_kcount_t kc;                      /* host path with -r: the counted table; its key array becomes `tab` at the seal */
     /* the assembly being read */
     int64_t contigs, bases, kmers, missing;
     FILE *fc, *fb;
@@ -78,7 +85,7 @@ static void truth_scan(cornetto_accel_t *h, const cli_recname_t *r, int64_t n, c
     qv_t *Q = (qv_t *)arg;
     Q->t_recs += n;
     for (int64_t i = 0; i < n; ++i) Q->t_bases += r[i].len;
-    const int rc = cornetto_kset_add(h, Q->set, a);
+    const int rc = Q->reads ? cornetto_kset_count(h, Q->set, a, 0) : cornetto_kset_add(h, Q->set, a);
     if (rc == CORNETTO_E_NOMEM) qv_overflow(Q);
     cli_accel_check(h, rc, "qv: inserting the truth's k-mers");
 }
@@ -138,6 +145,10 @@ static void host_record(qv_t *Q, const cli_rec_t *rec, int truth)
         uint64_t key;
         if (!cli_kroll_push(&R, s[e], &key)) continue;
         const int64_t pos = e - (k - 1);
+        if (truth && Q->reads) {
+            if (cli_kcount_add(&Q->kc, key, 0) < 0) qv_overflow(Q);
+            continue;
+        }
         if (truth) {
             const int r = host_insert(Q, key);
             if (r < 0) qv_overflow(Q);
@@ -202,13 +213,19 @@ int64_t cli_kmer_file_bound(const char *path)
 static void usage(FILE *fp)
 {
     fprintf(fp, "Usage: cornetto qv [options] <truth.fasta> <assembly.fasta> [assembly2.fasta ...]\n");
+    fprintf(fp, "       cornetto qv [options] -r <reads.fastq> [-r <more.fastq> ...] <assembly.fasta> [assembly2.fasta ...]\n");
     fprintf(fp, "k-mer consensus quality of assemblies against a truth assembly: the share of every assembly's k-mers that the truth\n");
     fprintf(fp, "does not hold, as error rate and QV (Merqury's rule).  FASTA or FASTQ, plain, gzip or BGZF.\n");
     fprintf(fp, "   -k INT                     k-mer length, odd, 11 to 31 [21]\n");
     fprintf(fp, "   -t FILE                    a further truth file, e.g. the other haplotype (may be repeated)\n");
     fprintf(fp, "   -c FILE                    write the per-contig table to FILE (one assembly only)\n");
     fprintf(fp, "   -b FILE                    write the merged spans of the missing k-mers to FILE as BED (one assembly only)\n");
-    fprintf(fp, "   --slots INT                slots of the k-mer table, 8 bytes each [twice the bases of the truth]\n");
+    fprintf(fp, "   -r FILE                    the truth is the k-mers of these reads from --min-count occurrences upward (may be repeated);\n");
+    fprintf(fp, "                              every positional argument is then an assembly\n");
+    fprintf(fp, "   --min-count INT            with -r: a k-mer counts as true from INT occurrences in the reads, 1 to 65535 [2]\n");
+    fprintf(fp, "   --hist FILE                with -r: write the k-mer count histogram, count<TAB>kmers for counts 1 to 1023 (the last line: 1023 and more)\n");
+    fprintf(fp, "   --slots INT                slots of the k-mer table, 8 bytes each, 12 with -r [twice the bases of the truth or the reads;\n");
+    fprintf(fp, "                              about 1.5 times the expected distinct k-mers is the usual figure]\n");
     fprintf(fp, "   --accel=no                 run on the host\n");
     fprintf(fp, "   -h                         help\n");
 }
@@ -222,18 +239,22 @@ static void usage_fail(const char *msg)
 
 int qv_main(int argc, char *argv[])
 {
-    static const struct option lo[] = {{"help", no_argument, 0, 'h'}, {"slots", required_argument, 0, 1000}, {"accel", required_argument, 0, 1001}, {0, 0, 0, 0}};
-    const char *k_arg = "21", *c_arg = NULL, *b_arg = NULL, *slots_arg = NULL;
-    const char **truth = (const char **)cli_xmalloc(((size_t)argc + 1) * sizeof(char *));
-    int n_truth = 1, c, li = 0;
+    static const struct option lo[] = {{"help", no_argument, 0, 'h'}, {"slots", required_argument, 0, 1000}, {"accel", required_argument, 0, 1001},
+                                       {"min-count", required_argument, 0, 1002}, {"hist", required_argument, 0, 1003}, {0, 0, 0, 0}};
+    const char *k_arg = "21", *c_arg = NULL, *b_arg = NULL, *slots_arg = NULL, *mc_arg = NULL, *hist_arg = NULL;
+    const char **truth_mem = (const char **)cli_xmalloc(2 * ((size_t)argc + 1) * sizeof(char *)), **truth = truth_mem, **reads = truth + argc + 1;
+    int n_truth = 1, n_reads = 0, c, li = 0;
     FILE *fp_help = stderr;
     optind = 1;
-    while ((c = getopt_long(argc, argv, "k:t:c:b:h", lo, &li)) >= 0) {
+    while ((c = getopt_long(argc, argv, "k:t:r:c:b:h", lo, &li)) >= 0) {
         if (c == 'k') k_arg = optarg;
         else if (c == 't') truth[n_truth++] = optarg;
+        else if (c == 'r') reads[n_reads++] = optarg;
         else if (c == 'c') c_arg = optarg;
         else if (c == 'b') b_arg = optarg;
         else if (c == 1000) slots_arg = optarg;
+        else if (c == 1002) mc_arg = optarg;
+        else if (c == 1003) hist_arg = optarg;
         else if (c == 1001) {
             if (!strcmp(optarg, "no") || !strcmp(optarg, "n")) cli_host_set(1);
             else if (!strcmp(optarg, "yes") || !strcmp(optarg, "y")) cli_host_set(0);
@@ -245,14 +266,28 @@ int qv_main(int argc, char *argv[])
         usage(stdout);
         exit(EXIT_SUCCESS);
     }
-    if (argc - optind < 2) {
+    if (!n_reads && (mc_arg || hist_arg)) usage_fail("--min-count and --hist go with -r: a truth assembly holds every k-mer once");
+    if (n_reads && n_truth > 1) usage_fail("-t names a further truth assembly; it does not go with -r");
+    if (argc - optind < (n_reads ? 1 : 2)) {
         usage(stderr);
         exit(EXIT_FAILURE);
     }
-    truth[0] = argv[optind];
-    char **asms = argv + optind + 1;
-    const int n_asm = argc - optind - 1;
+    /* with -r every positional is an assembly and the files that fill the table are the reads */
+    if (n_reads) {
+        truth = reads;
+        n_truth = n_reads;
+    } else {
+        truth[0] = argv[optind];
+    }
+    char **asms = argv + optind + (n_reads ? 0 : 1);
+    const int n_asm = argc - optind - (n_reads ? 0 : 1);
     char *end = NULL;
+    long long min_count = 2;
+    if (mc_arg) {
+        errno = 0;
+        min_count = strtoll(mc_arg, &end, 10);
+        if (*end || end == mc_arg || errno || min_count < 1 || min_count > CORNETTO_KSET_COUNT_CAP) usage_fail("--min-count: a number from 1 to 65535");
+    }
     const long long k = strtoll(k_arg, &end, 10);
     if (*end || end == k_arg || k < 11 || k > 31 || !(k & 1)) usage_fail("-k: k is an odd number from 11 to 31");
     if ((c_arg || b_arg) && n_asm != 1) usage_fail("-c and -b take one assembly");
@@ -264,7 +299,8 @@ int qv_main(int argc, char *argv[])
     } else {
         for (int i = 0; i < n_truth; ++i) {
             const int64_t b = cli_kmer_file_bound(truth[i]);
-            if (b < 0) usage_fail("a truth that is a FIFO or `-` can be read only once: size the table with --slots");
+            if (b < 0) usage_fail(n_reads ? "a reads file that is a FIFO or `-` can be read only once: size the table with --slots"
+                                          : "a truth that is a FIFO or `-` can be read only once: size the table with --slots");
             slots += 2 * b;
         }
         if (slots < 1) slots = 1;
@@ -274,10 +310,19 @@ int qv_main(int argc, char *argv[])
     memset(&Q, 0, sizeof(Q));
     Q.k = (int)k;
     Q.slots = (int64_t)slots;
+    Q.reads = n_reads > 0;
     const int host = cli_host_mode();
     cornetto_accel_t *h = NULL;
     int64_t stats[3] = {0, 0, 0};
-    if (host) {
+    if (host && Q.reads) {
+        if (cli_kcount_init(&Q.kc, Q.slots, 1) != 0) {
+            CLI_ERROR("a k-mer table of %lld slots wants %lld bytes: give a smaller one with --slots", slots, slots * 12);
+            exit(EXIT_FAILURE);
+        }
+        for (int i = 0; i < n_truth; ++i) host_file(&Q, truth[i], 1);
+        stats[0] = Q.kc.pos;
+        stats[1] = Q.kc.distinct;
+    } else if (host) {
         Q.tab = (size_t)slots > SIZE_MAX / 8 ? NULL : (uint64_t *)malloc((size_t)slots * 8);
         if (!Q.tab) {
             CLI_ERROR("a k-mer table of %lld slots wants %lld bytes: give a smaller one with --slots", slots, slots * 8);
@@ -289,7 +334,7 @@ int qv_main(int argc, char *argv[])
         stats[1] = Q.h_distinct;
     } else {
         h = cli_accel_open();
-        const int rc = cornetto_kset_open(h, Q.k, Q.slots, &Q.set);
+        const int rc = Q.reads ? cornetto_kset_open_counted(h, Q.k, Q.slots, 1, &Q.set) : cornetto_kset_open(h, Q.k, Q.slots, &Q.set);
         if (rc == CORNETTO_E_NOMEM) {
             CLI_ERROR("%s: give a smaller one with --slots", cornetto_accel_last_error(h));
             exit(EXIT_FAILURE);
@@ -298,8 +343,34 @@ int qv_main(int argc, char *argv[])
         for (int i = 0; i < n_truth; ++i) stream_records_on(h, truth[i], 1, truth_scan, &Q);
         cornetto_kset_stats(Q.set, stats);
     }
-    fprintf(stderr, "[qv] truth: %lld records, %lld bases, %lld k-mers, %lld distinct, k=%d\n", (long long)Q.t_recs, (long long)Q.t_bases, (long long)stats[0],
-            (long long)stats[1], Q.k);
+    if (Q.reads) {
+        /* the histogram first, then the seal: from here on the table is the plain set of the solid k-mers */
+        if (hist_arg) {
+            int64_t hist[CORNETTO_KSET_HIST_BINS];
+            if (host) cli_kcount_hist(&Q.kc, 0, hist);
+            else cli_accel_check(h, cornetto_kset_hist(h, Q.set, 0, hist), "qv: the histogram of the k-mer counts");
+            FILE *fh = cli_fopen_chk(hist_arg, "w");
+            for (int i = 1; i < CORNETTO_KSET_HIST_BINS; ++i) fprintf(fh, "%d\t%lld\n", i, (long long)hist[i]);
+            if (fclose(fh) != 0) {
+                CLI_ERROR("%s", "writing the --hist file failed");
+                exit(EXIT_FAILURE);
+            }
+        }
+        const int m = (int)min_count;
+        const int32_t m32 = (int32_t)min_count;
+        int64_t solid = 0;
+        if (host) {
+            cli_kcount_seal(&Q.kc, &m, &solid);
+            Q.tab = Q.kc.tab;
+        } else {
+            cli_accel_check(h, cornetto_kset_seal(h, Q.set, &m32, &solid), "qv: sealing the k-mer counts");
+        }
+        fprintf(stderr, "[qv] reads: %lld records, %lld bases, %lld k-mers, %lld distinct, %lld solid (count >= %d), k=%d\n", (long long)Q.t_recs, (long long)Q.t_bases,
+                (long long)stats[0], (long long)stats[1], (long long)solid, m, Q.k);
+    } else {
+        fprintf(stderr, "[qv] truth: %lld records, %lld bases, %lld k-mers, %lld distinct, k=%d\n", (long long)Q.t_recs, (long long)Q.t_bases, (long long)stats[0],
+                (long long)stats[1], Q.k);
+    }
 
     Q.fc = c_arg ? cli_fopen_chk(c_arg, "w") : NULL;
     Q.fb = b_arg ? cli_fopen_chk(b_arg, "w") : NULL;
@@ -320,6 +391,6 @@ int qv_main(int argc, char *argv[])
     }
     if (Q.set) cornetto_kset_free(h, Q.set);
     free(Q.tab);
-    free(truth);
+    free(truth_mem);
     return EXIT_SUCCESS;
 }

@@ -1,12 +1,16 @@
-/* trioeval_main.c — `cornetto trioeval [-k INT] [-P FILE]... [-M FILE]... [-c FILE] [--slots INT] [--accel=no] <pat.fa> <mat.fa> <asm.fa> [asm2.fa ...]`:
+/* trioeval_main.c — `cornetto trioeval [-k INT] [-P FILE]... [-M FILE]... [-c FILE] [--slots INT] [--accel=no] <pat.fa> <mat.fa> <asm.fa> [asm2.fa ...]`,
+ * or from parental reads, `cornetto trioeval --pat-reads FILE [...] --mat-reads FILE [...] [--min-count INT[,INT]] [--hist FILE] [...] <asm.fa> [asm2.fa ...]`:
  * the switch error and the Hamming error of phased assemblies against the k-mers of the two parents.  Not in the reference: its protocol
  * (docs/protocol.md:292-308) runs `yak trioeval pat.yak mat.yak asm.hap1+hap2.fasta` here, from read k-mer counts with thresholds; this works from
- * parental (or truth-haplotype) assemblies.  The rule is stated once in include/cornetto_accel.h; parity with yak is unpinned.
+ * parental (or truth-haplotype) assemblies, or from parental reads with a count threshold of its own.  The rule is stated once in
+ * include/cornetto_accel.h; parity with yak is unpinned.
  *
  * The parental files are read once (stream.c) and every batch of their records goes into one tagged set of canonical k-mers that stays resident
  * in HBM (cornetto_kset_add_tag); every assembly is then read the same way and phased against it (cornetto_kset_phase).  One device handle
- * serves all files.  --accel=no / CORNETTO_ACCEL=no: the same rule on the host, qv's single-threaded open-addressing set with the tag in the
- * two top bits of a slot, and the sequential reader; the same bytes. */
+ * serves all files.  With parental reads the set is a counted one of two channels (cornetto_kset_open_counted, cornetto_kset_count per batch);
+ * its histograms go to --hist, and the seal with --min-count (cornetto_kset_seal) leaves the tagged set that the same phasing walks.
+ * --accel=no / CORNETTO_ACCEL=no: the same rule on the host, qv's single-threaded open-addressing set with the tag in the two top bits of a
+ * slot (kmer.h has the counted one), and the sequential reader; the same bytes. */
 #include <errno.h>
 #include <getopt.h>
 #include <stdlib.h>
@@ -26,6 +30,8 @@ typedef struct {
     cornetto_kset_t *set;                 /* device path */
     uint64_t *tab;                        /* host path: open addressing, linear probing, key | tag << 62, ~0 = empty */
     int64_t h_pos, h_distinct;
+    int reads;                            /* --pat-reads / --mat-reads: the parents are counted, not inserted */
+    cli_kcount_t kc;                      /* host path with reads: the counted table; its key array becomes `tab` at the seal */
     /* the assembly being read */
     int64_t contigs, bases, kmers, pat, mat, pairs, switches, hamming;
     FILE *fc;
@@ -67,7 +73,7 @@ static void parent_scan(cornetto_accel_t *h, const cli_recname_t *r, int64_t n, 
     trio_t *T = (trio_t *)arg;
     T->p_recs += n;
     for (int64_t i = 0; i < n; ++i) T->p_bases += r[i].len;
-    const int rc = cornetto_kset_add_tag(h, T->set, a, T->tag);
+    const int rc = T->reads ? cornetto_kset_count(h, T->set, a, T->tag - 1) : cornetto_kset_add_tag(h, T->set, a, T->tag);
     if (rc == CORNETTO_E_NOMEM) trio_overflow(T);
     cli_accel_check(h, rc, "trioeval: inserting the parents' k-mers");
 }
@@ -127,6 +133,10 @@ static void host_record(trio_t *T, const cli_rec_t *rec, int tag)
     for (int64_t e = 0; e < len; ++e) {
         uint64_t key;
         if (!cli_kroll_push(&R, s[e], &key)) continue;
+        if (tag && T->reads) {
+            if (cli_kcount_add(&T->kc, key, tag - 1) < 0) trio_overflow(T);
+            continue;
+        }
         if (tag) {
             const int r = host_insert(T, key, (uint64_t)tag);
             if (r < 0) trio_overflow(T);
@@ -160,6 +170,7 @@ static void host_file(trio_t *T, const char *path, int tag)
 static void usage(FILE *fp)
 {
     fprintf(fp, "Usage: cornetto trioeval [options] <pat.fasta> <mat.fasta> <assembly.fasta> [assembly2.fasta ...]\n");
+    fprintf(fp, "       cornetto trioeval [options] --pat-reads <pat.fastq> [...] --mat-reads <mat.fastq> [...] <assembly.fasta> [assembly2.fasta ...]\n");
     fprintf(fp, "switch error and Hamming error of phased assemblies against the k-mers of the two parents (or truth haplotypes): a position\n");
     fprintf(fp, "whose k-mer only one parent holds is a marker; a switch is a marker whose type differs from the marker in front of it in\n");
     fprintf(fp, "the contig, the Hamming error of a contig is its minority markers.  FASTA or FASTQ, plain, gzip or BGZF.\n");
@@ -167,7 +178,12 @@ static void usage(FILE *fp)
     fprintf(fp, "   -P FILE                    a further paternal file (may be repeated)\n");
     fprintf(fp, "   -M FILE                    a further maternal file (may be repeated)\n");
     fprintf(fp, "   -c FILE                    write the per-contig table to FILE (one assembly only)\n");
-    fprintf(fp, "   --slots INT                slots of the k-mer table, 8 bytes each [twice the bases of the parents]\n");
+    fprintf(fp, "   --pat-reads FILE           the paternal k-mers are those of these reads from --min-count occurrences upward (may be repeated);\n");
+    fprintf(fp, "   --mat-reads FILE           the same for the mother; both are needed, and every positional argument is then an assembly\n");
+    fprintf(fp, "   --min-count INT[,INT]      with reads: a k-mer counts from INT occurrences, 1 to 65535; one value for both parents or pat,mat [2]\n");
+    fprintf(fp, "   --hist FILE                with reads: write the k-mer count histograms, count<TAB>pat<TAB>mat for counts 1 to 1023 (the last line: 1023 and more)\n");
+    fprintf(fp, "   --slots INT                slots of the k-mer table, 8 bytes each, 16 with reads [twice the bases of the parents;\n");
+    fprintf(fp, "                              about 1.5 times the expected distinct k-mers is the usual figure]\n");
     fprintf(fp, "   --accel=no                 run on the host\n");
     fprintf(fp, "   -h                         help\n");
 }
@@ -181,11 +197,14 @@ static void usage_fail(const char *msg)
 
 int trioeval_main(int argc, char *argv[])
 {
-    static const struct option lo[] = {{"help", no_argument, 0, 'h'}, {"slots", required_argument, 0, 1000}, {"accel", required_argument, 0, 1001}, {0, 0, 0, 0}};
-    const char *k_arg = "21", *c_arg = NULL, *slots_arg = NULL;
+    static const struct option lo[] = {{"help", no_argument, 0, 'h'}, {"slots", required_argument, 0, 1000}, {"accel", required_argument, 0, 1001},
+                                       {"min-count", required_argument, 0, 1002}, {"hist", required_argument, 0, 1003}, {"pat-reads", required_argument, 0, 1004},
+                                       {"mat-reads", required_argument, 0, 1005}, {0, 0, 0, 0}};
+    const char *k_arg = "21", *c_arg = NULL, *slots_arg = NULL, *mc_arg = NULL, *hist_arg = NULL;
     /* the parental files in reading order: the <pat.fasta> argument, the -P files, <mat.fasta>, the -M files */
-    const char **pat = (const char **)cli_xmalloc(2 * ((size_t)argc + 1) * sizeof(char *)), **mat = pat + argc + 1;
-    int n_pat = 1, n_mat = 1, c, li = 0;
+    const char **pat_mem = (const char **)cli_xmalloc(4 * ((size_t)argc + 1) * sizeof(char *)), **pat = pat_mem, **mat = pat + argc + 1;
+    const char **pat_reads = mat + argc + 1, **mat_reads = pat_reads + argc + 1;
+    int n_pat = 1, n_mat = 1, n_pr = 0, n_mr = 0, c, li = 0;
     FILE *fp_help = stderr;
     optind = 1;
     while ((c = getopt_long(argc, argv, "k:P:M:c:h", lo, &li)) >= 0) {
@@ -194,6 +213,10 @@ int trioeval_main(int argc, char *argv[])
         else if (c == 'M') mat[n_mat++] = optarg;
         else if (c == 'c') c_arg = optarg;
         else if (c == 1000) slots_arg = optarg;
+        else if (c == 1002) mc_arg = optarg;
+        else if (c == 1003) hist_arg = optarg;
+        else if (c == 1004) pat_reads[n_pr++] = optarg;
+        else if (c == 1005) mat_reads[n_mr++] = optarg;
         else if (c == 1001) {
             if (!strcmp(optarg, "no") || !strcmp(optarg, "n")) cli_host_set(1);
             else if (!strcmp(optarg, "yes") || !strcmp(optarg, "y")) cli_host_set(0);
@@ -205,15 +228,42 @@ int trioeval_main(int argc, char *argv[])
         usage(stdout);
         exit(EXIT_SUCCESS);
     }
-    if (argc - optind < 3) {
+    const int reads = n_pr > 0 || n_mr > 0;
+    if (reads && !(n_pr > 0 && n_mr > 0)) usage_fail("--pat-reads and --mat-reads go together: the reads of both parents are needed");
+    if (!reads && (mc_arg || hist_arg)) usage_fail("--min-count and --hist go with --pat-reads / --mat-reads: a parental assembly holds every k-mer once");
+    if (reads && (n_pat > 1 || n_mat > 1)) usage_fail("-P and -M name further parental assemblies; they do not go with --pat-reads / --mat-reads");
+    if (argc - optind < (reads ? 1 : 3)) {
         usage(stderr);
         exit(EXIT_FAILURE);
     }
-    pat[0] = argv[optind];
-    mat[0] = argv[optind + 1];
-    char **asms = argv + optind + 2;
-    const int n_asm = argc - optind - 2;
+    /* with parental reads every positional is an assembly and the files that fill the table are the reads */
+    if (reads) {
+        pat = pat_reads;
+        mat = mat_reads;
+        n_pat = n_pr;
+        n_mat = n_mr;
+    } else {
+        pat[0] = argv[optind];
+        mat[0] = argv[optind + 1];
+    }
+    char **asms = argv + optind + (reads ? 0 : 2);
+    const int n_asm = argc - optind - (reads ? 0 : 2);
     char *end = NULL;
+    int min_count[2] = {2, 2};
+    if (mc_arg) {
+        errno = 0;
+        const long long a = strtoll(mc_arg, &end, 10);
+        long long b = a;
+        const char *second = *end == ',' ? end + 1 : NULL;
+        if (end == mc_arg || (*end && !second)) usage_fail("--min-count: one number from 1 to 65535, or two as pat,mat");
+        if (second) {
+            b = strtoll(second, &end, 10);
+            if (*end || end == second) usage_fail("--min-count: one number from 1 to 65535, or two as pat,mat");
+        }
+        if (errno || a < 1 || a > CORNETTO_KSET_COUNT_CAP || b < 1 || b > CORNETTO_KSET_COUNT_CAP) usage_fail("--min-count: one number from 1 to 65535, or two as pat,mat");
+        min_count[0] = (int)a;
+        min_count[1] = (int)b;
+    }
     const long long k = strtoll(k_arg, &end, 10);
     if (*end || end == k_arg || k < 11 || k > 31 || !(k & 1)) usage_fail("-k: k is an odd number from 11 to 31");
     if (c_arg && n_asm != 1) usage_fail("-c takes one assembly");
@@ -235,10 +285,16 @@ int trioeval_main(int argc, char *argv[])
     memset(&T, 0, sizeof(T));
     T.k = (int)k;
     T.slots = (int64_t)slots;
+    T.reads = reads;
     const int host = cli_host_mode();
     cornetto_accel_t *h = NULL;
     int64_t stats[3] = {0, 0, 0};
-    if (host) {
+    if (host && reads) {
+        if (cli_kcount_init(&T.kc, T.slots, 2) != 0) {
+            CLI_ERROR("a k-mer table of %lld slots wants %lld bytes: give a smaller one with --slots", slots, slots * 16);
+            exit(EXIT_FAILURE);
+        }
+    } else if (host) {
         T.tab = (size_t)slots > SIZE_MAX / 8 ? NULL : (uint64_t *)malloc((size_t)slots * 8);
         if (!T.tab) {
             CLI_ERROR("a k-mer table of %lld slots wants %lld bytes: give a smaller one with --slots", slots, slots * 8);
@@ -247,7 +303,7 @@ int trioeval_main(int argc, char *argv[])
         memset(T.tab, 0xFF, (size_t)slots * 8);
     } else {
         h = cli_accel_open();
-        const int rc = cornetto_kset_open(h, T.k, T.slots, &T.set);
+        const int rc = reads ? cornetto_kset_open_counted(h, T.k, T.slots, 2, &T.set) : cornetto_kset_open(h, T.k, T.slots, &T.set);
         if (rc == CORNETTO_E_NOMEM) {
             CLI_ERROR("%s: give a smaller one with --slots", cornetto_accel_last_error(h));
             exit(EXIT_FAILURE);
@@ -261,13 +317,40 @@ int trioeval_main(int argc, char *argv[])
         else stream_records_on(h, path, 1, parent_scan, &T);
     }
     if (host) {
-        stats[0] = T.h_pos;
-        stats[1] = T.h_distinct;
+        stats[0] = reads ? T.kc.pos : T.h_pos;
+        stats[1] = reads ? T.kc.distinct : T.h_distinct;
     } else {
         cornetto_kset_stats(T.set, stats);
     }
-    fprintf(stderr, "[trioeval] parents: %lld records, %lld bases, %lld k-mers, %lld distinct, k=%d\n", (long long)T.p_recs, (long long)T.p_bases, (long long)stats[0],
-            (long long)stats[1], T.k);
+    if (reads) {
+        /* the histograms first, then the seal: from here on the table is the tagged set of the solid k-mers */
+        if (hist_arg) {
+            int64_t hist[2][CORNETTO_KSET_HIST_BINS];
+            for (int ch = 0; ch < 2; ++ch) {
+                if (host) cli_kcount_hist(&T.kc, ch, hist[ch]);
+                else cli_accel_check(h, cornetto_kset_hist(h, T.set, ch, hist[ch]), "trioeval: the histogram of the k-mer counts");
+            }
+            FILE *fh = cli_fopen_chk(hist_arg, "w");
+            for (int i = 1; i < CORNETTO_KSET_HIST_BINS; ++i) fprintf(fh, "%d\t%lld\t%lld\n", i, (long long)hist[0][i], (long long)hist[1][i]);
+            if (fclose(fh) != 0) {
+                CLI_ERROR("%s", "writing the --hist file failed");
+                exit(EXIT_FAILURE);
+            }
+        }
+        const int32_t m32[2] = {min_count[0], min_count[1]};
+        int64_t solid[2] = {0, 0};
+        if (host) {
+            cli_kcount_seal(&T.kc, min_count, solid);
+            T.tab = T.kc.tab;
+        } else {
+            cli_accel_check(h, cornetto_kset_seal(h, T.set, m32, solid), "trioeval: sealing the k-mer counts");
+        }
+        fprintf(stderr, "[trioeval] parent reads: %lld records, %lld bases, %lld k-mers, %lld distinct, %lld pat solid, %lld mat solid (count >= %d,%d), k=%d\n",
+                (long long)T.p_recs, (long long)T.p_bases, (long long)stats[0], (long long)stats[1], (long long)solid[0], (long long)solid[1], min_count[0], min_count[1], T.k);
+    } else {
+        fprintf(stderr, "[trioeval] parents: %lld records, %lld bases, %lld k-mers, %lld distinct, k=%d\n", (long long)T.p_recs, (long long)T.p_bases, (long long)stats[0],
+                (long long)stats[1], T.k);
+    }
 
     T.fc = c_arg ? cli_fopen_chk(c_arg, "w") : NULL;
     if (T.fc) fprintf(T.fc, "#contig\tlength\tkmers\tpat\tmat\tpp\tpm\tmp\tmm\n");
@@ -289,6 +372,6 @@ int trioeval_main(int argc, char *argv[])
     }
     if (T.set) cornetto_kset_free(h, T.set);
     free(T.tab);
-    free(pat);
+    free(pat_mem);
     return EXIT_SUCCESS;
 }

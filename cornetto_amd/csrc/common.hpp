@@ -160,6 +160,7 @@ enum {   // device workspace slots
     WS_DF_STAGE, WS_DF_SIZE, WS_DF_TOTAL,
     WS_KQ_CNT, WS_KQ_MAP, WS_KQ_ROWS,
     WS_KT_CNT, WS_KT_MAP,
+    WS_KC_HIST,
     WS_COUNT
 };
 static_assert(WS_COUNT <= 80, "cornetto_accel::dev has 80 slots");

@@ -123,35 +123,7 @@ __global__ void __launch_bounds__(256) kq_run_emit(const unsigned long long *__r
 
 extern "C" {
 
-int cornetto_kset_open(cornetto_accel_t *h, int32_t k, int64_t slots, cornetto_kset_t **out)
-{
-    if (!h || !out || slots < 1) return cn_fail(h, CORNETTO_E_ARG, "kset_open: bad argument");
-    *out = nullptr;
-    if (!kq_k_ok(k)) return cn_fail(h, CORNETTO_E_UNSUPPORTED, "kset_open: k = %d; k is odd, 11 to 31", (int)k);
-    CN_HIP(h, hipSetDevice(h->device));
-    if (slots > ((int64_t)1 << 59)) return cn_fail(h, CORNETTO_E_NOMEM, "kset_open: a table of %lld slots wants more than 2^62 bytes", (long long)slots);
-    cornetto_kset_t *s = new (std::nothrow) cornetto_kset;
-    if (!s) return cn_fail(h, CORNETTO_E_NOMEM, "kset_open: host allocation failed");
-    s->k = k;
-    s->slots = slots;
-    s->stats[2] = slots;
-    if (hipMalloc((void **)&s->d_tab, (size_t)slots * 8) != hipSuccess || hipMalloc((void **)&s->d_stat, 64) != hipSuccess) {
-        (void)hipGetLastError();
-        if (s->d_tab) (void)hipFree(s->d_tab);
-        delete s;
-        return cn_fail(h, CORNETTO_E_NOMEM, "kset_open: a table of %lld slots wanted %lld bytes of device memory", (long long)slots, (long long)slots * 8);
-    }
-    // every slot empty, whatever the memory held: on the handle's stream, in front of the first insert
-    const hipError_t e1 = hipMemsetAsync(s->d_tab, 0xFF, (size_t)slots * 8, h->stream), e2 = hipMemsetAsync(s->d_stat, 0, 64, h->stream);
-    if (e1 != hipSuccess || e2 != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) {
-        (void)hipFree(s->d_tab);
-        (void)hipFree(s->d_stat);
-        delete s;
-        return cn_fail(h, CORNETTO_E_HIP, "kset_open: the table could not be cleared");
-    }
-    *out = s;
-    return CORNETTO_OK;
-}
+int cornetto_kset_open(cornetto_accel_t *h, int32_t k, int64_t slots, cornetto_kset_t **out) { return kq_open(h, "kset_open", k, slots, 0, out); }
 
 void cornetto_kset_free(cornetto_accel_t *h, cornetto_kset_t *s)
 {
@@ -159,6 +131,7 @@ void cornetto_kset_free(cornetto_accel_t *h, cornetto_kset_t *s)
     if (h) (void)hipSetDevice(h->device);
     if (s->d_tab) (void)hipFree(s->d_tab);
     if (s->d_stat) (void)hipFree(s->d_stat);
+    if (s->d_cnt) (void)hipFree(s->d_cnt);
     if (s->d_tiles) (void)hipFree(s->d_tiles);
     s->pref.release();
     delete s;
@@ -173,6 +146,7 @@ void cornetto_kset_stats(const cornetto_kset_t *s, int64_t *stats)
 int cornetto_kset_add(cornetto_accel_t *h, cornetto_kset_t *s, const cornetto_asm_t *truth)
 {
     if (!h || !s || !truth) return cn_fail(h, CORNETTO_E_ARG, "kset_add: bad argument");
+    if (s->counted) return cn_fail(h, CORNETTO_E_UNSUPPORTED, "kset_add: the set is counted (kset_count); it takes no keys without a count");
     if (s->mode == KSET_TAGGED) return cn_fail(h, CORNETTO_E_UNSUPPORTED, "kset_add: the set is tagged (kset_add_tag); a set is either plain or tagged");
     if (s->dead) return cn_fail(h, CORNETTO_E_NOMEM, "kset_add: the table of %lld slots has overflowed; the set is unusable", (long long)s->slots);
     s->mode = KSET_PLAIN;
@@ -206,6 +180,7 @@ int cornetto_kset_query(cornetto_accel_t *h, const cornetto_kset_t *cs, const co
         *runs = nullptr;
         *n_runs = 0;
     }
+    if (s->mode == KSET_COUNTED) return cn_fail(h, CORNETTO_E_UNSUPPORTED, "kset_query: the set is counted and not sealed yet (kset_seal)");
     if (s->mode == KSET_TAGGED) return cn_fail(h, CORNETTO_E_UNSUPPORTED, "kset_query: the set is tagged; its query is kset_phase");
     if (s->dead) return cn_fail(h, CORNETTO_E_ARG, "kset_query: the set is unusable, its table has overflowed");
     // the runs are placed by 32-bit ranks: at most one run per two positions and one more per contig

@@ -14,6 +14,7 @@
 //   kq_lookup()   the same walk with plain loads; a key is missing at the first EMPTY slot or after `slots` steps;
 //   kq_bit()      word and mask of position `pos` of a contig whose first tile is `tile0` in the bitmap (KQ_TILE bits per tile).
 //   kq_insert_tag(), kq_lookup_tag()   the same table with a 2-bit tag in bits 63:62 of a slot, for `cornetto trioeval` (ktrio.hip): below.
+//   kq_deal(), kq_insert_at(), kq_bump(), kq_hist_bin(), kq_seal_word()   the counted table of `qv -r` / `trioeval --pat-reads` (kcount.hip): at the end.
 // The empty slot is ~0: no key, k <= 31 makes every key smaller than 2^62.
 #pragma once
 #include <cstdint>
@@ -132,18 +133,28 @@ KQ_HD static inline uint64_t kq_mulhi(uint64_t a, uint64_t b)
 KQ_HD static inline uint64_t kq_home(uint64_t key, uint64_t slots) { return kq_mulhi(kq_mix(key), slots); }   // < slots
 KQ_HD static inline uint64_t kq_next(uint64_t slot, uint64_t slots) { return slot + 1 == slots ? 0 : slot + 1; }
 
+// the walk of kq_insert(); `at` = the slot the key sits in (untouched on KQ_FULL), which the counted table of kcount.hip adds its count at
 template <class Cas, class Stop>
-KQ_HD static inline int kq_insert(uint64_t *tab, uint64_t slots, uint64_t key, Cas cas, Stop stop)
+KQ_HD static inline int kq_insert_at(uint64_t *tab, uint64_t slots, uint64_t key, Cas cas, Stop stop, uint64_t &at)
 {
     uint64_t slot = kq_home(key, slots);
     for (uint64_t step = 0; step < slots; ++step) {
         const uint64_t old = cas(tab + slot, KQ_EMPTY, key);
-        if (old == KQ_EMPTY) return KQ_NEW;
-        if (old == key) return KQ_PRESENT;
+        if (old == KQ_EMPTY || old == key) {
+            at = slot;
+            return old == key ? KQ_PRESENT : KQ_NEW;
+        }
         if ((step & 1023) == 1023 && stop()) return KQ_FULL;
         slot = kq_next(slot, slots);
     }
     return KQ_FULL;
+}
+
+template <class Cas, class Stop>
+KQ_HD static inline int kq_insert(uint64_t *tab, uint64_t slots, uint64_t key, Cas cas, Stop stop)
+{
+    uint64_t at;
+    return kq_insert_at(tab, slots, key, cas, stop, at);
 }
 
 KQ_HD static inline bool kq_lookup(const uint64_t *tab, uint64_t slots, uint64_t key)
@@ -216,5 +227,70 @@ KQ_HD static inline void kq_bit(int64_t tile0, int64_t pos, int64_t &word, uint6
 KQ_HD static inline uint64_t kq_starts(uint64_t w, uint64_t prev) { return w & ~((w << 1) | (prev & 1)); }
 KQ_HD static inline uint64_t kq_ends(uint64_t w, uint64_t next) { return w & ~((w >> 1) | ((next & 1) << 63)); }
 KQ_HD static inline uint32_t kq_end_rank(uint32_t rank, uint64_t w, uint64_t prev) { return rank - (uint32_t)(prev & w & 1); }
+
+// ---- the counted table of `cornetto qv -r` and `cornetto trioeval --pat-reads / --mat-reads` (kcount.hip; include/cornetto_accel.h states the
+// rule).  The table of keys is the plain one above; beside it stand channels * slots uint32_t counts, count[ch * slots + slot] for the key in
+// `slot`.  Sealing with thresholds turns the table into the plain or the tagged one in place, so kq_lookup() / kq_lookup_tag() and the kernels
+// around them serve a sealed set unchanged.
+//   kq_deal()       the decomposition of a batch of (short) records: lanes are dealt runs, not records.  first[c] = sum over the records in front
+//                   of c of ceil(len / KQ_RUN); run g of the batch is run g - first[c] of its record c = kq_record_of(), the bases [b0, b1) of it, with
+//                   b1 <= len: kq_lead() + kq_step() on them read seq[max(b0 - k + 1, 0) .. b1), never a byte outside the record;
+//   kq_bump()       one occurrence into a count that must never wrap: the add is issued only while a load of the count reads below
+//                   CORNETTO_KSET_COUNT_CAP.  Counts only grow, so (1) while fewer than CAP occurrences have been added every load reads below CAP
+//                   and no add is skipped: a true count below CAP is stored exactly; (2) if the stored value ended below CAP, every load would
+//                   have read below CAP and every add would have been issued, so a true count of CAP or more ends at CAP or more.  Hence
+//                   min(stored, CAP) = min(true, CAP), whatever the order.  (3) An add is issued only by a lane whose load read below CAP; after the
+//                   value reaches CAP only the lanes that loaded before that still add, so stored < CAP + lanes in flight on the device
+//                   (< 2^20 on 256 CUs of 2048 lanes) — far from 2^32, also across launches, since every launch starts from a stored value
+//                   that obeys the same bound and a value of CAP or more admits no new add;
+//   kq_count_of()   min(stored, CAP): the count of the rule;
+//   kq_hist_bin()   min(count, BINS - 1): the histogram bin of a key, 0 for a key this channel never saw;
+//   kq_seal_word()  the slot's word after sealing: `tag` = bit ch set iff the key is solid in channel ch.  One channel: the key, or KQ_TOMB.  Two:
+//                   key | tag << 62, or KQ_TOMB for tag 0.
+// KQ_TOMB = KQ_EMPTY - 1 = 2^64 - 2 marks an occupied slot whose key is solid nowhere: a walk passes it (only KQ_EMPTY ends a walk, so keys behind
+// a removed one stay reachable) and no key matches it.  kq_lookup() compares the whole word, and every key is below 2^62.  kq_lookup_tag() compares
+// under KQ_KEYMASK, where the tombstone reads 2^62 - 2: for k < 31 every key is below 2^58; for k = 31 the code 2^62 - 2 is T...TG, whose reverse
+// complement CA...A = 2^60 is smaller, so the canonical code of that k-mer is 2^60 and 2^62 - 2 is never a key.  No sealed word equals KQ_EMPTY
+// (kq_insert_tag's argument above) and none but the tombstone equals KQ_TOMB: that would take tag 3 and the key 2^62 - 2.
+constexpr uint64_t KQ_TOMB = KQ_EMPTY - 1;
+constexpr uint32_t KQ_CAP = CORNETTO_KSET_COUNT_CAP;
+constexpr int KQ_BINS = CORNETTO_KSET_HIST_BINS;
+static_assert((uint32_t)(KQ_BINS - 1) <= KQ_CAP, "the last bin lies at or below the cap: min(stored, BINS - 1) is the bin of min(stored, CAP)");
+
+KQ_HD static inline int64_t kq_runs_of(int64_t len) { return (len + KQ_RUN - 1) / KQ_RUN; }
+
+// the record c with first[c] <= g < first[c + 1] (first[0] = 0 <= g < first[n]; records without a run are skipped): tiles.hpp's bisection
+KQ_HD static inline int kq_record_of(const int64_t *first, int n, int64_t g)
+{
+    int lo = 0, hi = n;   // first[lo] <= g < first[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (first[mid] <= g) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// run j of a record of `len` bases -> its bases [b0, b1)
+KQ_HD static inline void kq_deal(int64_t j, int64_t len, int64_t &b0, int64_t &b1)
+{
+    b0 = j * KQ_RUN;
+    b1 = b0 + KQ_RUN < len ? b0 + KQ_RUN : len;
+}
+
+template <class Load, class Add>
+KQ_HD static inline void kq_bump(uint32_t *c, Load load, Add add)
+{
+    if (load(c) < KQ_CAP) add(c);
+}
+
+KQ_HD static inline uint32_t kq_count_of(uint32_t stored) { return stored < KQ_CAP ? stored : KQ_CAP; }
+KQ_HD static inline int kq_hist_bin(uint32_t stored) { return stored < (uint32_t)(KQ_BINS - 1) ? (int)stored : KQ_BINS - 1; }
+
+KQ_HD static inline uint64_t kq_seal_word(uint64_t key, int channels, int tag)
+{
+    if (!tag) return KQ_TOMB;
+    return channels == 1 ? key : key | (uint64_t)tag << KQ_TAG_SHIFT;
+}
 
 }  // namespace

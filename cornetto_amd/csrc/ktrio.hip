@@ -162,6 +162,7 @@ extern "C" {
 int cornetto_kset_add_tag(cornetto_accel_t *h, cornetto_kset_t *s, const cornetto_asm_t *a, int32_t tag)
 {
     if (!h || !s || !a || (tag != CORNETTO_TRIO_PAT && tag != CORNETTO_TRIO_MAT)) return cn_fail(h, CORNETTO_E_ARG, "kset_add_tag: bad argument (the tag is 1, pat, or 2, mat)");
+    if (s->counted) return cn_fail(h, CORNETTO_E_UNSUPPORTED, "kset_add_tag: the set is counted (kset_count); it takes no keys without a count");
     if (s->mode == KSET_PLAIN) return cn_fail(h, CORNETTO_E_UNSUPPORTED, "kset_add_tag: the set is plain (kset_add); a set is either plain or tagged");
     if (s->dead) return cn_fail(h, CORNETTO_E_NOMEM, "kset_add_tag: the table of %lld slots has overflowed; the set is unusable", (long long)s->slots);
     s->mode = KSET_TAGGED;
@@ -190,6 +191,7 @@ int cornetto_kset_add_tag(cornetto_accel_t *h, cornetto_kset_t *s, const cornett
 int cornetto_kset_phase(cornetto_accel_t *h, cornetto_kset_t *s, const cornetto_asm_t *a, int64_t *counts)
 {
     if (!h || !s || !a || (a->n > 0 && !counts)) return cn_fail(h, CORNETTO_E_ARG, "kset_phase: bad argument");
+    if (s->mode == KSET_COUNTED) return cn_fail(h, CORNETTO_E_UNSUPPORTED, "kset_phase: the set is counted and not sealed yet (kset_seal)");
     if (s->mode == KSET_PLAIN) return cn_fail(h, CORNETTO_E_UNSUPPORTED, "kset_phase: the set is plain; its query is kset_query");
     if (s->dead) return cn_fail(h, CORNETTO_E_ARG, "kset_phase: the set is unusable, its table has overflowed");
     CN_HIP(h, hipSetDevice(h->device));

@@ -118,6 +118,7 @@ constexpr WsRow ws_table[] = {
     WS_SCR(WS_DF_STAGE), WS_SCR(WS_DF_SIZE), WS_SCR(WS_DF_TOTAL),
     WS_SCR(WS_KQ_CNT), WS_SCR(WS_KQ_MAP), WS_SCR(WS_KQ_ROWS),
     WS_SCR(WS_KT_CNT), WS_SCR(WS_KT_MAP),
+    WS_SCR(WS_KC_HIST),
 };
 #undef WS_ROW
 #undef WS_SCR

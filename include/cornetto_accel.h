@@ -876,6 +876,42 @@ int cornetto_kset_query(cornetto_accel_t *h, const cornetto_kset_t *s, const cor
 void cornetto_kset_free(cornetto_accel_t *h, cornetto_kset_t *s);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Counted k-mer sets: the truth of `cornetto qv -r` and `cornetto trioeval --pat-reads / --mat-reads` from READS, whose k-mers are evidence only
+ * from a count threshold upward (Merqury works this way; the reference's protocol builds `yak` indexes of parental reads, docs/protocol.md:292-308;
+ * parity with either is unpinned).  Extraction is the rule of `cornetto qv` above, unchanged: the same valid bytes, canonical code and positions.
+ * THE RULE:
+ *   - a counted set has `channels` = 1 or 2.  Channel 0 is the truth of `qv`; for `trioeval`, channel 0 is pat and channel 1 is mat;
+ *   - count[ch][key] = min(occurrences of key at the positions of every record counted into channel ch, CORNETTO_KSET_COUNT_CAP): an integer that
+ *     does not depend on batch boundaries, on the order of the records or on the order of the probes;
+ *   - hist[ch][c], c = 1 .. CORNETTO_KSET_HIST_BINS - 1: the number of distinct keys with min(count[ch][key], BINS - 1) == c.  Bin 0 is unused and
+ *     stays 0; the last bin collects every count from BINS - 1 up;
+ *   - sealing with thresholds m[ch] >= 1: key x is SOLID in ch iff count[ch][x] >= m[ch]; S_ch = the solid keys of channel ch, solid[ch] = |S_ch|.
+ *     With one channel the set becomes the plain set S_0, and cornetto_kset_query() answers exactly as a plain set filled with S_0 would.  With two
+ *     it becomes the tagged set with tag = (x in S_0 ? PAT : 0) | (x in S_1 ? MAT : 0); keys with tag 0 are absent, and cornetto_kset_phase()
+ *     answers as a tagged set built from S_0 and S_1 would;
+ *   - hence with m = 1 and every record counted once, the result is that of cornetto_kset_add() / cornetto_kset_add_tag() on the same records.
+ * The state machine; a call out of order returns CORNETTO_E_UNSUPPORTED, a null object CORNETTO_E_ARG: kset_count and kset_hist only before the
+ * seal, kset_query (one channel) and kset_phase (two) only after it, kset_add and kset_add_tag never on a counted set, kset_seal once.  A set whose
+ * table has overflowed refuses everything, as a plain one does.
+ * On the device (csrc/kcount.hip, kqv.hpp): the table of `qv` with channels * slots uint32_t counts beside it (12 or 16 bytes per slot), added
+ * with one atomic per k-mer; lanes are dealt runs of the batch's records, not records, so 150-base reads fill the waves; sealing rewrites the
+ * table in place and frees the counts, a key that is solid nowhere leaves a tombstone that no key equals and every walk passes.
+ * ------------------------------------------------------------------------------------------------- */
+#define CORNETTO_KSET_COUNT_CAP 65535
+#define CORNETTO_KSET_HIST_BINS 1024
+/* cornetto_kset_open() for a counted set of `channels` (1 or 2, else CORNETTO_E_ARG) channels: the table emptied and the counts zeroed on the
+ * handle's stream, whatever the memory held.  CORNETTO_E_NOMEM: the message says how many bytes were wanted (8 + 4 * channels per slot). */
+int cornetto_kset_open_counted(cornetto_accel_t *h, int32_t k, int64_t slots, int32_t channels, cornetto_kset_t **out);
+/* the k-mers of every record of `reads` counted into `channel` (kq_count); may be called repeatedly, once per batch of a streamer.  Overflow as
+ * in cornetto_kset_add(): CORNETTO_E_NOMEM, the set is unusable, never a hang.  cornetto_kset_stats(): positions counted (all channels), distinct
+ * keys counted, slots. */
+int cornetto_kset_count(cornetto_accel_t *h, cornetto_kset_t *s, const cornetto_asm_t *reads, int32_t channel);
+/* hist[0 .. CORNETTO_KSET_HIST_BINS) of `channel` (kq_hist) */
+int cornetto_kset_hist(cornetto_accel_t *h, cornetto_kset_t *s, int32_t channel, int64_t *hist);
+/* min_count[0 .. channels), each 1 .. CORNETTO_KSET_COUNT_CAP (else CORNETTO_E_ARG); solid[0 .. channels) (kq_seal).  The counts are freed. */
+int cornetto_kset_seal(cornetto_accel_t *h, cornetto_kset_t *s, const int32_t *min_count, int64_t *solid);
+
+/* ---------------------------------------------------------------------------------------------------
  * Switch and Hamming error of a phased assembly against parental k-mers: `cornetto trioeval`.  An EXTENSION (the reference's protocol runs
  * `yak trioeval pat.yak mat.yak asm.fa` at this step, docs/protocol.md:292-308; yak works from read k-mer counts with thresholds, this works
  * from parental or truth-haplotype ASSEMBLIES, as `cornetto qv hg002.mat.fa -t hg002.pat.fa` does; parity with yak is unpinned).  THE RULE:
