@@ -164,6 +164,7 @@ def lib(dev=False):
         raise ImportError("%s is missing: run `make -C cornetto_amd` (or __graft_entry__.build()); "
                           "there is no fallback implementation" % path)
     L = C.CDLL(path)
+    L.path = path
     vp, i32, i64, cp = C.c_void_p, C.c_int32, C.c_int64, C.c_char_p
     pp = C.POINTER(vp)
     sig = {
@@ -482,6 +483,7 @@ class Accel:
 
     def __init__(self, device=0, stream=None, dev=False):
         self.L = lib(dev)
+        self.lib_path = self.L.path                     # the library this handle runs: LIB_PATH, or DEV_LIB_PATH with dev=True
         h = C.c_void_p()
         rc = self.L.cornetto_accel_open(C.byref(h), device, stream)
         if rc != 0:
@@ -814,12 +816,13 @@ class Accel:
         self._chk(self.L.cornetto_sdust_asm_end(self.h, asm.ptr, T, W, C.byref(p), C.byref(n)))
         return _take(self.L, p, n.value, IVL_DT)
 
-    def sdust_stats(self, asm, T=20, W=64):
+    def sdust_stats(self, asm, T=20, W=64, intervals=False):
         """one extra sdust pass with the counting build of the kernel -> its counters as a dict (see
-        cornetto_accel_sdust_stats() in include/cornetto_accel.h); None for parameters the production kernel does not take"""
+        cornetto_accel_sdust_stats() in include/cornetto_accel.h); None for parameters the production kernel does not take.
+        intervals=True: -> (that, the intervals of the counting pass)"""
         self.L.cornetto_accel_sdust_stats(self.h, 1, None, 0)
         try:
-            self.sdust(asm, T, W)
+            ivls = self.sdust(asm, T, W)
         finally:
             out = np.zeros(256, dtype=np.uint64)
             n = self.L.cornetto_accel_sdust_stats(self.h, 0, out.ctypes.data, 256)
@@ -827,19 +830,21 @@ class Accel:
         waves = s[254]
         if n > 207 and s[206]:
             # the sift / resolve kernel (csrc/sdust_sift.hpp): positions after each filter, steps of the stepping stages
-            return {"kernel": "sd_sift", "chunks": s[255], "tiles_of_64_bases": s[206], "positions_ct_above_T10": s[203], "after_L1": s[204], "after_L2": s[205],
+            st = {"kernel": "sd_sift", "chunks": s[255], "tiles_of_64_bases": s[206], "positions_ct_above_T10": s[203], "after_L1": s[204], "after_L2": s[205],
                     "resolve_steps": s[200], "resolve_window_reads": s[201], "dp_tiles": s[208], "passes_with_candidates": s[202], "base_by_base_steps_of_chunks_with_other_bytes": s[207],
                     "window_reads_behind_a_gap_of": {"2": s[209], "3-4": s[210], "5-8": s[211]} if n > 211 else None}
+            return (st, ivls) if intervals else st
         if not waves or not s[2]:
-            return None
+            return (None, ivls) if intervals else None
         hist = []
         for b in range(32):
             w = s[16 + 4 * b]
             if w:
                 hist.append({"ms": [b * 0.5, b * 0.5 + 0.5], "waves": w, "jobs": s[18 + 4 * b], "find_perfect": s[19 + 4 * b], "find_perfect_with_candidates": s[17 + 4 * b]})
-        return {"waves": waves, "chunks": s[255], "chunks_sampled_low_complexity": s[7], "wave_steps": s[2], "find_perfect_calls": s[3],
+        st = {"waves": waves, "chunks": s[255], "chunks_sampled_low_complexity": s[7], "wave_steps": s[2], "find_perfect_calls": s[3],
                 "find_perfect_with_candidates": s[10], "plain_groups": s[4], "wave_ms_avg": round(s[5] / waves / 1e5, 3), "wave_ms_max": round(s[6] / 1e5, 3),
                 "queue_fetch_rounds_per_wave": round(s[11] / waves, 1), "wave_time_histogram": hist}
+        return (st, ivls) if intervals else st
 
     # ---- panel interval stage ---------------------------------------------------------------------
     def cov_select_merged(self, cov, lo, hi, low_mq, edge_len, min_ctg_len, boring, merge_dist=1000, min_len=30000):

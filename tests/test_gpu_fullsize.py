@@ -26,13 +26,14 @@ def _make(lens, seed, profile="uniform", coverage=True, dev=False):
     import torch
     from cornetto_amd import synth
     import cornetto_amd
-    dev = torch.device("cuda", 0)
-    bases, offs = synth.make_assembly(torch, dev, lens, seed, profile)
+    tdev = torch.device("cuda", 0)
+    bases, offs = synth.make_assembly(torch, tdev, lens, seed, profile)
     depth = mq = None
     if coverage:
-        depth, mq = synth.make_coverage(torch, dev, lens, offs, seed)
+        depth, mq = synth.make_coverage(torch, tdev, lens, offs, seed)
     torch.cuda.synchronize()
     acc = cornetto_amd.Accel(0, dev=dev)                  # dev: the development build of the library (the CORNETTO_SDUST_* switches exist there only)
+    assert acc.lib_path == (cornetto_amd.DEV_LIB_PATH if dev else cornetto_amd.LIB_PATH), acc.lib_path
     asm = acc.asm_wrap(bases.data_ptr(), offs, np.array(lens, dtype=np.int64))
     cov = acc.cov_wrap(depth.data_ptr(), mq.data_ptr(), offs, np.array(lens, dtype=np.int32)) if coverage else None
     return dict(torch=torch, acc=acc, asm=asm, cov=cov, lens=lens, offs=offs, bases=bases, depth=depth, mq=mq)

@@ -51,14 +51,13 @@ import pytest
 
 import oracle_bind as ob
 from helpers import fmt_sdust, ref_sdust
+from sift_cases import ACGT, OTHER, _first_diff, _pick, _repeat      # (shared with the planted cases of the fast path)
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REFSO = os.path.join(ROOT, "oracle", "_ref", "libcornetto_ref.so")
 REFCLI = os.path.join(ROOT, "oracle", "_ref", "cornetto")
-ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
-OTHER = np.frombuffer(b"NNNnRYKMSWBDHVryk", dtype=np.uint8)      # N and IUPAC letters: all of them 4 in seq_nt4_table
 
 K_G = [(40, 258), (70, 514), (70, 515), (80, 530), (110, 777), (150, 1025), (150, 1026)]
 K_256 = [(20, 67), (20, 100), (25, 130), (30, 200), (40, 256), (40, 257)]
@@ -96,27 +95,6 @@ def _chunk_value(chunk, W):
 
 def _n_chunks(seqs, c):
     return sum((len(s) + c - 1) // c for s in seqs)
-
-
-def _repeat(rng, n, p, subst):
-    """n bases of a random unit of p letters (no homopolymer unless p = 1), with about 2 % substitutions when asked"""
-    while True:
-        u = ACGT[rng.integers(0, 4, size=p)]
-        if p == 1 or len(set(u.tolist())) > 1:
-            break
-    r = np.resize(u, n).copy()
-    if subst and n >= 20:
-        pos = rng.choice(n, size=max(1, n // 50), replace=False)
-        r[pos] = ACGT[(np.searchsorted(ACGT, r[pos]) + rng.integers(1, 4, size=len(pos))) % 4]
-    return r
-
-
-def _pick(rng, T, W, n_lo=60, n_hi=110):
-    """length and period of a planted repeat that the pair masks: a period-p array of k words scores about k / (2 p) per word, and k is at
-    most the window's W - 2: p <= 5 k / (1.3 T), at most k / 2 (every word at least twice in the window) and at most 7"""
-    n = int(rng.integers(n_lo, n_hi + 1))
-    k = min(n, W) - 2
-    return n, int(rng.integers(1, max(1, min(7, k // 2, int(5 * k / (1.3 * max(T, 1))))) + 1))
 
 
 class _Case:
@@ -318,13 +296,6 @@ def _gpu(acc, seqs, T, W):
         return [(int(x["ctg"]), int(x["start"]), int(x["finish"])) for x in acc.sdust(asm, T, W)]
     finally:
         asm.close()
-
-
-def _first_diff(got, exp):
-    for i, (g, e) in enumerate(zip(got, exp)):
-        if g != e:
-            return "interval %d: device %r, expected %r" % (i, g, e)
-    return "device %d intervals, expected %d; the first one side lacks: %r" % (len(got), len(exp), (got + exp)[min(len(got), len(exp)):][:1])
 
 
 # ---- 1. oracle-exact -------------------------------------------------------------------------------------------------------------------
