@@ -34,6 +34,13 @@
 //            the same wave with the same lane <-> age state, from the warm-up start sd_find_start() gives: the reference's loop
 //            (:139-157) with its flush at a non-base and the window that lives on across it (P slots are keyed by start VALUE:
 //            while a run is shorter than W behind a non-base the window start stands still and the slots do not age).
+// The carried seam (SIFT_GROUP below; tools/sim/sdust_sift_sim.c, argument `group`, checks it the same way): a wave takes a group of
+// consecutive chunks, and where chunk k + 1 follows chunk k in one contig and both hold plain letters, the two tiles in front of k + 1 are
+// not sifted again: the 64 count bytes and the 64 sifted bits of k's last tile are taken over.  ct, L1 and L2 are local functions of the
+// sequence, so the counts are the exact ones; and the bits k computed with exact counts behind them are a subset of what the redone tile
+// gives (its L1 / L2 look back into 255-filled bytes: a superset) and still a superset of the positions at which something is inserted —
+// which is all the resolve stage asks of the sift.  Staging, the unclean test, the resolve stage's start W - 2 steps in front of the chunk
+// with an empty P, the rows and the recording rule are untouched.  The full argument stands where the seam is taken out of the buffer.
 #pragma once
 
 struct SiftArgs {
@@ -52,7 +59,7 @@ struct SiftArgs {
     const uint32_t *order;
     uint32_t *walk_out;
     uint32_t *iswalk_out;
-    uint32_t *counter;        // [SIFT_NCTR * 16], zero before the launch: counter c (at index 16 c) hands out the chunks c + j SIFT_NCTR
+    uint32_t *counter;        // [SIFT_NCTR * 16], zero before the launch: counter c (at index 16 c) hands out the groups c + j SIFT_NCTR
     int32_t thr, lmin;        // equal words a last word needs (T / 10 + 1); shortest l with 10 l (l + 1) / 2 > T l, capped at 16
     int32_t abl;              // development aid (CORNETTO_SIFT_ABL): 1 no resolve, 2 no L1 / L2, 4 no tiles: timing only, results are wrong
     int32_t dp_min;           // a tile with at least this many sifted positions is resolved end-parallel (dp tile); 65: never (CORNETTO_SIFT_DP)
@@ -63,6 +70,12 @@ struct SiftArgs {
 #define SIFT_WPB 1               // waves (= chunks) per workgroup; the waves share nothing
 #endif
 constexpr int SIFT_NCTR = 64;    // chunk counters, 64 bytes apart
+// A counter request hands out a GROUP of this many consecutive positions of the hand-out order (order[] where there is one, chunk ids
+// otherwise), and the wave works through them front to back: where two of them are neighbouring chunks of plain letters in one contig,
+// the second takes the seam tile over from the first instead of redoing it (see "the carried seam" in sd_sift).
+#ifndef SIFT_GROUP
+#define SIFT_GROUP 4
+#endif
 constexpr int SIFT_PAD = 16;     // positions in front of the word / count buffer (look-back of L1 / L2 below offset 0)
 #ifndef SIFT_K
 #define SIFT_K 16                // L2: partial sums over this many counts, the exact walk over the suffixes of up to this many words
@@ -212,7 +225,11 @@ __global__ __launch_bounds__(64 * SIFT_WPB) __attribute__((amdgpu_waves_per_eu(C
     const int LS = CAPW - 1 < SIFT_LS ? CAPW - 1 : SIFT_LS;
     const bool long_ok = CAPW - 1 > LS;               // suffixes longer than the walk exist
     // statistics build: counted per wave, added up once at the end
-    unsigned long long st_steps = 0, st_jumps = 0, st_cand = 0, st_trig = 0, st_l1 = 0, st_l2 = 0, st_walk = 0, st_tiles = 0, st_dp = 0, st_g2 = 0, st_g4 = 0, st_g8 = 0;
+    unsigned long long st_steps = 0, st_jumps = 0, st_cand = 0, st_trig = 0, st_l1 = 0, st_l2 = 0, st_walk = 0, st_tiles = 0, st_dp = 0, st_g2 = 0, st_g4 = 0, st_g8 = 0, st_carry = 0;
+    // The carried seam (wave-uniform): the chunk this wave finished last, if it left something to take over — it took the sift path and its
+    // region ends with a whole tile inside the contig; -2: nothing (it was walked, it ended its contig, a new group has begun).  One register:
+    // whatever else the next chunk needs to know of it is read from the chunk table again.
+    int pv_k = -2;
 
     struct Meta {
         SdChunk ch;
@@ -249,7 +266,8 @@ __global__ __launch_bounds__(64 * SIFT_WPB) __attribute__((amdgpu_waves_per_eu(C
         return d;
     };
 
-  auto process = [&](const int k, const Meta &M, const Data &D) {
+  // seam: chunk k is chunk pv_k + 1 of the same contig and starts where that one ended
+  auto process = [&](const int k, const Meta &M, const Data &D, const bool seam) {
     const SdChunk ch = M.ch;
     const int len = M.len;
     const uint8_t *seq = M.seq;
@@ -260,6 +278,33 @@ __global__ __launch_bounds__(64 * SIFT_WPB) __attribute__((amdgpu_waves_per_eu(C
     const bool islast = ch.end == len;
     const int rec_from = ch.start;
 
+    // ---- the carried seam ---------------------------------------------------------------------------------------------
+    // The two tiles in front of a chunk rebuild what the wave that finished the chunk before held a moment earlier: tile 0 only feeds tile 1's
+    // "tile before" tables, tile 1 is sifted in full (table OR, three gathers, counts, its triggers through L1 / L2).  None of it depends on
+    // the chunk: ct, L1 and L2 are local functions of the sequence.  When THIS wave has just finished chunk k - 1 on the sift path, the 64 count
+    // bytes of that chunk's last tile (one per lane) and its 64 sifted bits (uniform) are still in the buffer: they are taken out here, before
+    // the buffer is staged again, and put back where tile 1 would have written them once the staging has shown that this chunk holds letters
+    // only.  Staging itself is unchanged — the whole region with the 128 bases in front is loaded, checked and staged.  Then tile 0 is not
+    // run at all and tile 1 only ORs its words into the equal-word tables (tile 2 counts against them); everything from tile 2 on is as ever.
+    // Exact, because (header) the resolve stage needs the exact words — staged as ever — and ANY superset of the inserting positions:
+    //   * the carried counts are the exact counts: chunk k - 1 counted its last tile against its own tile before, inside the contig;
+    //   * redone, tile 1's L1 / L2 look back into the 255-filled count bytes of tile 0, which yields a superset of the inserting positions
+    //     among its 64; chunk k - 1 sifted the same 64 positions with the exact counts behind them: a subset of that superset and still a
+    //     superset of the inserting positions (its own resolve stage rests on it).
+    // Tile 0's count bytes stay 0 as staged; nobody reads them: L1 / L2 of tile 2 look back SIFT_K - 1 positions, into tile 1.
+    // (They wait in the upper halves of the two lists, which are empty between chunks and which staging does not touch: held in registers
+    // across the staging they cost the tile loop what it does not have.)
+    if (seam) {
+        const SdChunk pc = A.chunks[k - 1];
+        const int pt = ((pc.end - pc.start + (pc.start > 0 ? 128 : 0)) >> 6) - 1;      // the last tile of its region
+        const uint32_t cnt = wc[2 * (pt * 64 + lane) + 1];
+        const uint2 bits = *reinterpret_cast<const uint2 *>(&sb[2 * pt]);
+        SD_LDS_ORDER();
+        tl[64 + lane] = (uint16_t)cnt;
+        if (lane == 0) *reinterpret_cast<uint2 *>(&tl2[64]) = bits;
+        SD_LDS_ORDER();
+    }
+    pv_k = -2;
     // ---- stage the words of the region --------------------------------------------------------------------------------
     tab[lane] = 0;
     tab[64 + lane] = 0;
@@ -474,6 +519,7 @@ __global__ __launch_bounds__(64 * SIFT_WPB) __attribute__((amdgpu_waves_per_eu(C
     }
 
     typedef __attribute__((address_space(3))) uint32_t lds_u32;
+    const bool carried = seam && abl == 0;            // both chunks hold letters only: the seam tile is taken over, not redone
     int ntl = 0, ntl2 = 0;                            // (uniform) entries in the two lists
 #ifdef SIFT_L2_ADAPT
     int l2_hot = 0, l2_skipped = 0;                   // (uniform) consecutive full L2 batches that kept nearly everything; L1 batches sifted without L2 since
@@ -627,7 +673,7 @@ __global__ __launch_bounds__(64 * SIFT_WPB) __attribute__((amdgpu_waves_per_eu(C
     // ---- the tiles ---------------------------------------------------------------------------------------------------
     // PAR: parity of the tile (which pair of tables is "this tile").  GENERAL: lanes without a word (the first two positions of
     // a contig, behind its end) stay out of the tables.  TABLE_ONLY: the first tile in front of a chunk.
-    uint8_t *pq = wc + 2 * lane;                      // this lane's position in the current tile
+    uint8_t *pq = wc + 2 * lane + (carried ? 256 : 0);   // this lane's position in the current tile (the seam carried: tile 2 is the first)
     // the three table addresses of a tile, one shift-add each (written out: the compiler shares the shift and pays an add per base, one of them
     // the addition of the block's LDS offset, which is zero)
     const uint32_t tab_a = (uint32_t)(uintptr_t)(lds_u32 *)tab, mine0_a = (uint32_t)(uintptr_t)(lds_u32 *)mine0, mine1_a = (uint32_t)(uintptr_t)(lds_u32 *)mine1,
@@ -691,16 +737,31 @@ __global__ __launch_bounds__(64 * SIFT_WPB) __attribute__((amdgpu_waves_per_eu(C
         using P0 = std::integral_constant<int, 0>;
         using P1 = std::integral_constant<int, 1>;
         int q = 0;
-        if (halo) tile(P0{}, std::false_type{}, std::true_type{}, q++);        // (a halo lies inside the contig: every lane has a word)
-        else tile(P0{}, std::true_type{}, std::false_type{}, q++);
+        if (carried) {
+            // Tile 1 as a table-only pass (a halo of plain letters: every lane has a word); its counts and sifted bits put back.  Its words go
+            // into the tables of parity 0 and tile 2 runs as a tile of parity 1: which pair of tables is "this tile" only has to alternate, and
+            // with the parities swapped a carried chunk enters the pairs below as they are (an eighth instance of the tile, for an even tile in
+            // front of the pairs, cost the literal-size build two vector registers it does not have).
+            (void)__hip_atomic_fetch_or(lds_at((uint32_t)pq[-128], mine0_a), mybit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            pq[-127] = (uint8_t)tl[64 + lane];
+            if (lane == 0) *reinterpret_cast<uint2 *>(&sb[2]) = *reinterpret_cast<const uint2 *>(&tl2[64]);
+            if (STATS) ++st_carry;
+            SD_LDS_ORDER();
+            q = 2;
+        } else if (halo) {
+            tile(P0{}, std::false_type{}, std::true_type{}, q++);        // (a halo lies inside the contig: every lane has a word)
+        } else {
+            tile(P0{}, std::true_type{}, std::false_type{}, q++);
+        }
         // pairs of whole tiles, then what is left: at most one whole tile and the contig's last, partial one
         for (; q + 1 < ntile - 1; q += 2) {
             tile(P1{}, std::false_type{}, std::false_type{}, q);
             tile(P0{}, std::false_type{}, std::false_type{}, q + 1);
         }
-        if (q < ntile - 1) { tile(P1{}, std::false_type{}, std::false_type{}, q); ++q; }
+        bool p1_next = true;                          // (the parity of the tile that is next: not that of q when the seam was carried)
+        if (q < ntile - 1) { tile(P1{}, std::false_type{}, std::false_type{}, q); ++q; p1_next = false; }
         if (q < ntile) {
-            if (q & 1) tile(P1{}, std::true_type{}, std::false_type{}, q);
+            if (p1_next) tile(P1{}, std::true_type{}, std::false_type{}, q);
             else tile(P0{}, std::true_type{}, std::false_type{}, q);
         }
     }
@@ -994,13 +1055,16 @@ __global__ __launch_bounds__(64 * SIFT_WPB) __attribute__((amdgpu_waves_per_eu(C
             if (STATS) st_tiles += (unsigned long long)ntile;
         }
     }
+    // what the next chunk of the group may take over: the region's last tile, when it is a whole one that ends with the chunk inside the contig
+    pv_k = !islast && !(rlen & 63) && abl == 0 ? k : -2;
   };
 
     // The waves stay (as many as the caller lets this kernel hold of the chip: the other stream needs its share) and take
-    // chunks from SIFT_NCTR counters — counter c hands out the chunks c, c + SIFT_NCTR, c + 2 SIFT_NCTR, ... (a repeat array is
-    // spread over all of them); a wave starts at counter (its number mod SIFT_NCTR) and moves on when one runs dry.  One counter
+    // groups of SIFT_GROUP chunks from SIFT_NCTR counters — counter c hands out the groups c, c + SIFT_NCTR, c + 2 SIFT_NCTR, ... (a repeat
+    // array is spread over all of them); a wave starts at counter (its number mod SIFT_NCTR) and moves on when one runs dry.  One counter
     // for everything took 14 ns per request: 1.8 M chunks = 25 ms.  The request for the next index is in flight while the
-    // current chunk is worked on.
+    // current group is worked on.  Group g holds the positions g SIFT_GROUP .. of the hand-out order: the chunks order[] puts first (walked
+    // chunks, chunks inside arrays) stay at the front; they never take a seam over.
     int c = (int)((blockIdx.x * SIFT_WPB + wave) % SIFT_NCTR), dry = 0;
     auto ask = [&](int cc) {
         uint32_t v = 0;
@@ -1008,37 +1072,57 @@ __global__ __launch_bounds__(64 * SIFT_WPB) __attribute__((amdgpu_waves_per_eu(C
         return v;
     };
     uint32_t nxt = ask(c);
+    static_assert(SIFT_GROUP >= 1 && !(SIFT_GROUP & (SIFT_GROUP - 1)), "a group ends where the position is a multiple of its size");
+    int p = 0;                                        // the position of the hand-out order that is next; a multiple of the group size, or all of them taken: ask for a group
     for (;;) {
-        const long long kk = (long long)__builtin_amdgcn_readfirstlane((int)nxt) * SIFT_NCTR + c;
-        if (kk >= A.n_chunks) {
-            // This counter is dry: a look at ALL of them at once, lane <-> counter (round 5; before: one request after the other at the next
-            // counter until SIFT_NCTR of them had come back dry — at the end of the kernel every wave's 64 dependent atomic round trips, 7168 waves
-            // on each address: 0.1 ms of a launch whatever its size, a seventh of the kernel of a 1/8 share).  Counters only grow, so one read at
-            // or above its limit is final; one read below it is asked as before.
-            static_assert(SIFT_NCTR == 64, "one lane per counter");
-            if (dry < 2 * SIFT_NCTR) {
-                const uint32_t seen = __hip_atomic_load(&A.counter[lane * 16], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const long long left = (long long)A.n_chunks - lane;                    // counter `lane` hands out lane, lane + 64, ...: (left + 63) / 64 of them
-                const unsigned long long open = sd_ballot(left > 0 && (long long)seen < (left + SIFT_NCTR - 1) / SIFT_NCTR);
-                if (!open) break;
-                ++dry;                                                                  // (a wave loses the race for a counter's last chunk once per counter at most)
-                const int from = c + 1 == SIFT_NCTR ? 0 : c + 1;
-                const unsigned long long rot = from ? (open >> from) | (open << (SIFT_NCTR - from)) : open;
-                c = (from + __builtin_ctzll(rot)) & (SIFT_NCTR - 1);
+        if (!(p & (SIFT_GROUP - 1)) || p >= A.n_chunks) {
+            // (the group count, and below the lane's counter address and limit, from values the compiler cannot see through: as loop invariants
+            // they are computed in front of the chunk loop and hold two scalar and four vector registers through every tile for a path taken
+            // once per wave)
+            int nch = A.n_chunks;
+            asm volatile("" : "+s"(nch));
+            const int n_groups = (int)(((long long)nch + SIFT_GROUP - 1) / SIFT_GROUP);
+            const long long kk = (long long)__builtin_amdgcn_readfirstlane((int)nxt) * SIFT_NCTR + c;
+            if (kk >= n_groups) {
+                // This counter is dry: a look at ALL of them at once, lane <-> counter (round 5; before: one request after the other at the next
+                // counter until SIFT_NCTR of them had come back dry — at the end of the kernel every wave's 64 dependent atomic round trips, 7168 waves
+                // on each address: 0.1 ms of a launch whatever its size, a seventh of the kernel of a 1/8 share).  Counters only grow, so one read at
+                // or above its limit is final; one read below it is asked as before.
+                static_assert(SIFT_NCTR == 64, "one lane per counter");
+                if (dry < 2 * SIFT_NCTR) {
+                    int lane_c = lane;
+                    asm volatile("" : "+v"(lane_c));
+                    const uint32_t seen = __hip_atomic_load(&A.counter[lane_c * 16], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const long long left = (long long)n_groups - lane_c;                    // counter `lane` hands out lane, lane + 64, ...: (left + 63) / 64 of them
+                    const unsigned long long open = sd_ballot(left > 0 && (long long)seen < (left + SIFT_NCTR - 1) / SIFT_NCTR);
+                    if (!open) break;
+                    ++dry;                                                                  // (a wave loses the race for a counter's last group once per counter at most)
+                    const int from = c + 1 == SIFT_NCTR ? 0 : c + 1;
+                    const unsigned long long rot = from ? (open >> from) | (open << (SIFT_NCTR - from)) : open;
+                    c = (from + __builtin_ctzll(rot)) & (SIFT_NCTR - 1);
+                    nxt = ask(c);
+                    continue;
+                }
+                // (not seen: reads that keep showing an open counter.  The exhaustive way: SIFT_NCTR dry answers in a row, one counter after the other)
+                if (++dry >= 3 * SIFT_NCTR) break;
+                c = c + 1 == SIFT_NCTR ? 0 : c + 1;
                 nxt = ask(c);
                 continue;
             }
-            // (not seen: reads that keep showing an open counter.  The exhaustive way: SIFT_NCTR dry answers in a row, one counter after the other)
-            if (++dry >= 3 * SIFT_NCTR) break;
-            c = c + 1 == SIFT_NCTR ? 0 : c + 1;
+            dry = 0;
             nxt = ask(c);
-            continue;
+            p = (int)kk * SIFT_GROUP;
+            pv_k = -2;                                // (a seam is carried inside a group only)
         }
-        dry = 0;
-        nxt = ask(c);
-        const int ko = A.order ? __builtin_amdgcn_readfirstlane((int)A.order[kk]) : (int)kk;
+        const int ko = A.order ? __builtin_amdgcn_readfirstlane((int)A.order[p]) : p;
         const Meta m = meta(ko);
-        process(ko, m, fetch(m));
+        bool seam = false;
+        if (ko == pv_k + 1) {                         // (then ko >= 1)
+            const SdChunk pc = A.chunks[ko - 1];
+            seam = pc.ctg == m.ch.ctg && pc.end == m.ch.start;
+        }
+        process(ko, m, fetch(m), seam);
+        ++p;
     }
     if (STATS && O.stats && lane == 0) {
         atomicAdd(&O.stats[0], st_steps);
@@ -1053,5 +1137,7 @@ __global__ __launch_bounds__(64 * SIFT_WPB) __attribute__((amdgpu_waves_per_eu(C
         atomicAdd(&O.stats[9], st_g2);
         atomicAdd(&O.stats[10], st_g4);
         atomicAdd(&O.stats[11], st_g8);
+        atomicAdd(&O.stats[12], st_carry);
+        atomicMax(&O.stats[13], (unsigned long long)SIFT_GROUP);
     }
 }

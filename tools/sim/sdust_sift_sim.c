@@ -15,8 +15,20 @@
  *   Chunks that see a non-ACGT byte within [start - 2W, end) are left to the sequential model ("slow path" = what
  *   sdust_w64 computes: the reference's process, recorded by save time).
  *
+ *
+ * The carried seam (argument `group`).  With group = 0 the sifted positions S are one global set, as above.
+ * With group >= 1 the sift is modelled the way the kernel runs it, per chunk, over the chunk's own region [start - 128, end):
+ *   redone   (every chunk at group = 1; the first chunk of a group; behind a slow chunk) the first 64 positions of the region only
+ *            feed the equal-word tables and get the count 255 ("unknown, large"), the next 64 are sifted with exact counts; their
+ *            L1 / L2 sums look back into the 255s, which can only keep MORE positions: a superset of the inserting positions.
+ *   carried  (chunk k + 1 of a group, both clean, k at least 64 bases) the 64 positions in front of the chunk are not sifted at
+ *            all: their counts and their sifted bits are what chunk k computed for its last 64 positions.  The counts are the
+ *            exact ones; the bits are chunk k's superset of the inserting positions.  The positions in front of those 64 keep
+ *            the count 0 that staging leaves: nothing reads it (L1 / L2 look back 15 positions from the chunk's first).
+ * Either way the resolve stage starts W - 2 steps in front of the chunk with an empty P and takes the chunk's own set.
+ *
  * build: gcc -O2 -o /tmp/sift_sim tools/sim/sdust_sift_sim.c oracle/oracle.c -Ioracle -lm -lz
- * usage: /tmp/sift_sim [n_bases] [seeds] [T] [W] [chunk]
+ * usage: /tmp/sift_sim [n_bases] [seeds] [T] [W] [chunk] [mode] [group]
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -122,6 +134,7 @@ static void sequential_by_time(const uint8_t *seq, int len, int T, int W, ivlv_t
 
 /* ---- the new decomposition ---------------------------------------------------------------------------------- */
 static unsigned long long st_pos, st_k1, st_k2a, st_k2, st_k3steps, st_k3cand, st_k3ins, st_hot;
+static unsigned long long st_seams, st_carried, st_lk2, st_lextra;
 
 int main(int argc, char **argv)
 {
@@ -131,6 +144,7 @@ int main(int argc, char **argv)
     const int W = argc > 4 ? atoi(argv[4]) : 64;
     const int chunk = argc > 5 ? atoi(argv[5]) : 1792;
     const int mode = argc > 6 ? atoi(argv[6]) : 0;       /* 0 mixed, 1 pure random, 2 repeat rich */
+    const int group = argc > 7 ? atoi(argv[7]) : 0;      /* 0 one global sift; G >= 1: per chunk, the seam carried inside groups of G chunks */
     const int CAPW = W - 2;
     const int thr = T / 10 + 1;                          /* c > T / 10 */
     int bad = 0;
@@ -228,8 +242,12 @@ int main(int argc, char **argv)
             }
             if (shortc || (ok16 && CAPW - 1 > LS)) { S[i] = 1; ++st_k2; }
         }
-        free(ct);
         /* K3 per chunk */
+        uint8_t *Sl = calloc(n + 64, 1);                    /* the chunk's own sifted set (group >= 1) */
+        int *cl = calloc(n + 64, sizeof(int));              /* ... and its count bytes */
+        uint8_t pS[64];
+        int pc[64], prev_ok = 0;                            /* what the chunk before left of its last 64 positions */
+        const uint8_t *Sx = group ? Sl : S;
         ivlv_t got = {0, 0, 0}, seqall = {0, 0, 0};
         sequential_by_time(seq, n, T, W, &seqall);
         for (int k = 0; k < nch; ++k) {
@@ -237,7 +255,44 @@ int main(int argc, char **argv)
             if (slow[k]) {
                 for (int64_t q = 0; q < seqall.n; ++q)
                     if (seqall.a[q].tm >= cs && (seqall.a[q].tm < ce || (last && seqall.a[q].tm == n))) push(&got, seqall.a[q].s, seqall.a[q].f);
+                prev_ok = 0;
                 continue;
+            }
+            if (group) {
+                const int rb = cs > 128 ? cs - 128 : 0, halo = rb > 0;
+                const int carried = group > 1 && k % group != 0 && prev_ok && halo;
+                if (k) ++st_seams;
+                st_carried += carried;
+                for (int i = rb; i < ce; ++i) {
+                    if (halo && i < rb + 64) cl[i] = carried ? 0 : 255;
+                    else if (carried && i < cs) cl[i] = pc[i - (cs - 64)];
+                    else cl[i] = ct[i];
+                    Sl[i] = carried && i >= cs - 64 && i < cs ? pS[i - (cs - 64)] : 0;
+                }
+#define CNT(p) ((p) >= rb ? cl[p] : halo ? 255 : 0)
+                for (int i = halo ? (carried ? cs : rb + 64) : 2; i < ce; ++i) {
+                    if (!isw[i] || cl[i] < thr) continue;
+                    int sum = 0, ok = 1, ok16 = 1;
+                    for (int kk = 1; kk <= 16; ++kk) {
+                        sum += CNT(i - (kk - 1));
+                        if (!(10 * sum > T * kk)) { if (kk <= K1n) ok = 0; ok16 = 0; }
+                    }
+                    if (!ok) continue;
+                    int keep = CAPW - 1 < LS || i - LS < 2;      /* a short window: no L2; a position without a word among the sixteen: kept */
+                    if (!keep) {
+                        int c[64] = {0}, r = 0;
+                        for (int a = 0; a <= LS; ++a) {
+                            r += c[word[i - a]]++;
+                            if (a >= 1 && r * 10 > T * a) keep = 1;
+                        }
+                        if (ok16 && CAPW - 1 > LS) keep = 1;
+                    }
+                    if (keep) { Sl[i] = 1; ++st_lk2; st_lextra += !S[i]; }
+                }
+#undef CNT
+                /* what the next chunk may take over: the last 64 positions, all of them sifted by THIS chunk with exact counts */
+                prev_ok = ce - cs >= 64 && !last;
+                if (prev_ok) for (int j = 0; j < 64; ++j) { pS[j] = Sl[ce - 64 + j]; pc[j] = cl[ce - 64 + j]; }
             }
             /* lane <-> age arrays */
             int w[64], r[64], sr[64], sl[64];                /* slot: r, l (l = 0: empty) */
@@ -245,7 +300,7 @@ int main(int argc, char **argv)
             memset(sl, 0, sizeof sl); memset(sr, 0, sizeof sr);
             const int i0 = cs == 0 ? 2 : cs - W + 2;
             for (int i = i0 < 2 ? 2 : i0; i < ce; ++i) {
-                if (!S[i]) continue;
+                if (!Sx[i]) continue;
                 ++st_k3steps;
                 const int amax = i - 2 < CAPW - 1 ? i - 2 : CAPW - 1;
                 if (!have || i - cur != 1) {
@@ -317,10 +372,13 @@ int main(int argc, char **argv)
                     break;
                 }
         }
-        free(seq); free(word); free(isw); free(slow); free(bad_prefix); free(S); free(got.a); free(seqall.a); orc_free(ref);
+        free(seq); free(word); free(isw); free(slow); free(bad_prefix); free(S); free(ct); free(Sl); free(cl); free(got.a); free(seqall.a); orc_free(ref);
     }
     printf("T %d W %d chunk %d: words %llu, K1 %.4f %%, L1 %.4f %%, L2 = S %.4f %%, K3 steps %llu with candidates %llu, insertions %llu\n",
            T, W, chunk, st_pos, 100.0 * st_k1 / st_pos, 100.0 * st_k2a / st_pos, 100.0 * st_k2 / st_pos, st_k3steps, st_k3cand, st_k3ins);
+    if (group)
+        printf("group %d: seams between clean chunks %llu, carried %llu; chunk-local sifted positions %llu, of them outside the global set %llu\n",
+               group, st_seams, st_carried, st_lk2, st_lextra);
     (void)st_hot;
     return bad != 0;
 }
