@@ -2,10 +2,12 @@
 // the product object of this file is empty, tests/test_abi.py looks for the prefix in both libraries).  tests/test_gpu_scan.py
 // (tests/selftest_bind.py) compares them with numpy on inputs the product entry points cannot produce: prepared tile states for the
 // look-back, full-range values, strides and counter sets at more than one tile, epochs next to the wrap.  cn_selftest_ws_fill sets the
-// contents of the handle's workspaces between two calls (tests/test_gpu_ws_fill.py: no stage depends on what they held).  Not part of the C ABI: no
+// contents of the handle's workspaces between two calls (tests/test_gpu_ws_fill.py: no stage depends on what they held); cn_selftest_telo_marks brings the
+// mark bitmap of the telofind pass to the host (tests/test_gpu_telofind_seams.py compares it word by word).  Not part of the C ABI: no
 // declaration in include/cornetto_accel.h.  Every entry takes host pointers, allocates, copies and synchronises by itself.
 #ifdef CN_DEV
 #include "common.hpp"
+#include "internal.hpp"
 #include "ivlmerge.hpp"
 #include "scan.hpp"
 #include "sort.hpp"
@@ -340,6 +342,31 @@ int cn_selftest_sort_pairs(cornetto_accel_t *h, const unsigned long long *keys, 
     CN_HIP(h, hipStreamSynchronize(h->stream));
     cn_timing_end(h);
     return CORNETTO_OK;
+}
+
+// cn_telo_marks_impl itself (internal.hpp: what cornetto_telo_ends builds its regions from), the words brought to the host: a motif without a
+// border takes tf_scan's own marks in its count-only mode, one with a border or beyond the automaton the marked runs.  words_out[0 .. n_words):
+// the contigs back to back, every contig from a multiple of 64 bits, n_words = the sum of ceil(len / 64) — anything else is CORNETTO_E_ARG
+int cn_selftest_telo_marks(cornetto_accel_t *h, const cornetto_asm_t *a, const char *motif, unsigned long long *words_out, int64_t n_words)
+{
+    if (!h || !a || !motif || n_words < 0 || (n_words > 0 && !words_out)) return cn_fail(h, CORNETTO_E_ARG, "selftest_telo_marks: bad argument");
+    int64_t want = 0;
+    for (int32_t c = 0; c < a->n; ++c) want += ((int64_t)a->len[c] + 63) / 64;
+    if (n_words != want) return cn_fail(h, CORNETTO_E_ARG, "selftest_telo_marks: %lld words asked for, the assembly has %lld", (long long)n_words, (long long)want);
+    CN_HIP(h, hipSetDevice(h->device));
+    cn_timing_begin(h);
+    const unsigned long long *d_marks = nullptr;
+    const int rc = [&]() -> int {
+        CN_TRY(cn_telo_marks_impl(h, a, motif, &d_marks));
+        if (n_words > 0) {
+            if (!d_marks) return cn_fail(h, CORNETTO_E_HIP, "selftest_telo_marks: no marks");
+            CN_HIP(h, hipMemcpyAsync(words_out, d_marks, (size_t)n_words * 8, hipMemcpyDeviceToHost, h->stream));
+        }
+        CN_HIP(h, hipStreamSynchronize(h->stream));
+        return CORNETTO_OK;
+    }();
+    cn_timing_end(h);                                  // (on an error as well: the events go back to the pool)
+    return rc;
 }
 
 }  // extern "C"

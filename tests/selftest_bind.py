@@ -1,6 +1,7 @@
 """ctypes binding of the cn_selftest_* entry points (cornetto_amd/csrc/selftest.hip, bgrun.hip): the scan primitives of wave.hpp /
 scan.hpp / ivlmerge.hpp on their own, and the hook that sets the contents of a handle's workspaces (cn_selftest_ws_fill), in the DEVELOPMENT
-build of the library only.  Not part of the C ABI; used by test_gpu_scan.py, test_gpu_ws_fill.py and test_ws_table.py.
+build of the library only.  Not part of the C ABI; used by test_gpu_scan.py, test_gpu_ws_fill.py, test_ws_table.py and test_gpu_telofind_seams.py (the mark bitmap of the
+telofind pass, cn_selftest_telo_marks).
 Every function takes an `Accel(0, dev=True)` (the `dacc` fixture) and numpy arrays."""
 import ctypes as C
 
@@ -29,6 +30,7 @@ def _lib():
         "cn_selftest_merge_fused": [vp, vp, i64, i64, i32, vp, C.POINTER(i64)],
         "cn_selftest_scan_u64": [vp, vp, i64, C.POINTER(C.c_uint64)],
     }
+    sig["cn_selftest_telo_marks"] = [vp, vp, C.c_char_p, vp, i64]
     sig["cn_selftest_ws_fill"] = [vp, C.c_int, vp, vp, C.c_int, vp, C.c_int]
     sig["cn_selftest_ws_class"] = [C.c_int, C.POINTER(C.c_char_p)]
     for name, args in sig.items():
@@ -175,3 +177,11 @@ def scan_u64(acc, v):
     tot = C.c_uint64(0)
     acc._chk(_lib().cn_selftest_scan_u64(acc.h, _p(io), io.size, C.byref(tot)))
     return io, int(tot.value)
+
+
+def telo_marks(acc, asm, motif, n_words):
+    """cn_telo_marks_impl over the resident assembly `asm` of this handle: the first n_words = sum of ceil(len / 64) words of the mark bitmap,
+    the contigs back to back from multiples of 64 bits (uint64)"""
+    out = np.empty(n_words, dtype=np.uint64)
+    acc._chk(_lib().cn_selftest_telo_marks(acc.h, asm.ptr, motif, _p(out), n_words))
+    return out
