@@ -88,6 +88,7 @@ class FqSeqOpt(C.Structure):
     _fields_ = [("min_len", C.c_int32), ("records", C.c_int32), ("window", C.c_int64)]
 
 
+KSET_CN_BINS = 6  # CORNETTO_KSET_CN_BINS: the copy-number classes of Kset.spectrum()
 KSET_COUNT_CAP, KSET_HIST_BINS = 65535, 1024  # CORNETTO_KSET_COUNT_CAP, CORNETTO_KSET_HIST_BINS: the counted sets of Accel.kset(channels=1 or 2)
 KQV_TILE = 4096  # CORNETTO_KQV_TILE: bases per workgroup of kq_insert / kq_query (tests plant seams at its multiples)
 FQSEQ_TILE = 16384  # CORNETTO_FQSEQ_TILE: output bytes per workgroup of fqseq_text (checked against the library when it is loaded)
@@ -312,6 +313,9 @@ def lib(dev=False):
         "cornetto_kset_count": (C.c_int, [vp, vp, vp, i32]),
         "cornetto_kset_hist": (C.c_int, [vp, vp, i32, C.POINTER(i64)]),
         "cornetto_kset_seal": (C.c_int, [vp, vp, C.POINTER(i32), C.POINTER(i64)]),
+        "cornetto_kset_copies": (C.c_int, [vp, vp, vp]),
+        "cornetto_kset_copies_clear": (C.c_int, [vp, vp]),
+        "cornetto_kset_spectrum": (C.c_int, [vp, vp, i32, i32, C.POINTER(i64), C.POINTER(i64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)          # AttributeError if the library does not export a declared symbol
@@ -408,7 +412,8 @@ class _Resident:
 
 class Kset:
     """a set of canonical k-mers resident in HBM (cornetto_kset_*): Accel.kset(k, slots); with channels = 1 or 2 a counted set, which takes
-    count() and hist() until seal() makes it the plain (1 channel) or the tagged (2) set that query() / phase() probe"""
+    count() and hist() until seal() makes it the plain (1 channel) or the tagged (2) set that query() / phase() probe; a counted set of one
+    channel also takes copies(), copies_clear() and spectrum() before its seal: completeness and the copy-number spectrum of an assembly"""
 
     def __init__(self, acc, ptr, k, slots, channels=0):
         self.acc, self.ptr, self.k, self.slots, self.channels = acc, ptr, k, slots, channels
@@ -422,6 +427,22 @@ class Kset:
         out = np.zeros(KSET_HIST_BINS, dtype=np.int64)
         self.acc._chk(self.acc.L.cornetto_kset_hist(self.acc.h, self.ptr, channel, out.ctypes.data_as(C.POINTER(C.c_int64))))
         return out
+
+    def copies(self, asm):
+        """the k-mers of every contig of the resident assembly into the copy counts of a one-channel counted set, before its seal
+        (cornetto_kset_copies); a k-mer the reads never held takes a slot with count 0; status -4 when the table overflowed"""
+        self.acc._chk(self.acc.L.cornetto_kset_copies(self.acc.h, self.ptr, asm.ptr))
+
+    def copies_clear(self):
+        """every copy count back to 0; the keys stay (cornetto_kset_copies_clear)"""
+        self.acc._chk(self.acc.L.cornetto_kset_copies_clear(self.acc.h, self.ptr))
+
+    def spectrum(self, min_count, channel=0):
+        """-> (int64[6, 1024], solid, found): spec[a, c] = keys with min(copies, 5) == a and min(count, 1023) == c; solid = keys with count >=
+        min_count, found = those of them with a copy (cornetto_kset_spectrum)"""
+        spec, tot = np.zeros((KSET_CN_BINS, KSET_HIST_BINS), dtype=np.int64), (C.c_int64 * 2)()
+        self.acc._chk(self.acc.L.cornetto_kset_spectrum(self.acc.h, self.ptr, channel, int(min_count), spec.ctypes.data_as(C.POINTER(C.c_int64)), tot))
+        return spec, int(tot[0]), int(tot[1])
 
     def seal(self, min_count):
         """min_count: an int, or one per channel -> the solid k-mers per channel; the set is plain or tagged from here on (cornetto_kset_seal)"""

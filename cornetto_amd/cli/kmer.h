@@ -69,9 +69,12 @@ static inline int cli_kroll_push(cli_kroll_t *r, unsigned char byte, uint64_t *k
 #define CLI_KCOUNT_CAP CORNETTO_KSET_COUNT_CAP
 #define CLI_KCOUNT_BINS CORNETTO_KSET_HIST_BINS
 
+#define CLI_KCOUNT_CN_BINS CORNETTO_KSET_CN_BINS
+
 typedef struct {
     uint64_t *tab;
     uint32_t *cnt;
+    uint8_t *cop;        /* one channel, from the first cli_kcount_copy(): the copies of the slot's key in the assembly, saturating at CN_BINS - 1 */
     int64_t slots, pos, distinct;
     int channels;
 } cli_kcount_t;
@@ -127,6 +130,46 @@ static inline void cli_kcount_hist(const cli_kcount_t *t, int ch, int64_t *hist)
     }
 }
 
+/* one occurrence of `key` in the assembly ("Completeness and copy-number spectrum" in include/cornetto_accel.h): a key the table does not hold
+ * takes a slot with count 0 and is no distinct key of the reads.  0, or -1 when the table has no room or the bytes cannot be had */
+static inline int cli_kcount_copy(cli_kcount_t *t, uint64_t key)
+{
+    const uint64_t slots = (uint64_t)t->slots;
+    if (!t->cop && !(t->cop = (uint8_t *)calloc((size_t)slots, 1))) return -1;
+    uint64_t s = cli_kmer_mix(key) % slots;
+    for (uint64_t step = 0; step < slots; ++step) {
+        if (t->tab[s] == ~(uint64_t)0) t->tab[s] = key;
+        if (t->tab[s] == key) {
+            if (t->cop[s] < CLI_KCOUNT_CN_BINS - 1) ++t->cop[s];
+            return 0;
+        }
+        s = s + 1 == slots ? 0 : s + 1;
+    }
+    return -1;
+}
+
+static inline void cli_kcount_copies_clear(cli_kcount_t *t)
+{
+    if (t->cop) memset(t->cop, 0, (size_t)t->slots);
+}
+
+/* spec[a * CLI_KCOUNT_BINS + c] of channel `ch` and totals = {solid, found} for the threshold m */
+static inline void cli_kcount_spectrum(const cli_kcount_t *t, int ch, int m, int64_t *spec, int64_t *totals)
+{
+    memset(spec, 0, (size_t)CLI_KCOUNT_CN_BINS * CLI_KCOUNT_BINS * sizeof(int64_t));
+    totals[0] = totals[1] = 0;
+    for (int64_t i = 0; i < t->slots; ++i) {
+        const uint32_t c = t->cnt[(int64_t)ch * t->slots + i];
+        const int a = t->cop ? t->cop[i] : 0;
+        if (!c && !a) continue;
+        spec[(int64_t)a * CLI_KCOUNT_BINS + (c < CLI_KCOUNT_BINS - 1 ? c : CLI_KCOUNT_BINS - 1)]++;
+        if (c && c >= (uint32_t)m) {
+            totals[0]++;
+            totals[1] += a != 0;
+        }
+    }
+}
+
 /* the seal: solid[ch] = keys with count >= m[ch]; the counts are freed, t->tab is the plain or the tagged table */
 static inline void cli_kcount_seal(cli_kcount_t *t, const int *m, int64_t *solid)
 {
@@ -144,6 +187,8 @@ static inline void cli_kcount_seal(cli_kcount_t *t, const int *m, int64_t *solid
     }
     free(t->cnt);
     t->cnt = NULL;
+    free(t->cop);
+    t->cop = NULL;
 }
 
 /* an upper bound of the positions of a file of parental or truth records: the bytes of a plain regular file, else the sum of the record lengths

@@ -1,5 +1,5 @@
 /* qv_main.c — `cornetto qv [-k INT] [-t FILE]... [-c FILE] [-b FILE] [--slots INT] [--accel=no] <truth.fa> <asm.fa> [asm2.fa ...]`, or from reads,
- * `cornetto qv -r reads.fq [-r more.fq] [--min-count INT] [--hist FILE] [...] <asm.fa> [asm2.fa ...]`: the k-mer consensus quality of assemblies
+ * `cornetto qv -r reads.fq [-r more.fq] [--min-count INT] [--hist FILE] [--completeness] [--spectra-cn FILE] [...] <asm.fa> [asm2.fa ...]`: the k-mer consensus quality of assemblies
  * against a truth assembly, or against the k-mers that the sample's own accurate reads hold at least --min-count times.  Not in the reference: its
  * protocol (docs/protocol.md:292-303) runs `yak count`
  * and `yak qv` against the HG002 Q100 assembly for asm-1 .. asm-n, primary and hap1+hap2.  The rule is stated once in include/cornetto_accel.h
@@ -9,6 +9,10 @@
  * (cornetto_kset_add); every assembly is then read the same way and probed against it (cornetto_kset_query).  One device handle serves all files.
  * With -r the set is a counted one (cornetto_kset_open_counted, cornetto_kset_count per batch), its histogram goes to --hist, and the seal with
  * --min-count (cornetto_kset_seal) leaves the plain set that the same probes walk.
+ * With --completeness or --spectra-cn every assembly is read once more, in front of the seal while the counts are still there: its k-mers go into
+ * the copy counts beside them (cornetto_kset_copies per batch), the spectrum of copies against counts is taken at --min-count
+ * (cornetto_kset_spectrum) and the copies are cleared for the next assembly.  The seal drops the k-mers only an assembly held, so the QV pass
+ * behind it answers what it answers without the two options.
  * --accel=no / CORNETTO_ACCEL=no: the same rule on the host, a single-threaded open-addressing set (kmer.h has the counted one) and the sequential
  * reader; the same bytes. */
 #include <errno.h>
@@ -32,6 +36,7 @@ typedef struct {
     int64_t h_pos, h_distinct;
     int reads;                            /* -r: the truth is counted, not inserted */
     cli_kcount_t kc;                      /* host path with -r: the counted table; its key array becomes `tab` at the seal */
+    int64_t *x_solid, *x_found;           /* --completeness / --spectra-cn: per assembly, from the pass in front of the seal */
     /* the assembly being read */
     int64_t contigs, bases, kmers, missing;
     FILE *fc, *fb;
@@ -40,6 +45,14 @@ typedef struct {
 static void qv_overflow(const qv_t *Q)
 {
     CLI_ERROR("the k-mer table of %lld slots overflowed: the truth holds more distinct %d-mers; give a larger table with --slots", (long long)Q->slots, Q->k);
+    exit(EXIT_FAILURE);
+}
+
+/* the same in the copies pass of --completeness / --spectra-cn on the host, where the reads fitted: the k-mers only the assembly holds found no slot */
+static void qv_copies_overflow(const qv_t *Q)
+{
+    CLI_ERROR("the k-mer table of %lld slots overflowed: the assembly holds %d-mers the reads do not, and each takes a slot until the seal; give a larger table with --slots",
+              (long long)Q->slots, Q->k);
     exit(EXIT_FAILURE);
 }
 
@@ -101,6 +114,19 @@ static void asm_scan(cornetto_accel_t *h, const cli_recname_t *r, int64_t n, con
     for (int64_t i = 0; i < n_rows; ++i) bed_row(Q, r[rows[i].ctg].name, (size_t)r[rows[i].ctg].name_len, rows[i].start, rows[i].finish);
     cornetto_free(rows);
     free(km);
+}
+
+static void copies_scan(cornetto_accel_t *h, const cli_recname_t *r, int64_t n, const cornetto_asm_t *a, void *arg)
+{
+    qv_t *Q = (qv_t *)arg;
+    (void)r;
+    (void)n;
+    const int rc = cornetto_kset_copies(h, Q->set, a);
+    if (rc == CORNETTO_E_NOMEM) {          /* the library says which: the assembly-only k-mers found no slot, or the byte a slot could not be had */
+        CLI_ERROR("%s: size the table with --slots", cornetto_accel_last_error(h));
+        exit(EXIT_FAILURE);
+    }
+    cli_accel_check(h, rc, "qv: counting the assembly's k-mers");
 }
 
 /* ---------------------------------------------------------------- the host path: the same rule, one record at a time */
@@ -186,6 +212,23 @@ static void host_file(qv_t *Q, const char *path, int truth)
     cli_fastx_close(fx);
 }
 
+/* the k-mers of every record of an assembly into the copy counts of the counted table */
+static void host_copies_file(qv_t *Q, const char *path)
+{
+    cli_fastx_t *fx = cli_fastx_open(path, 1);
+    cli_rec_t *r;
+    while ((r = cli_fastx_next_checked(fx)) != NULL) {
+        const unsigned char *s = (const unsigned char *)r->seq.s;
+        cli_kroll_t R;
+        cli_kroll_init(&R, Q->k);
+        for (size_t e = 0; e < r->seq.l; ++e) {
+            uint64_t key;
+            if (cli_kroll_push(&R, s[e], &key) && cli_kcount_copy(&Q->kc, key) < 0) qv_copies_overflow(Q);
+        }
+    }
+    cli_fastx_close(fx);
+}
+
 /* ---------------------------------------------------------------- sizing */
 static void sum_lengths(cornetto_accel_t *h, const cli_recname_t *r, int64_t n, const cornetto_asm_t *a, void *arg)
 {
@@ -194,17 +237,24 @@ static void sum_lengths(cornetto_accel_t *h, const cli_recname_t *r, int64_t n, 
     for (int64_t i = 0; i < n; ++i) *(int64_t *)arg += r[i].len;
 }
 
-/* kmer.h: an upper bound of the positions of a truth file */
-int64_t cli_kmer_file_bound(const char *path)
+/* the bytes of a regular file, or -1 for a FIFO or `-`, which can be read only once.  A file that does not exist gets the reference's open error; exit 1 */
+static int64_t regular_size(const char *path)
 {
     struct stat st;
     if (!strcmp(path, "-")) return -1;
-    if (stat(path, &st) != 0) (void)cli_gz_open(path, 1);      /* the reference's open error; exit 1 */
-    if (!S_ISREG(st.st_mode)) return -1;
+    if (stat(path, &st) != 0) (void)cli_gz_open(path, 1);
+    return S_ISREG(st.st_mode) ? (int64_t)st.st_size : -1;
+}
+
+/* kmer.h: an upper bound of the positions of a truth file */
+int64_t cli_kmer_file_bound(const char *path)
+{
+    const int64_t size = regular_size(path);
+    if (size < 0) return -1;
     FILE *fp = cli_fopen_chk(path, "rb");
     const int c0 = fgetc(fp), c1 = fgetc(fp);
     fclose(fp);
-    if (!(c0 == 0x1f && c1 == 0x8b)) return (int64_t)st.st_size;
+    if (!(c0 == 0x1f && c1 == 0x8b)) return size;
     int64_t sum = 0;
     stream_names(path, 1, sum_lengths, &sum);
     return sum;
@@ -224,6 +274,10 @@ static void usage(FILE *fp)
     fprintf(fp, "                              every positional argument is then an assembly\n");
     fprintf(fp, "   --min-count INT            with -r: a k-mer counts as true from INT occurrences in the reads, 1 to 65535 [2]\n");
     fprintf(fp, "   --hist FILE                with -r: write the k-mer count histogram, count<TAB>kmers for counts 1 to 1023 (the last line: 1023 and more)\n");
+    fprintf(fp, "   --completeness             with -r: three more columns, solid found completeness: the reads' k-mers from --min-count occurrences upward,\n");
+    fprintf(fp, "                              those of them the assembly holds, and their share; every assembly is read twice\n");
+    fprintf(fp, "   --spectra-cn FILE          with -r: write the copy-number spectrum, count<TAB>cn0..cn5+ for counts 0 to 1023: the k-mers the reads hold\n");
+    fprintf(fp, "                              `count` times and the assembly 0, 1, 2, 3, 4 and more than 4 times (one assembly only; it is read twice)\n");
     fprintf(fp, "   --slots INT                slots of the k-mer table, 8 bytes each, 12 with -r [twice the bases of the truth or the reads;\n");
     fprintf(fp, "                              about 1.5 times the expected distinct k-mers is the usual figure]\n");
     fprintf(fp, "   --accel=no                 run on the host\n");
@@ -240,8 +294,10 @@ static void usage_fail(const char *msg)
 int qv_main(int argc, char *argv[])
 {
     static const struct option lo[] = {{"help", no_argument, 0, 'h'}, {"slots", required_argument, 0, 1000}, {"accel", required_argument, 0, 1001},
-                                       {"min-count", required_argument, 0, 1002}, {"hist", required_argument, 0, 1003}, {0, 0, 0, 0}};
-    const char *k_arg = "21", *c_arg = NULL, *b_arg = NULL, *slots_arg = NULL, *mc_arg = NULL, *hist_arg = NULL;
+                                       {"min-count", required_argument, 0, 1002}, {"hist", required_argument, 0, 1003}, {"completeness", no_argument, 0, 1004},
+                                       {"spectra-cn", required_argument, 0, 1005}, {0, 0, 0, 0}};
+    const char *k_arg = "21", *c_arg = NULL, *b_arg = NULL, *slots_arg = NULL, *mc_arg = NULL, *hist_arg = NULL, *spec_arg = NULL;
+    int completeness = 0;
     const char **truth_mem = (const char **)cli_xmalloc(2 * ((size_t)argc + 1) * sizeof(char *)), **truth = truth_mem, **reads = truth + argc + 1;
     int n_truth = 1, n_reads = 0, c, li = 0;
     FILE *fp_help = stderr;
@@ -255,6 +311,8 @@ int qv_main(int argc, char *argv[])
         else if (c == 1000) slots_arg = optarg;
         else if (c == 1002) mc_arg = optarg;
         else if (c == 1003) hist_arg = optarg;
+        else if (c == 1004) completeness = 1;
+        else if (c == 1005) spec_arg = optarg;
         else if (c == 1001) {
             if (!strcmp(optarg, "no") || !strcmp(optarg, "n")) cli_host_set(1);
             else if (!strcmp(optarg, "yes") || !strcmp(optarg, "y")) cli_host_set(0);
@@ -267,6 +325,7 @@ int qv_main(int argc, char *argv[])
         exit(EXIT_SUCCESS);
     }
     if (!n_reads && (mc_arg || hist_arg)) usage_fail("--min-count and --hist go with -r: a truth assembly holds every k-mer once");
+    if (!n_reads && (completeness || spec_arg)) usage_fail("--completeness and --spectra-cn go with -r: a truth assembly holds every k-mer once");
     if (n_reads && n_truth > 1) usage_fail("-t names a further truth assembly; it does not go with -r");
     if (argc - optind < (n_reads ? 1 : 2)) {
         usage(stderr);
@@ -291,6 +350,11 @@ int qv_main(int argc, char *argv[])
     const long long k = strtoll(k_arg, &end, 10);
     if (*end || end == k_arg || k < 11 || k > 31 || !(k & 1)) usage_fail("-k: k is an odd number from 11 to 31");
     if ((c_arg || b_arg) && n_asm != 1) usage_fail("-c and -b take one assembly");
+    if (spec_arg && n_asm != 1) usage_fail("--spectra-cn takes one assembly");
+    const int extras = completeness || spec_arg;
+    for (int i = 0; extras && i < n_asm; ++i)
+        if (regular_size(asms[i]) < 0)          /* (not cli_kmer_file_bound(): it would inflate a whole gzip assembly to say so) */
+            usage_fail("--completeness and --spectra-cn read an assembly twice: it cannot be a FIFO or `-`");
     long long slots = 0;
     if (slots_arg) {
         errno = 0;
@@ -359,6 +423,38 @@ int qv_main(int argc, char *argv[])
         const int m = (int)min_count;
         const int32_t m32 = (int32_t)min_count;
         int64_t solid = 0;
+        if (extras) {
+            /* in front of the seal, while the counts are there: per assembly its copies, the spectrum at the threshold, and the copies cleared */
+            int64_t *spec = (int64_t *)cli_xmalloc((size_t)CORNETTO_KSET_CN_BINS * CORNETTO_KSET_HIST_BINS * sizeof(int64_t)), totals[2];
+            Q.x_solid = (int64_t *)cli_xmalloc(2 * (size_t)n_asm * sizeof(int64_t));
+            Q.x_found = Q.x_solid + n_asm;
+            for (int i = 0; i < n_asm; ++i) {
+                if (host) {
+                    host_copies_file(&Q, asms[i]);
+                    cli_kcount_spectrum(&Q.kc, 0, m, spec, totals);
+                    cli_kcount_copies_clear(&Q.kc);
+                } else {
+                    stream_records_on(h, asms[i], 1, copies_scan, &Q);
+                    cli_accel_check(h, cornetto_kset_spectrum(h, Q.set, 0, m32, spec, totals), "qv: the copy-number spectrum");
+                    cli_accel_check(h, cornetto_kset_copies_clear(h, Q.set), "qv: clearing the copy counts");
+                }
+                Q.x_solid[i] = totals[0];
+                Q.x_found[i] = totals[1];
+                if (!spec_arg) continue;
+                FILE *fs = cli_fopen_chk(spec_arg, "w");
+                fprintf(fs, "#count\tcn0\tcn1\tcn2\tcn3\tcn4\tcn5+\n");
+                for (int cbin = 0; cbin < CORNETTO_KSET_HIST_BINS; ++cbin) {
+                    fprintf(fs, "%d", cbin);
+                    for (int a = 0; a < CORNETTO_KSET_CN_BINS; ++a) fprintf(fs, "\t%lld", (long long)spec[a * CORNETTO_KSET_HIST_BINS + cbin]);
+                    fputc('\n', fs);
+                }
+                if (fclose(fs) != 0) {
+                    CLI_ERROR("%s", "writing the --spectra-cn file failed");
+                    exit(EXIT_FAILURE);
+                }
+            }
+            free(spec);
+        }
         if (host) {
             cli_kcount_seal(&Q.kc, &m, &solid);
             Q.tab = Q.kc.tab;
@@ -375,14 +471,20 @@ int qv_main(int argc, char *argv[])
     Q.fc = c_arg ? cli_fopen_chk(c_arg, "w") : NULL;
     Q.fb = b_arg ? cli_fopen_chk(b_arg, "w") : NULL;
     if (Q.fc) fprintf(Q.fc, "#contig\tlength\tkmers\tmissing\terror\tqv\n");
-    printf("#file\tcontigs\tbases\tkmers\tmissing\terror\tqv\n");
+    printf(completeness ? "#file\tcontigs\tbases\tkmers\tmissing\terror\tqv\tsolid\tfound\tcompleteness\n" : "#file\tcontigs\tbases\tkmers\tmissing\terror\tqv\n");
     for (int i = 0; i < n_asm; ++i) {
         Q.contigs = Q.bases = Q.kmers = Q.missing = 0;
         if (host) host_file(&Q, asms[i], 0);
         else stream_records_on(h, asms[i], 1, asm_scan, &Q);
         char e[48], q[48];
         qv_format(Q.kmers, Q.missing, Q.k, e, q, sizeof(e));
-        printf("%s\t%lld\t%lld\t%lld\t%lld\t%s\t%s\n", asms[i], (long long)Q.contigs, (long long)Q.bases, (long long)Q.kmers, (long long)Q.missing, e, q);
+        printf("%s\t%lld\t%lld\t%lld\t%lld\t%s\t%s", asms[i], (long long)Q.contigs, (long long)Q.bases, (long long)Q.kmers, (long long)Q.missing, e, q);
+        if (completeness) {
+            printf("\t%lld\t%lld\t", (long long)Q.x_solid[i], (long long)Q.x_found[i]);
+            if (Q.x_solid[i]) printf("%.6f", (double)Q.x_found[i] / (double)Q.x_solid[i]);
+            else printf("NA");
+        }
+        putchar('\n');
         fflush(stdout);
     }
     if ((Q.fc && fclose(Q.fc) != 0) || (Q.fb && fclose(Q.fb) != 0)) {
@@ -391,6 +493,7 @@ int qv_main(int argc, char *argv[])
     }
     if (Q.set) cornetto_kset_free(h, Q.set);
     free(Q.tab);
+    free(Q.x_solid);
     free(truth_mem);
     return EXIT_SUCCESS;
 }

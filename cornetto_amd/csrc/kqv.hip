@@ -132,6 +132,7 @@ void cornetto_kset_free(cornetto_accel_t *h, cornetto_kset_t *s)
     if (s->d_tab) (void)hipFree(s->d_tab);
     if (s->d_stat) (void)hipFree(s->d_stat);
     if (s->d_cnt) (void)hipFree(s->d_cnt);
+    if (s->d_cop) (void)hipFree(s->d_cop);
     if (s->d_tiles) (void)hipFree(s->d_tiles);
     s->pref.release();
     delete s;

@@ -15,6 +15,7 @@
 //   kq_bit()      word and mask of position `pos` of a contig whose first tile is `tile0` in the bitmap (KQ_TILE bits per tile).
 //   kq_insert_tag(), kq_lookup_tag()   the same table with a 2-bit tag in bits 63:62 of a slot, for `cornetto trioeval` (ktrio.hip): below.
 //   kq_deal(), kq_insert_at(), kq_bump(), kq_hist_bin(), kq_seal_word()   the counted table of `qv -r` / `trioeval --pat-reads` (kcount.hip): at the end.
+//   kq_copy_bump(), kq_copy_word(), kq_copy_shift(), kq_copy_of(), kq_spec_cell()   the copies of `qv -r --completeness / --spectra-cn`: behind them.
 // The empty slot is ~0: no key, k <= 31 makes every key smaller than 2^62.
 #pragma once
 #include <cstdint>
@@ -291,6 +292,46 @@ KQ_HD static inline uint64_t kq_seal_word(uint64_t key, int channels, int tag)
 {
     if (!tag) return KQ_TOMB;
     return channels == 1 ? key : key | (uint64_t)tag << KQ_TAG_SHIFT;
+}
+
+// ---- the copies of `cornetto qv -r --completeness / --spectra-cn` (kcount.hip: kq_copies, kq_spectrum; include/cornetto_accel.h states the rule).
+// Beside the counts of a one-channel counted table stands one BYTE per slot, copies[slot] = min(occurrences of the slot's key in the assembly,
+// KQ_CN_MAX), packed four to a uint32_t: slot i is byte i & 3 (bits 8 * (i & 3) ..) of word i >> 2, ceil(slots / 4) words.
+//   kq_copy_bump()   one occurrence into the byte at `shift` of `word`: a relaxed load of the word; leave if the byte reads KQ_CN_MAX (or more: it
+//                    never does); else cas(word, seen, seen + (1 << shift)) -> the word that was there; done when that is `seen`, else it becomes
+//                    `seen` and the step repeats.  Termination and exactness: the bytes only grow between two clears.  A compare-and-swap fails
+//                    only when the word differs from `seen`, i.e. when another lane's compare-and-swap on that word has succeeded since `seen`
+//                    was read.  A success raises one byte by one and happens only on a word whose byte was seen below KQ_CN_MAX IN THAT SAME WORD
+//                    VALUE — the swap stores seen + 1 in the byte only if the word still is `seen` — so a byte takes at most KQ_CN_MAX = 5
+//                    successes between two clears and a word at most 20: no lane fails more than 19 times.  Every occurrence either succeeds
+//                    once or leaves at a byte that reads 5, and a byte below 5 turns no occurrence away, so the stored byte is exactly
+//                    min(occurrences, 5).  There is no overshoot to bound, unlike kq_bump(): an add of 1 << shift behind a load check could pass 5
+//                    by the lanes in flight and carry into the neighbour's byte;
+//   kq_spec_cell()   the cell of a key in the 6 x 1024 spectrum: min(copies, 5) * KQ_BINS + kq_hist_bin(stored count).  A slot with count 0 and
+//                    copies 0 — empty, or an assembly-only key after a clear — is in no cell: the kernels skip it.
+constexpr int KQ_CN_BINS = CORNETTO_KSET_CN_BINS;
+constexpr uint32_t KQ_CN_MAX = KQ_CN_BINS - 1;
+static_assert(KQ_CN_MAX < 255, "a copy count is a byte");
+
+KQ_HD static inline uint64_t kq_copy_words(uint64_t slots) { return (slots + 3) >> 2; }
+KQ_HD static inline uint64_t kq_copy_word(uint64_t slot) { return slot >> 2; }   // < kq_copy_words(slots) for slot < slots
+KQ_HD static inline int kq_copy_shift(uint64_t slot) { return (int)(slot & 3) * 8; }
+KQ_HD static inline uint32_t kq_copy_of(uint32_t word, uint64_t slot) { return (word >> kq_copy_shift(slot)) & 0xFFu; }
+
+template <class Load, class Cas>
+KQ_HD static inline void kq_copy_bump(uint32_t *word, int shift, Load load, Cas cas)
+{
+    uint32_t seen = load(word);
+    while (((seen >> shift) & 0xFFu) < KQ_CN_MAX) {
+        const uint32_t old = cas(word, seen, seen + ((uint32_t)1 << shift));
+        if (old == seen) return;
+        seen = old;
+    }
+}
+
+KQ_HD static inline int kq_spec_cell(uint32_t copies, uint32_t stored)
+{
+    return (int)(copies < KQ_CN_MAX ? copies : KQ_CN_MAX) * KQ_BINS + kq_hist_bin(stored);
 }
 
 }  // namespace

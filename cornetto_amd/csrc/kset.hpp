@@ -17,6 +17,8 @@ struct cornetto_kset {
     uint64_t *d_tab = nullptr;
     unsigned long long *d_stat = nullptr;   // [0] positions inserted, [1] distinct, [2] overflow, [3], [4] solid keys per channel (kq_seal)
     uint32_t *d_cnt = nullptr;              // a counted set before its seal: channels * slots counts, count[ch * slots + slot]
+    uint32_t *d_cop = nullptr;              // ... of one channel, from its first kset_copies: a byte of copies per slot, four to a word (kqv.hpp)
+    bool copied = false;                    // kset_copies has run: the table may hold assembly-only keys, kset_count is refused
     int32_t channels = 0;                   // 0: not a counted set
     bool counted = false;                   // opened by cornetto_kset_open_counted (also after the seal)
     int64_t stats[3] = {0, 0, 0};           // host copy of [0], [1]; [2] = slots

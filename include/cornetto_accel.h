@@ -912,6 +912,41 @@ int cornetto_kset_hist(cornetto_accel_t *h, cornetto_kset_t *s, int32_t channel,
 int cornetto_kset_seal(cornetto_accel_t *h, cornetto_kset_t *s, const int32_t *min_count, int64_t *solid);
 
 /* ---------------------------------------------------------------------------------------------------
+ * k-mer completeness and copy-number spectrum of an assembly against the counted reads: `cornetto qv -r ... --completeness --spectra-cn FILE`.
+ * An EXTENSION (Merqury's completeness and spectra-cn classes; parity with Merqury or yak is unpinned).  k, the valid bytes, the positions and
+ * the canonical code are those of `cornetto qv` above.  A counted set of ONE channel, BEFORE its seal, may additionally hold copies[key].
+ * THE RULE:
+ *   - copies[key] = min(occurrences of key at the positions of every contig handed to cornetto_kset_copies() since the last clear,
+ *     CORNETTO_KSET_CN_BINS - 1).  The classes are Merqury's: read-only (0), 1, 2, 3, 4, more than 4;
+ *   - a key of the assembly that the table does not hold is inserted with count 0: an ASSEMBLY-ONLY key.  It takes a slot; a table without room is
+ *     the overflow status of cornetto_kset_count() (CORNETTO_E_NOMEM, the set unusable, never a hang);
+ *   - assembly-only keys do not count in the distinct keys of cornetto_kset_stats(), they are in no bin of cornetto_kset_hist() (which skips count 0),
+ *     and the seal turns them into tombstones: a set that has seen copies calls seals into exactly the set it would have sealed into without
+ *     them, and every later cornetto_kset_query() answer is the same;
+ *   - spec[a * CORNETTO_KSET_HIST_BINS + c], a = 0 .. CORNETTO_KSET_CN_BINS - 1, c = 0 .. CORNETTO_KSET_HIST_BINS - 1: the number of keys with
+ *     min(copies, CN_BINS - 1) == a and min(count, HIST_BINS - 1) == c.  The cell a = 0, c = 0 stays 0 (a key that is in neither, e.g. an
+ *     assembly-only key of an earlier assembly after a clear); row c = 0 is the assembly-only keys; for c >= 1 the sum over a of spec[a][c] is
+ *     hist[c]; before any copies call spec[0][c] == hist[c];
+ *   - with a threshold m in 1 .. CORNETTO_KSET_COUNT_CAP: solid = the keys with min(count, CAP) >= m, which is what the seal with m will return;
+ *     found = those of them with copies >= 1.  Both are exact for every m, also above HIST_BINS - 1 where the bins no longer tell;
+ *   - completeness = found / solid, on the host in double, printed with %.6f, or NA when solid is 0.
+ * Every number is an integer independent of batch boundaries and of the order of records, contigs and probes.
+ * The state machine: kset_copies, kset_copies_clear and kset_spectrum on a plain, tagged, sealed or two-channel set return
+ * CORNETTO_E_UNSUPPORTED; so does kset_count after the first kset_copies (the distinct-keys stat would no longer mean what it says); a channel
+ * out of range, m outside 1 .. CAP and null arguments are CORNETTO_E_ARG; a set whose table has overflowed refuses everything.
+ * On the device (csrc/kcount.hip, kqv.hpp): one byte per slot, packed four to a 32-bit word (13 bytes a slot), allocated and zeroed at the first
+ * kset_copies, freed by the seal; a byte is raised by a compare-and-swap of its word, so it never passes CN_BINS - 1 and never carries.
+ * ------------------------------------------------------------------------------------------------- */
+#define CORNETTO_KSET_CN_BINS 6
+/* the k-mers of every contig of `a` into copies[] (kq_copies); may be called repeatedly, once per batch of a streamer.  CORNETTO_E_NOMEM: the
+ * copies could not be allocated (the message says how many bytes were wanted), or the table overflowed and the set is unusable. */
+int cornetto_kset_copies(cornetto_accel_t *h, cornetto_kset_t *s, const cornetto_asm_t *a);
+/* every copy count to 0; the keys stay, assembly-only ones included */
+int cornetto_kset_copies_clear(cornetto_accel_t *h, cornetto_kset_t *s);
+/* spec[0 .. CORNETTO_KSET_CN_BINS * CORNETTO_KSET_HIST_BINS) and totals[0 .. 2) = {solid, found} for min_count (kq_spectrum) */
+int cornetto_kset_spectrum(cornetto_accel_t *h, cornetto_kset_t *s, int32_t channel, int32_t min_count, int64_t *spec, int64_t *totals);
+
+/* ---------------------------------------------------------------------------------------------------
  * Switch and Hamming error of a phased assembly against parental k-mers: `cornetto trioeval`.  An EXTENSION (the reference's protocol runs
  * `yak trioeval pat.yak mat.yak asm.fa` at this step, docs/protocol.md:292-308; yak works from read k-mer counts with thresholds, this works
  * from parental or truth-haplotype ASSEMBLIES, as `cornetto qv hg002.mat.fa -t hg002.pat.fa` does; parity with yak is unpinned).  THE RULE:
